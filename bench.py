@@ -15,6 +15,11 @@ render its share, ONE RCCL sum of the destination bus per step inside the produc
 render"), the result lands in rank 0's page-locked host buffer.  The process group (gloo) only carries the communicator id,
 the barrier, the max-over-ranks time and the float64 check's input sum.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) builds the graph, warms up, times the N steps, writes the last step's
+output when --dump-outputs DIR is given (DIR/bus.npy: the float32 [2][frames] destination bus the caller receives; a fixed, seeded
+sample of it above 64 MB) and prints the line.  The headline needs nothing else: `variants`, `parity` (the float64 check of the
+last timed step included) and `cpu_baseline` below are computed only with --full.
+
 One JSON line on stdout (rank 0).  Besides the contract keys:
   roofline       -- the dominant kernel of the EXECUTED formulation; its name is what the library reports it ran
                     (ga_stats.stage_kernel).  `achieved` = the HBM bytes the launch HAS to move in that formulation (inputs read
@@ -414,6 +419,26 @@ def attach_pmc_traffic(roof, profile_json):
     return roof
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (float64 kept), at most DUMP_LIMIT_BYTES in all.  Outputs above
+    the limit are replaced by a fixed, seeded sample of their elements (flattened, ascending index order): the same elements for
+    the same shapes, so two builds still compare element for element."""
+    arrays = {k: np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES / total
+        for k, a in arrays.items():
+            idx = np.unique(np.random.default_rng(1234).integers(0, a.size, int(a.size * keep)))
+            arrays[k] = a.reshape(-1)[idx]
+        sys.stderr.write(f"bench.py: --dump-outputs: {total} bytes of output, a seeded sample of {keep:.3f} of the elements written\n")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def timed_steps(ctx, step, sync, steps, warmup):
     for _ in range(warmup):
         step()
@@ -498,8 +523,9 @@ def oracle_short_form(build, channels, frames, options=None):
     return (frames - 128) / dt, dt, G.rms(ref - got), G.rms(ref), st
 
 
-def run_variant(name, torch, G, frames, steps, warmup, build, channels, options, describe, truth=None, extra=None):
-    """one more measurement on a context of its own: same step loop, same stage table, its own dominant kernel"""
+def run_variant(name, torch, G, frames, steps, warmup, build, channels, options, describe, truth=None, extra=None, dump=None):
+    """one more measurement on a context of its own: same step loop, same stage table, its own dominant kernel; `dump`: directory
+    for the output of the last timed step (--dump-outputs)"""
     from graphaudio_amd import OfflineAudioContext
     from tests import _f64model as M
     t_build = time.perf_counter()
@@ -519,6 +545,8 @@ def run_variant(name, torch, G, frames, steps, warmup, build, channels, options,
         ctx.Synchronize()
         torch.cuda.synchronize()
     dt, t_enq, st0, st1 = timed_steps(ctx, lambda: ctx.Render(out, frames), sync, steps, warmup)
+    if dump:
+        dump_outputs(dump, {"bus": out})
     stages, whole, _, per_step = stage_table(st0, st1, steps)
     rec = {"description": describe, "ms_per_step": dt / steps * 1e3, "frames_per_s": frames * steps / dt, "steps": steps, "warmup": warmup,
            "frames_per_step": frames, "host_issue_ms_per_step": t_enq / steps * 1e3,
@@ -537,7 +565,7 @@ def run_variant(name, torch, G, frames, steps, warmup, build, channels, options,
     return rec
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -571,7 +599,18 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="ga_set_option on the main context (measurements)")
     ap.add_argument("--library", default="", help="load this build of the library instead of the product (tools/build_variant.sh; measurements)")
     ap.add_argument("--force-dist", action="store_true", help="exercise the sharded-render path (ga_render_reduce) even with one rank")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the CPU baselines, the float64 check of the last timed step, the parity "
+                    "against the CPU oracle and the variants (--no-cpu-baseline / --no-check / --no-variants leave parts out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the output of the last timed step as DIR/bus.npy "
+                    "(float32 [channels][frames])")
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run times the headline steps only
+        args.no_cpu_baseline = args.no_variants = args.no_check = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -595,7 +634,8 @@ def main():
         for kv in args.opt:
             k, v = kv.split("=", 1)
             opts[k] = float(v)
-        print(json.dumps(run_variant(args.only_variant, torch, G, frames, args.steps, args.warmup, build, ch, opts, args.only_variant)))
+        print(json.dumps(run_variant(args.only_variant, torch, G, frames, args.steps, args.warmup, build, ch, opts, args.only_variant,
+                                     dump=args.dump_outputs)))
         return
     all_cores = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -702,6 +742,8 @@ def main():
         if xsum is not None:   # the float64 check needs the sum over ALL ranks' voices
             xs = torch.from_numpy(xsum)
             dist.reduce(xs, dst=0, op=dist.ReduceOp.SUM)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"bus": host_out})
 
     if rank == 0:
         from tests import _f64model as M

@@ -1,6 +1,6 @@
 """ga_render_reduce with a LIVE communicator: two ranks as two threads of this process, one context per GPU, RCCL between them.
 Needs two MI355X in one process -- skipped on the one-GPU boxes of this build (the round's driver runs the N = 2, 4, 8 scaling
-bench on a whole node: bench.py --gpus N goes through exactly this path, and checks its sum against float64 mathematics)."""
+bench on a whole node: bench.py --gpus N goes through exactly this path, and with --full checks its sum against float64 mathematics)."""
 import threading
 
 import numpy as np
