@@ -168,8 +168,6 @@ void Context::chunkTopology(ChunkRun& r) {
       int lvl = 0, dep = 0;
       for (auto& p : nd.params)
         if (!p.modulation.empty()) {
-          if (nd.type == GA_NODE_BUFFER_SOURCE)   // a modulated playbackRate makes the resampler's consumption depend on audio data
-            fail(GA_ERR_UNSUPPORTED, "audio-rate modulation of AudioBufferSourceNode.playbackRate is not on the device path");
           for (auto& m : p.modulation) {
             if (!dfs(m.first)) continue;
             NodeS& up = *nodes[m.first];
@@ -274,6 +272,61 @@ void Context::chunkTopology(ChunkRun& r) {
   }
   maxDepth = topoMaxDepth;
   maxLevel = topoMaxLevel;
+  // ---- playbackRate modulated by a signal (AudioBufferSourceNode / AudioStreamSourceNode): a two-stage chunk (runTwoStageChunk) ----
+  // The rate decides how many samples each block consumes and where a one-shot source ends, and the planner needs that before it can
+  // plan the rest: the modulation inputs' cone is rendered first.  The cases that cannot be split so are refused here, before any state
+  // moves (the context stays usable).
+  if (rateModsVersion != graphVersion || rateCone.size() != nodes.size()) {
+    topoRateMods.clear();
+    for (int id : topo) {
+      const NodeS& nd = *nodes[id];
+      if ((nd.type == GA_NODE_BUFFER_SOURCE || nd.type == GA_NODE_STREAM_SOURCE) && !nd.params.empty() && !nd.params[0].modulation.empty())
+        topoRateMods.push_back({id, 0});
+    }
+    // the cone: every node the modulation inputs reach backwards (params before inputs, as Nodes/AudioNode.cs:167-175 pulls them)
+    rateCone.assign(nodes.size(), 0);
+    std::vector<int> stack;
+    for (const auto& pm : topoRateMods)
+      for (const auto& m : nodes[pm.first]->params[pm.second].modulation)
+        if (!rateCone[m.first]) {
+          rateCone[m.first] = 1;
+          stack.push_back(m.first);
+        }
+    while (!stack.empty()) {
+      const NodeS& nd = *nodes[stack.back()];
+      stack.pop_back();
+      auto visit = [&](int up) {
+        if (!rateCone[up]) {
+          rateCone[up] = 1;
+          stack.push_back(up);
+        }
+      };
+      for (const auto& p : nd.params)
+        for (const auto& m : p.modulation) visit(m.first);
+      for (const auto& in : nd.inputs)
+        for (const Conn& cn : in.connected) visit(cn.node);
+    }
+    rateModsVersion = graphVersion;
+  }
+  if (!topoRateMods.empty()) {
+    for (const auto& pm : topoRateMods)
+      if (rateCone[pm.first])
+        fail(GA_ERR_UNSUPPORTED, "a modulated playbackRate depends on a source whose own playbackRate is modulated, or on its own output "
+                                 "(nested modulated rates / feedback through the rate) -- not on the device path");
+    if (topoHasCycles)
+      fail(GA_ERR_UNSUPPORTED, "a modulated playbackRate in a graph with a feedback loop is not on the device path");
+    for (int id : topo)
+      if (rateCone[id] && nodes[id]->type == GA_NODE_CONVOLVER)
+        fail(GA_ERR_UNSUPPORTED, "a ConvolverNode in front of a modulated playbackRate is not on the device path");
+    for (const auto& pm : topoRateMods) {
+      NodeS& nd = *nodes[pm.first];
+      if (nd.type != GA_NODE_BUFFER_SOURCE || !nd.loop || nd.bufId < 0 || !buffers[nd.bufId]) continue;
+      const SrcGeom g = sourceGeom(*this, nd, *buffers[nd.bufId]);
+      if (g.loopEndFrame <= g.loopStartFrame)   // (the replay's guard would fire inside the device walk: refused while nothing has moved)
+        fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
+    }
+    r.rateMods = topoRateMods;
+  }
   // automated runs that ended hand their state back to the host: only nodes whose state went to the device are looked at
   // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, NodeS::bqDynSeq / panDynSeq, not a flag to reset)
   for (size_t i = 0; i < deviceStateNodes.size();) {
@@ -343,7 +396,8 @@ void Context::chunkSimulate(ChunkRun& r) {
     if (r.srcIndex.empty()) r.srcIndex.assign(nodes.size(), -1);
     r.srcIndex[id] = (int)srcIds.size();
     srcIds.push_back(id);
-    srcPlans.push_back(scheduled ? planScheduled(*this, nd, n, bt) : planSource(*this, nd, n, bt));
+    const RateModIn* rm = (id < (int)r.rmOf.size() && r.rmOf[id] >= 0) ? &r.rmIn[r.rmOf[id]] : nullptr;
+    srcPlans.push_back(scheduled ? planScheduled(*this, nd, n, bt) : planSource(*this, nd, n, bt, rm));
     for (const SrcSpan& sp : nd.spans)
       if (sp.b0 > 0 && sp.b0 < n) breaks.push_back(sp.b0);
     if (srcPlans.back().partialBlock >= 0) {
@@ -354,23 +408,33 @@ void Context::chunkSimulate(ChunkRun& r) {
   for (int id : topo) {   // AudioStreamNodeBase: replay on indices; a change of channel count / silence is a segment break
     NodeS& nd = *nodes[id];
     if (nd.type != GA_NODE_STREAM_SOURCE) continue;
-    for (auto& p : nd.params)
-      if (!p.modulation.empty()) fail(GA_ERR_UNSUPPORTED, "audio-rate modulation of AudioStreamSourceNode.playbackRate is not on the device path");
+    // (a modulated rate: the values the first stage read back)
+    nd.stRateMod = (id < (int)r.rmOf.size() && r.rmOf[id] >= 0) ? r.rmIn[r.rmOf[id]].rates : nullptr;
+    if (!nd.stRateMod && !nd.params.empty() && !nd.params[0].modulation.empty()) fail(GA_ERR_DEVICE, "internal: modulated stream rate without its values");
     streamReplay(nd, n, bt, false);
     r.streamIds.push_back(id);
     for (int64_t b = 1; b < n; b++)
       if (nd.stInfo[b].outCh != nd.stInfo[b - 1].outCh || nd.stInfo[b].silent != nd.stInfo[b - 1].silent) breaks.push_back(b);
   }
+  if (r.pre)   // the second stage breaks where the first stage's segments do: the rendered nodes' views change there
+    for (int64_t b : r.pre->preB0)
+      if (b > 0 && b < n) breaks.push_back(b);
   std::sort(breaks.begin(), breaks.end());
   breaks.erase(std::unique(breaks.begin(), breaks.end()), breaks.end());
   std::unordered_map<int64_t, std::vector<int>> goneAt;
   for (size_t i = 0; i < srcIds.size(); i++)
     if (srcPlans[i].gone && srcPlans[i].goneAt < n) goneAt[srcPlans[i].goneAt].push_back(srcIds[i]);
+  // The first stage of a two-stage chunk ends where one of its sources is disposed: a disposal disconnects the node from consumers the
+  // second stage has yet to evaluate for the blocks before it.  (At block 0 both stages see it.)
+  if (r.stage == 1)
+    for (const auto& kv : goneAt)
+      if (kv.first > 0) n = std::min(n, kv.first);
 
   r.tmSrc = nowMs();
   chunkPhase = 1;   // from here on persistent control state moves: a failure is sticky (see runChunk)
   // ---- simulate ----
   Sim sim{*this, n};
+  sim.pre = r.pre;
   std::vector<int64_t> extraBreaks;
   sim.extraBreaks = &extraBreaks;
   sim.blockTimes = &bt;
@@ -380,7 +444,8 @@ void Context::chunkSimulate(ChunkRun& r) {
     uint64_t prevHash = lastHash;
     const size_t kMaxSegs = 96;
     while (b < n) {
-      if (segs.size() >= kMaxSegs) {  // too fragmented: stop the chunk here, the caller continues with a new one
+      if (segs.size() >= kMaxSegs && r.stage != 2) {  // too fragmented: stop the chunk here, the caller continues with a new one
+        // (not in the second stage of a two-stage chunk: the first stage has rendered its blocks)
         n = b;
         break;
       }
@@ -400,7 +465,7 @@ void Context::chunkSimulate(ChunkRun& r) {
       // the first block of a steady chunk: nothing can have moved since the previous chunk's last segment (see Context::lastSegNodes)
       // -- its records are taken over, the traversal is skipped
       bool replayed = false;
-      if (b == 0 && simReplay && lastSegStable && !lastSegNodes.empty() && lastSegEpoch == apiEpoch && lastSegGraphVersion == graphVersion &&
+      if (b == 0 && r.stage == 0 && simReplay && lastSegStable && !lastSegNodes.empty() && lastSegEpoch == apiEpoch && lastSegGraphVersion == graphVersion &&
           !topoHasStreams && lastSegNodes.size() == topo.size() && g == goneAt.end()) {
         bool same = true;
         for (const NodeSeg& ns : lastSegNodes) {   // every source still in the phase (and on the buffer) the records say
@@ -455,7 +520,8 @@ void Context::chunkSimulate(ChunkRun& r) {
       if (!replayed) {
         inRender = true;
         try {
-          sim.evalNode(0);
+          if (r.stage == 1) sim.evalProbe(r.rateMods);
+          else sim.evalNode(0);
         } catch (...) {
           inRender = false;
           topoVersion = 0;   // nodes may be left marked as processing: rebuild (and reset) everything next time
@@ -480,7 +546,23 @@ void Context::chunkSimulate(ChunkRun& r) {
       }
       sg.b1 = std::min(nb, n);
       prevHash = sg.hash;
-      minDestCh = std::min(minDestCh, sg.nodes.back().outCh);
+      if (r.stage == 1) {   // the cone's output state in this segment, for the second stage (Sim::restorePre)
+        if (r.preRow.empty()) {
+          r.preRow.assign(nodes.size(), -1);
+          int row = 0;
+          for (int id : topo) {
+            r.preRow[id] = row;
+            row += (int)nodes[id]->outputs.size();
+          }
+        }
+        std::vector<ChunkRun::PreOut> snap;
+        for (int id : topo)
+          for (const OutputS& o : nodes[id]->outputs) snap.push_back(ChunkRun::PreOut{o.bufCh, o.silent, o.zero});
+        r.preSnap.push_back(std::move(snap));
+        r.preB0.push_back(sg.b0);
+      } else {
+        minDestCh = std::min(minDestCh, sg.nodes.back().outCh);
+      }
       b = sg.b1;
       segs.push_back(std::move(sg));
     }
@@ -491,7 +573,7 @@ void Context::chunkSimulate(ChunkRun& r) {
       for (int id : r.streamIds) streamReplay(*nodes[id], n, bt, false);
     }
   }
-  chunkMinDestCh = minDestCh;
+  if (r.stage != 1) chunkMinDestCh = minDestCh;
   r.tmSim = nowMs();
 
 }
@@ -545,7 +627,7 @@ void Context::chunkResources(ChunkRun& r) {
   }
 
   // ---- device resources for this chunk ----
-  resetSlabs(*this, frames);
+  if (r.stage != 2) resetSlabs(*this, frames);   // (the second stage reads the first stage's slabs: none is handed out again)
   if (zerosLen < frames) {
     if (zeros) {
       GA_HIP(hipStreamSynchronize(stream));
@@ -564,7 +646,8 @@ void Context::chunkResources(ChunkRun& r) {
   while ((int)busSlabs.size() < 32 && (int)busSlabs.size() < std::max(destOutCh, 2)) busSlabs.push_back((float*)dalloc((size_t)busCapFrames * 4));
   {
     int mx = 0;
-    for (auto& sg : segs) mx = std::max(mx, sg.nodes.back().outCh);
+    for (auto& sg : segs)
+      if (r.stage != 1) mx = std::max(mx, sg.nodes.back().outCh);
     while ((int)busSlabs.size() < mx) busSlabs.push_back((float*)dalloc((size_t)busCapFrames * 4));
   }
 
@@ -707,7 +790,16 @@ void Context::chunkCommit(ChunkRun& r) {
     PlayBuf* pb = s.bufId >= 0 ? buffers[s.bufId].get() : nullptr;
     bool rate1 = true;
     if (pb) rate1 = sourceGeom(*this, s, *pb).effectiveRate == 1.0;
-    if (s.gsr) {
+    if (s.gsr && s.gsrWalked >= 0) {   // walked on the device (a modulated rate): the state after the walked blocks
+      if (played == s.gsrWalked) {
+        s.playbackPosition = s.gsrTail.pp;
+        for (int k = 0; k < 4; k++) s.gsrW[k] = s.gsrTail.w[k];
+        s.gsrPos = s.gsrTail.pos;
+        s.gsrReady = s.gsrTail.ready;
+      } else if (!(po.gone && po.goneAt <= n)) {   // (a source that is gone leaves nothing to resume)
+        fail(GA_ERR_DEVICE, "internal: a walked source ends its chunk at another block than its walk");
+      }
+    } else if (s.gsr) {
       if (!s.gsrBlocks.empty()) {  // the state at the start of block `played` (END blocks leave nothing to resume)
         const GsrBlock& e = s.gsrBlocks[std::min<size_t>((size_t)played, s.gsrBlocks.size() - 1)];
         s.playbackPosition = e.pp;
@@ -737,6 +829,7 @@ void Context::chunkCommit(ChunkRun& r) {
     }
   }
   for (int id : r.streamIds) streamReplay(*nodes[id], n, bt, true);   // queue / resampler state at the end of the executed blocks
+  if (r.stage == 1) return;   // (the second stage of the chunk advances the clock)
   currentBlock += n;
   currentTime = bt[n];
   stats.blocks_rendered = currentBlock;
@@ -758,6 +851,10 @@ void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
   latched = true;
   profileNow = profile && (profileSeq++ % std::max(profileEvery, 1)) == 0;
   chunkTopology(r);
+  if (!r.rateMods.empty()) {   // a playbackRate modulated by a signal: the modulator cone first (runTwoStageChunk)
+    runTwoStageChunk(r);
+    return;
+  }
   chunkSimulate(r);
   chunkResources(r);
   r.tmRes = nowMs();
@@ -784,6 +881,14 @@ void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
   chunkExecute(r);
   const double tmEx = nowMs();
   chunkCommit(r);
+  chunkRetire(r);
+  if (gaTiming)
+    fprintf(stderr, "[ga]   host detail: param curves %.3f, conv scratch %.3f, plan nodes %.3f, plan convolvers %.3f, commit %.3f ms\n",
+            tmPar - r.tmRes, r.tmPre - tmPar, tmNodes, tmConv, nowMs() - tmEx);
+}
+
+// after the commit: the last segment's views and records stay for the next chunk, the other per-chunk tables go back to the pools
+void Context::chunkRetire(ChunkRun& r) {
   // the last segment's output views stay for one chunk (Context::chunkStaleSeed); the other per-node tables go back to the pools
   if (!r.ex->outViews.empty() && !r.segs.empty()) {
     if (!lastViews.empty() && viewsPool.size() < 8) viewsPool.push_back(std::move(lastViews));
@@ -814,12 +919,208 @@ void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
     sg.nodes.clear();
     if (segNodePool.size() < 8) segNodePool.push_back(std::move(sg.nodes));
   }
-  if (gaTiming) {
-    const double tmCm = nowMs();
-    r.ex.reset();
-    fprintf(stderr, "[ga]   host detail: param curves %.3f, conv scratch %.3f, plan nodes %.3f, plan convolvers %.3f, commit %.3f, ~Exec %.3f ms\n",
-            tmPar - r.tmRes, r.tmPre - tmPar, tmNodes, tmConv, tmCm - tmEx, nowMs() - tmCm);
+  r.ex.reset();
+}
+
+// ======================================================================================================
+// two-stage chunks: a k-rate playbackRate modulated by a signal
+// ======================================================================================================
+// The rate of every block (clamp(intrinsic(t0) + modulation[0]), AudioParam.cs:143-165) sets how many samples the block consumes and
+// where a one-shot source runs out of data: source spans, segments and the silence flags downstream depend on audio the host never
+// sees.  Stage 1 runs the ordinary passes over the modulator cone (chunkTopology: every node the modulation inputs depend on), mixes
+// the modulation inputs, computes the rates (krate_probe_kernel) and walks the buffer sources on the device (gsr_walk_kernel); ONE
+// wait, then the host reads the rates and the walk summaries back.  Stage 2 plans and runs everything else: the cone's nodes count as
+// rendered -- their per-block state comes from stage 1's simulation (Sim::restorePre), their output views from stage 1's executor.
+// Nothing of the next chunk overlaps this one's planning: the wait is on the whole of stage 1.
+void Context::runTwoStageChunk(ChunkRun& r) {
+  // ---- stage 1: the modulator cone ----
+  ChunkRun r1;
+  r1.stage = 1;
+  r1.n = r.n;
+  r1.tm0 = r.tm0;
+  r1.maxDepth = r.maxDepth;
+  r1.maxLevel = r.maxLevel;
+  r1.rateMods = r.rateMods;
+  for (int id : r.topo)
+    if (rateCone[id]) r1.topo.push_back(id);
+  lastSegStable = false;   // (no first-block replay on either side of the split: chunkSimulate)
+  chunkSimulate(r1);
+  chunkResources(r1);
+  r1.tmRes = nowMs();
+  bqSplitUsed = 0;
+  r1.ex = std::make_unique<Exec>(*this, r1.n, r1.segs);
+  r1.ex->outViews.resize(r1.segs.size());
+  r1.ex->plan.host.resize(16);
+  chunkStaleSeed(r1);   // (nodes an edit took out of the graph keep their last block before anything overwrites the slabs)
+  curveListTopoSize = ~(size_t)0;   // (the curve list is cached per topology: the two stages have different ones)
+  chunkParamCurves(r1);
+  chunkConvScratch(r1);
+  r1.tmPre = nowMs();
+  for (int d = 0; d <= r1.maxDepth; d++) {
+    chunkPlanNodes(r1, d);
+    chunkPlanConvolvers(r1, d);
   }
+  chunkDelayCommit(r1);
+  chunkRateProbe(r1);
+  chunkExecute(r1);
+  const double tw0 = nowMs();
+  GA_HIP(hipStreamSynchronize(stream));   // the rates and walk summaries (chunkRateProbe)
+  if (gaTiming) fprintf(stderr, "[ga]   two-stage chunk: stage 1 wait %.3f ms\n", nowMs() - tw0);
+
+  // ---- stage 2: everything else ----
+  r.stage = 2;
+  r.n = r1.n;
+  r.pre = &r1;
+  r.rmOf = std::move(r1.rmOf);
+  r.rmIn = std::move(r1.rmIn);
+  {
+    std::vector<int> rest;
+    rest.reserve(r.topo.size() - r1.topo.size());
+    for (int id : r.topo)
+      if (!rateCone[id]) rest.push_back(id);
+    r.topo.swap(rest);
+  }
+  chunkSimulate(r);
+  chunkResources(r);
+  r.tmRes = nowMs();
+  bqSplitUsed = 0;   // (stage 1 has finished on the device)
+  r.ex = std::make_unique<Exec>(*this, r.n, r.segs);
+  Exec& ex = *r.ex;
+  ex.outViews.resize(r.segs.size());
+  ex.plan.host.resize(16);
+  const Exec& ex1 = *r1.ex;
+  for (size_t si = 0; si < r.segs.size(); si++) {   // the cone's output views (and folded gains / gain curves) of stage 1
+    const size_t s1 = (size_t)(std::upper_bound(r1.preB0.begin(), r1.preB0.end(), r.segs[si].b0) - r1.preB0.begin()) - 1;
+    ex.outViews[si].resize(nodes.size());
+    for (int id : r1.topo) {
+      if (s1 < ex1.outViews.size() && id < (int)ex1.outViews[s1].size()) ex.outViews[si][id] = ex1.outViews[s1][id];
+      const float g = ex1.scaleOf((int)s1, id);
+      if (g != 1.f) ex.setScale((int)si, id, g);
+      if (const float* cv = ex1.curveOf((int)s1, id)) ex.setCurve((int)si, id, cv);
+    }
+  }
+  curveListTopoSize = ~(size_t)0;
+  chunkParamCurves(r);
+  chunkConvScratch(r);
+  r.tmPre = nowMs();
+  for (int d = 0; d <= r.maxDepth; d++) {
+    chunkPlanNodes(r, d);
+    chunkPlanConvolvers(r, d);
+  }
+  chunkDelayCommit(r);
+  chunkStaleCommit(r);
+  chunkExecute(r);
+  chunkCommit(r1);   // (the cone's sources; the clock moves with stage 2's commit)
+  chunkCommit(r);
+  curveListTopoSize = ~(size_t)0;
+  r1.ex.reset();
+  chunkRetire(r);
+  lastSegStable = false;   // (the last segment's records hold stage 2's nodes only: no first-block replay in the next chunk)
+}
+
+// stage 1: the modulation input of every modulated rate mixed (Exec::resolveInSeg: the mix every modulated parameter gets), the rate
+// of every block (krate_probe_kernel), the walk of every modulated buffer source (gsr_walk_kernel, option rate_mod_walk), and one
+// copy of the rates and walk summaries to page-locked memory
+void Context::chunkRateProbe(ChunkRun& r) {
+  Exec& ex = *r.ex;
+  const int64_t n = r.n;
+  const int nm = (int)r.rateMods.size();
+  std::vector<const float*> rows((size_t)nm * n, nullptr);
+  for (size_t si = 0; si < r.segs.size(); si++) {
+    const Segment& sg = r.segs[si];
+    for (int k = 0; k < nm && k < (int)sg.probe.size(); k++) {
+      const InSeg& is = sg.probe[k];
+      if (is.silent) continue;   // the intrinsic value alone (AudioParam.cs:143-165)
+      Views v = ex.resolveInSeg((int)si, r.rateMods[k].first, -1 - r.rateMods[k].second, is, false, nullptr);
+      const float* row = (!v.empty() && v[0]) ? v[0] : zeros;
+      for (int64_t b = sg.b0; b < sg.b1; b++) rows[(size_t)k * n + b] = row;
+    }
+  }
+  ex.flushLevel();
+  // walks
+  std::vector<GsrWalkJob> walks;
+  std::vector<int> walkOf(nm, -1), walkMod;
+  if (rateModWalk)
+    for (int k = 0; k < nm; k++) {
+      NodeS& s = *nodes[r.rateMods[k].first];
+      GsrWalkJob j{};
+      if (s.type != GA_NODE_BUFFER_SOURCE || !rateModWalkJob(*this, s, n, r.bt, j)) continue;
+      walkOf[k] = (int)walks.size();
+      walkMod.push_back(k);
+      walks.push_back(j);
+    }
+  // device area: rates [nm][n], walk summaries, descriptors; the first two are read back
+  const size_t ratesBytes = (size_t)roundup((int64_t)nm * n * (int64_t)sizeof(float), 16);
+  const size_t readBytes = ratesBytes + walks.size() * sizeof(GsrWalkOut);
+  size_t descCount = 0;
+  for (const GsrWalkJob& j : walks) descCount += (size_t)j.nrel + 1;
+  const size_t devBytes = readBytes + descCount * sizeof(GsrBlock);
+  if (rateModDevBytes < devBytes) {
+    if (rateModDev) {
+      GA_HIP(hipStreamSynchronize(stream));   // (the previous chunk's gsr_kernel may still read its descriptors)
+      dfree(rateModDev, rateModDevBytes);
+    }
+    rateModDevBytes = devBytes + devBytes / 2 + 4096;
+    rateModDev = dalloc(rateModDevBytes);
+  }
+  if (rateModHostBytes < readBytes) {
+    if (rateModHost) (void)hipHostFree(rateModHost);   // (nothing reads it outside the chunk that wrote it)
+    rateModHostBytes = readBytes + readBytes / 2 + 4096;
+    GA_HIP(hipHostMalloc(&rateModHost, rateModHostBytes, hipHostMallocDefault));
+  }
+  float* ratesDev = (float*)rateModDev;
+  GsrWalkOut* outsDev = (GsrWalkOut*)((char*)rateModDev + ratesBytes);
+  GsrBlock* descDev = (GsrBlock*)((char*)rateModDev + readBytes);
+  const float* ratesHost = (const float*)rateModHost;
+  const GsrWalkOut* outsHost = (const GsrWalkOut*)((const char*)rateModHost + ratesBytes);
+  size_t d0 = 0;
+  for (size_t w = 0; w < walks.size(); w++) {
+    GsrWalkJob& j = walks[w];
+    j.rates = ratesDev + (size_t)walkMod[w] * n;
+    j.desc = descDev + d0;
+    j.out = outsDev + w;
+    d0 += (size_t)j.nrel + 1;
+  }
+  // what stage 2 plans the modulated sources with
+  r.rmOf.assign(nodes.size(), -1);
+  r.rmIn.assign(nm, RateModIn{});
+  for (int k = 0; k < nm; k++) {
+    RateModIn& m = r.rmIn[k];
+    m.rates = ratesHost + (size_t)k * n;
+    if (walkOf[k] >= 0) {
+      const GsrWalkJob& j = walks[walkOf[k]];
+      m.walk = outsHost + walkOf[k];
+      m.desc = j.desc;
+      m.nrel = j.nrel;
+    }
+    r.rmOf[r.rateMods[k].first] = k;
+  }
+  // the probe
+  std::vector<KrateProbeJob> pjobs(nm);
+  const size_t rowsOff = ex.plan.putv(rows);
+  for (int k = 0; k < nm; k++) {
+    const ParamS& ps = nodes[r.rateMods[k].first]->params[r.rateMods[k].second];
+    KrateProbeJob& pj = pjobs[k];
+    pj.rows_off = rowsOff + (size_t)k * n * sizeof(const float*);
+    pj.events_off = ex.plan.putv(ps.events);
+    pj.nev = (int)ps.events.size();
+    pj.value = ps.value;
+    pj.vmin = ps.minv;
+    pj.vmax = ps.maxv;
+    pj.pad_ = 0;
+    pj.out = ratesDev + (size_t)k * n;
+  }
+  const size_t pjOff = ex.plan.putv(pjobs), btOff = ex.plan.putv(r.bt);
+  hipStream_t st = stream;
+  ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_krate_probe(st, (const KrateProbeJob*)(base + pjOff), nm, base, (const double*)(base + btOff), n); });
+  if (!walks.empty()) {
+    const size_t wOff = ex.plan.putv(walks);
+    const int nw = (int)walks.size();
+    ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_gsr_walk(st, (const GsrWalkJob*)(base + wOff), nw); });
+  }
+  void* hostDst = rateModHost;
+  const void* devSrc = rateModDev;
+  ex.plan.add(LK_OTHER, [=](uint8_t*) { GA_HIP(hipMemcpyAsync(hostDst, devSrc, readBytes, hipMemcpyDeviceToHost, st)); });
 }
 
 }  // namespace ga

@@ -79,7 +79,17 @@ struct SrcPlanOut {
   int partialProduced = 0;
 };
 
-SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt);
+// a source whose k-rate playbackRate is modulated by a signal: what the first stage of a two-stage chunk found (Context::runTwoStageChunk)
+struct RateModIn {
+  const float* rates = nullptr;      // the rate of every block of the chunk, read back (host memory, chunk-block indexed)
+  const GsrWalkOut* walk = nullptr;  // rate_mod_walk = 1: the device walk's summary (read back) ...
+  const GsrBlock* desc = nullptr;    // ... and the descriptors it wrote (device memory)
+  int64_t nrel = 0;                  // blocks walked
+};
+
+SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm = nullptr);
+// the walk of a modulated buffer source (gsr_walk_kernel) from the source's state; false = the source does not play in these blocks
+bool rateModWalkJob(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j);
 SrcPlanOut planScheduled(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt);
 
 static const SrcSpan& spanAt(const NodeS& s, int64_t b) {
@@ -91,6 +101,8 @@ static const SrcSpan& spanAt(const NodeS& s, int64_t b) {
 // ======================================================================================================
 // control-plane simulation
 // ======================================================================================================
+struct ChunkRun;
+
 struct Sim {
   Context& c;
   int64_t n;
@@ -99,6 +111,30 @@ struct Sim {
   int64_t brel = 0;
   std::vector<int64_t>* extraBreaks = nullptr;   // chunk-relative blocks at which a node asks to be evaluated again
   const std::vector<double>* blockTimes = nullptr;   // accumulated block clock of the chunk (chunk-relative block -> time)
+  const ChunkRun* pre = nullptr;   // second stage of a two-stage chunk: the first stage, whose nodes count as rendered
+
+  // a node the first stage rendered: its outputs' channel counts and silence flags in this block are the first stage's (Sim::evalNode)
+  bool restorePre(int id);
+
+  // first stage of a two-stage chunk: the modulation inputs of the modulated rates, pulled as AudioParam.ComputeValues pulls them
+  // (1 channel, explicit: AudioParam.cs:68,97-101) -- everything they depend on is evaluated, nothing else
+  void evalProbe(const std::vector<std::pair<int, int>>& mods) {
+    for (const auto& pm : mods) {
+      InSeg is;
+      is.bufCh = 1;
+      is.silent = true;
+      for (auto& m : c.nodes[pm.first]->params[pm.second].modulation) {
+        evalNode(m.first);
+        const NodeS& pn = *c.nodes[m.first];
+        const OutputS& o = pn.outputs[m.second];
+        if (o.bufCh != 0 && !o.silent) {
+          is.terms.push_back(TermS{m.first, m.second, o.bufCh, pn.isProcessing});
+          is.silent = false;
+        }
+      }
+      cur->probe.push_back(std::move(is));
+    }
+  }
 
   int computeOutputChannelCount(InputS& in) {  // AudioNodeInput.cs:140-168
     switch (in.mode) {
@@ -158,6 +194,7 @@ struct Sim {
   }
 
   void evalNode(int id) {  // AudioNode.ProcessInternal, Nodes/AudioNode.cs:152-183
+    if (pre && restorePre(id)) return;   // (before the memo check: the first stage stamped these nodes with this chunk's block numbers)
     NodeS& n_ = *c.nodes[id];
     if (n_.lastProcessedBlock == blockNumber) return;
     if (n_.isProcessing) fail(GA_ERR_CYCLE, "Audio graph cycle detected at node " + std::to_string(id));   // (unreachable, as in the reference)
@@ -441,6 +478,10 @@ struct Sim {
       }
       for (const InSeg& is : ns.pins)
         for (const TermS& t : is.terms) h = hmix(h, 0x5151ull ^ (((uint64_t)t.node << 16) | ((uint64_t)t.out << 8) | (uint64_t)t.ch | ((uint64_t)t.stale << 60)));
+    }
+    for (const InSeg& is : s.probe) {
+      h = hmix(h, 0x7070ull ^ (is.silent ? 1 : 0));
+      for (const TermS& t : is.terms) h = hmix(h, ((uint64_t)t.node << 16) | ((uint64_t)t.out << 8) | (uint64_t)t.ch);
     }
     return h;
   }
@@ -1022,8 +1063,34 @@ struct ChunkRun {
   std::vector<Segment> segs;
   std::unique_ptr<Exec> ex;
   int bHistMax = 0;
+  // two-stage chunks (sources whose playbackRate is modulated by a signal: Context::runTwoStageChunk)
+  int stage = 0;                                 // 0: one pass over the graph; 1: the modulator cone; 2: everything else
+  std::vector<std::pair<int, int>> rateMods;     // (source, param) of the modulated rates
+  struct PreOut { int bufCh; bool silent, zero; };
+  std::vector<int> preRow;                       // stage 1: node id -> its first output's row in a snapshot, -1 = not in the cone
+  std::vector<std::vector<PreOut>> preSnap;      // stage 1: [segment][row] the cone's output state
+  std::vector<int64_t> preB0;                    // stage 1: segment starts
+  const ChunkRun* pre = nullptr;                 // stage 2: stage 1
+  std::vector<int> rmOf;                         // stage 2: node id -> index into rmIn, -1 = none
+  std::vector<RateModIn> rmIn;
   double tm0 = 0, tmTopo = 0, tmSrc = 0, tmSim = 0, tmRes = 0, tmPre = 0, tmPlan = 0, tmLaunch = 0;
 };
+
+inline bool Sim::restorePre(int id) {
+  const ChunkRun& p = *pre;
+  if (id >= (int)p.preRow.size() || p.preRow[id] < 0) return false;
+  const size_t s1 = (size_t)(std::upper_bound(p.preB0.begin(), p.preB0.end(), brel) - p.preB0.begin()) - 1;
+  NodeS& n_ = *c.nodes[id];
+  const auto& snap = p.preSnap[s1];
+  for (size_t o = 0; o < n_.outputs.size(); o++) {
+    const ChunkRun::PreOut& q = snap[(size_t)p.preRow[id] + o];
+    n_.outputs[o].bufCh = q.bufCh;
+    n_.outputs[o].silent = q.silent;
+    n_.outputs[o].zero = q.zero;
+  }
+  n_.lastProcessedBlock = blockNumber;
+  return true;
+}
 
 // ---- pass 6, per node type -------------------------------------------------------------------------------------------------
 // dense tables indexed by node id, validated by a per-(stage, segment) stamp: no hashing on the per-node path

@@ -241,6 +241,8 @@ Context::~Context() {
     if (np && np->panDev) (void)hipFree(np->panDev);
   }
   for (auto& kv : tw16) (void)hipFree(kv.second);
+  if (rateModDev) (void)hipFree(rateModDev);
+  if (rateModHost) (void)hipHostFree(rateModHost);
   if (coarseTw) (void)hipFree(coarseTw);
   if (tw16pw) (void)hipFree(tw16pw);
   if (copyStream) {

@@ -30,6 +30,7 @@
 
 #include "../../include/graphaudio_hip.h"
 #include "ga_kernels.hpp"
+#include "ga_gsr.hpp"
 
 namespace ga {
 
@@ -182,6 +183,11 @@ struct NodeS {
   std::vector<GsrBlock> gsrBlocks;  // per chunk: one per processed block from the first played block, + the end state
   uint64_t gsrDevOff = 0;
   bool gsrUploaded = false;
+  // a playbackRate modulated by a signal, rate_mod_walk = 1: the descriptors gsr_walk_kernel wrote on the device (per chunk, null
+  // otherwise), how many blocks it walked, and the state after them (Context::runTwoStageChunk)
+  const GsrBlock* gsrDesc = nullptr;
+  int64_t gsrWalked = -1;
+  GsrBlock gsrTail{};
   // ConstantSourceNode / OscillatorNode share hasStarted/hasStopped/startTime/stopTime/endedRaised with the buffer source
   int oscType = 0;                 // OscillatorNode._type
   double* oscPhase = nullptr;      // device: OscillatorNode._phase (one double)
@@ -275,6 +281,7 @@ struct NodeS {
   int stCurrent = -1;
   int64_t stPos = 0;
   int stLastRate = 0;
+  const float* stRateMod = nullptr;   // per chunk: the read-back k-rate playbackRate of every block (a modulated rate), null otherwise
   int stState = GA_STREAM_STOPPED;
   int stChannels = -1;                      // _resamplers.Length ; -1 = null
   double stRsPos = 0.0;
@@ -466,6 +473,7 @@ struct NodeSeg {
 struct Segment {
   int64_t b0 = 0, b1 = 0;  // chunk-relative block range
   std::vector<NodeSeg> nodes;  // processing (post) order
+  std::vector<InSeg> probe;    // first stage of a two-stage chunk: the modulation input of every modulated rate (ChunkRun::rateMods)
   uint64_t hash = 0;
 };
 
@@ -666,6 +674,7 @@ struct Context {
   void releaseConvState(NodeS& n);
   void refOrderSensitivity(const std::vector<int>& topo);
   bool ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto);
+  bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);
   // formulation D
@@ -768,6 +777,20 @@ struct Context {
   void chunkStaleCommit(ChunkRun& r);   // feedback cycles: the block every stale producer put out becomes what its consumers read next
   void chunkExecute(ChunkRun& r);
   void chunkCommit(ChunkRun& r);
+  void chunkRetire(ChunkRun& r);
+  void runTwoStageChunk(ChunkRun& r);
+  void chunkRateProbe(ChunkRun& r);
+  // sources whose k-rate playbackRate is modulated by a signal (chunkTopology): (node, param), cached with the graph version, and the
+  // cone of nodes their modulation inputs depend on (rendered by the first stage of a two-stage chunk)
+  std::vector<std::pair<int, int>> topoRateMods;
+  std::vector<char> rateCone;
+  uint64_t rateModsVersion = ~0ull;
+  // the first stage's results: rates [mods][blocks] and walk summaries on the device (then the walks' descriptors), and their
+  // page-locked copy on the host
+  void* rateModDev = nullptr;
+  size_t rateModDevBytes = 0;
+  void* rateModHost = nullptr;
+  size_t rateModHostBytes = 0;
   void ensureBiquadState(NodeS& bn);
   // AudioStreamNodeBase.Process replayed on indices for `nblocks` blocks from the node's current state: fills the node's per-chunk
   // tables (commit = false) or moves the node's state to the end of the replayed blocks (commit = true)

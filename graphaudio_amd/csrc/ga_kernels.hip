@@ -12,6 +12,7 @@
 // multiply-adds appear only where written explicitly (fma(), MFMA).
 
 #include "ga_kernels.hpp"
+#include "ga_gsr.hpp"
 #include "ga_fft16.hpp"
 #include <type_traits>
 
@@ -2758,7 +2759,7 @@ __global__ __launch_bounds__(64) void gsr_kernel(const GsrJob* __restrict jobs, 
   if (bl0 >= job.nblocks) return;
   const int64_t b = bl0 + lane;
   if (b < job.nblocks) {
-    const GsrBlock d = ((const GsrBlock*)(base + job.desc_off))[b];   // (`base` is a kernel argument: global)
+    const GsrBlock d = (job.desc ? job.desc : (const GsrBlock*)(base + job.desc_off))[b];   // (`base` is a kernel argument: global)
     const GA_GLOBAL float* __restrict in = gptr(job.buf);
     int64_t ip = d.next;
     auto feed = [&]() {
@@ -2803,6 +2804,81 @@ void launch_gsr(hipStream_t s, const GsrJob* jobs_dev, int njobs, const uint8_t*
   if (njobs <= 0 || max_blocks <= 0) return;
   int gx = (int)((max_blocks + 63) / 64);
   GA_LAUNCH_JOBS(gsr_kernel, gx, 64, jobs_dev, njobs, plan_base_dev);
+}
+
+
+// =====================================================================================================
+//  Modulated k-rate playbackRate (see KrateProbeJob, GsrWalkJob): the rate of every block, then the source walk
+// =====================================================================================================
+__global__ __launch_bounds__(64) void krate_probe_kernel(const KrateProbeJob* __restrict jobs, const uint8_t* __restrict base,
+                                                         const double* __restrict bt, int64_t nblocks) {
+  const KrateProbeJob job = jobs[blockIdx.y];
+  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (b >= nblocks) return;
+  const float* const* rows = (const float* const*)(base + job.rows_off);
+  float v = param_value_at((const ParamEvent*)(base + job.events_off), job.nev, job.value, bt[b]);   // intrinsic value at the block start
+  const float* row = rows[b];
+  if (row) v = fminf(fmaxf(v + gptr(row)[b * kBlock], job.vmin), job.vmax);   // Math.Clamp(intrinsicValue + modulation, min, max)
+  gptr(job.out)[b] = v;
+}
+void launch_krate_probe(hipStream_t s, const KrateProbeJob* jobs_dev, int njobs, const uint8_t* plan_base_dev, const double* block_times_dev,
+                        int64_t nblocks) {
+  if (njobs <= 0 || nblocks <= 0) return;
+  int gx = (int)((nblocks + 63) / 64);
+  GA_LAUNCH_JOBS(krate_probe_kernel, gx, 64, jobs_dev, njobs, plan_base_dev, block_times_dev, nblocks);
+}
+
+__global__ __launch_bounds__(64) void gsr_walk_kernel(const GsrWalkJob* __restrict jobs, int njobs) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= njobs) return;
+  const GsrWalkJob job = jobs[i];
+  GsrState st = job.st;
+  int64_t endRel = -1;
+  int err = GSR_OK;
+  int64_t rel = 0;
+  for (; rel < job.nrel && err == GSR_OK; rel++) {
+    GsrBlock d;
+    bool end = false;
+    const int64_t b = job.bs + rel;
+    int e = (b >= 0 && b < job.nrates) ? gsrReplayBlock(job.g, job.rates[b], st, d, end) : GSR_ERR_FEED;
+    if (e == GSR_OK) {
+      if (end && endRel < 0) endRel = rel;
+      else if (!end && endRel >= 0) e = GSR_ERR_RESUMED;   // (with unchanged controls an END block is followed by END blocks only)
+    }
+    if (e == GSR_OK && endRel < 0) e = gsrCheckBlock(job.g, d);   // END blocks are cleared: no reads
+    if (e != GSR_OK) {
+      err = e;
+      d.copy = 1;
+      d.produced = 0;
+      d.next = 0;
+    }
+    job.desc[rel] = d;
+    if (endRel >= 0 && job.endsAtEnd) {
+      rel++;
+      break;
+    }
+  }
+  for (; rel < job.nrel; rel++) {   // (after a failure: silence; the host refuses the chunk before anything reads these)
+    GsrBlock d{};
+    d.copy = 1;
+    job.desc[rel] = d;
+  }
+  GsrBlock tail{};   // the state after the last walked block
+  tail.pp = st.pp;
+  for (int k = 0; k < 4; k++) tail.w[k] = st.w[k];
+  tail.pos = st.pos;
+  tail.ready = st.ready;
+  job.desc[job.nrel] = tail;
+  GsrWalkOut o;
+  o.endRel = endRel;
+  o.st = st;
+  o.err = err;
+  o.pad_ = 0;
+  *job.out = o;
+}
+void launch_gsr_walk(hipStream_t s, const GsrWalkJob* jobs_dev, int njobs) {
+  if (njobs <= 0) return;
+  hipLaunchKernelGGL(gsr_walk_kernel, dim3((njobs + 63) / 64), dim3(64), 0, s, jobs_dev, njobs);
 }
 
 

@@ -489,6 +489,7 @@ struct GsrJob {
   int64_t loop_start, loop_end;
   int loop;
   int pad_;
+  const GsrBlock* desc;  // descriptors written on the device (gsr_walk_kernel); null: the plan buffer at desc_off
 };
 void launch_gsr(hipStream_t s, const GsrJob* jobs_dev, int njobs, const uint8_t* plan_base_dev, int64_t max_blocks);
 

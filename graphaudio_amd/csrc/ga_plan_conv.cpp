@@ -812,7 +812,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
 
   // ---- convolver scratch planes are shared by all groups: size them for the largest group BEFORE any recorded
   //      launch captures their address ----
-  if (topoHasConvolvers) {   // (a graph without convolvers -- tens of thousands of nodes of config 4 -- skips these sweeps)
+  if (topoHasConvolvers && r.stage != 1) {   // (no convolver in the first stage of a two-stage chunk: chunkTopology) (a graph without convolvers -- tens of thousands of nodes of config 4 -- skips these sweeps)
     refOrderSensitivity(topo);
     assignConvPaths(topo, n);
     for (int id : topo) {

@@ -298,7 +298,7 @@ void Context::planBufferSource(NodePlanCtx& k) {
   PlayBuf& pb = *buffers[ns.srcBuf];
   SrcGeom g = sourceGeom(*this, nd, pb);
   if (nd.gsr) {  // general replay: one host-made descriptor per block
-    if (!nd.gsrUploaded) {
+    if (!nd.gsrUploaded && !nd.gsrDesc) {
       nd.gsrDevOff = ex.plan.putv(nd.gsrBlocks);
       nd.gsrUploaded = true;
     }
@@ -306,7 +306,8 @@ void Context::planBufferSource(NodePlanCtx& k) {
       GsrJob gj;
       gj.buf = pb.dev + (size_t)ch * pb.stride;
       gj.out = ex.nodeOut(ns.id, ch);
-      gj.desc_off = nd.gsrDevOff + (uint64_t)ns.srcBlk * sizeof(GsrBlock);
+      gj.desc_off = nd.gsrDesc ? 0 : nd.gsrDevOff + (uint64_t)ns.srcBlk * sizeof(GsrBlock);
+      gj.desc = nd.gsrDesc ? nd.gsrDesc + ns.srcBlk : nullptr;   // (written by gsr_walk_kernel: a modulated rate)
       gj.b0 = sg.b0;
       gj.nblocks = nb;
       gj.loop_start = g.loopStartFrame;

@@ -1,6 +1,7 @@
 // ga_sources.cpp -- source scheduling on the host: AudioBufferSourceNode / scheduled sources as per-chunk phase timelines, the resampler's
 // position recurrence, general source replay, AudioStreamNodeBase replay (see ga_chunk_internal.hpp).
 #include "ga_chunk_internal.hpp"
+#include "ga_gsr.hpp"
 
 namespace ga {
 
@@ -58,246 +59,183 @@ static void resampleBlockBounded(const ResampleBlock& st, double rate, int64_t a
   if (readyAfter) *readyAfter = ready;
 }
 
-// ---- general source replay: AudioBufferSourceNode.Process for ONE block on indices only (see GsrBlock) ----
-struct GsrState {
-  int64_t w[4];
-  double pos;
-  int ready;
-  int64_t pp;
+// ---- general source replay (ga_gsr.hpp): what a replay needs of the source ----
+static GsrGeom gsrGeom(Context& c, const SrcGeom& g, const NodeS& s, const PlayBuf& b) {
+  GsrGeom q;
+  q.loopStart = g.loopStartFrame;
+  q.loopEnd = g.loopEndFrame;
+  q.durEnd = g.durationEndFrame;
+  q.len = b.length;
+  q.ratio = b.sampleRate / (double)c.sampleRate;
+  q.loop = s.loop ? 1 : 0;
+  q.channels = b.channels;
+  return q;
+}
+
+static GsrState gsrStateOf(const NodeS& s) {
+  GsrState st;
+  for (int k = 0; k < 4; k++) st.w[k] = s.gsrW[k];
+  st.pos = s.gsrPos;
+  st.ready = s.gsrReady;
+  st.rsChannels = s.rsChannels;
+  st.pp = s.playbackPosition;
+  return st;
+}
+
+// The blocks of the chunk a buffer source plays in: `plays` = false for an idle source; bs = first block with t1 > startTime;
+// kTime = relative index of the block after which Ended is raised because t1 >= stopTime (INF: not inside this chunk)
+struct SrcStart {
+  bool plays = false;
+  int64_t bs = 0, kTime = 0;
 };
-
-static inline void gsrFeed(GsrState& st, int64_t idx) {  // CubicResampler.Shift, :91-97
-  st.w[0] = st.w[1];
-  st.w[1] = st.w[2];
-  st.w[2] = st.w[3];
-  st.w[3] = idx;
+static const int64_t kSrcInf = std::numeric_limits<int64_t>::max() / 4;
+static SrcStart srcStart(Context& c, const NodeS& s, int64_t n, const std::vector<double>& bt) {
+  SrcStart r;
+  r.kTime = kSrcInf;
+  const PlayBuf* b = s.bufId >= 0 ? c.buffers[s.bufId].get() : nullptr;
+  if (!s.hasStarted || !b || s.disposed) return r;
+  r.bs = std::upper_bound(bt.begin() + 1, bt.begin() + 1 + n, s.startTime) - (bt.begin() + 1);
+  if (r.bs >= n || (!std::isnan(s.stopTime) && !(bt[r.bs] < s.stopTime))) return r;
+  r.plays = true;
+  if (!std::isnan(s.stopTime))  // may be >= n - bs: not inside this chunk
+    r.kTime = std::lower_bound(bt.begin() + 1 + r.bs, bt.begin() + 1 + n, s.stopTime) - (bt.begin() + 1 + r.bs);
+  return r;
 }
 
-// CubicResampler.Process (:26-63) on an index stream at(k), k < inLen
-template <class At>
-static void gsrProcess(GsrState& st, At at, int inLen, int outLen, double rate, int& consumed, int& produced) {
-  int inPos = 0, outPos = 0;
-  while (st.ready < 4 && inPos < inLen) {
-    gsrFeed(st, at(inPos++));
-    st.ready++;
-  }
-  if (st.ready < 4) {
-    consumed = inPos;
-    produced = 0;
-    return;
-  }
-  while (outPos < outLen) {
-    int consume = (int)st.pos;
-    if (inPos + consume > inLen) break;
-    for (int i = 0; i < consume; i++) gsrFeed(st, at(inPos++));
-    st.pos -= consume;
-    outPos++;
-    st.pos += rate;
-  }
-  consumed = inPos;
-  produced = outPos;
-}
-
-// returns true when the block is an END block (`!hasMoreData || (!_loop && _playbackPosition >= durationEndFrame)`, :360)
-static bool gsrReplayBlock(NodeS& s, const SrcGeom& g, PlayBuf& b, Context& c, float playbackRate, GsrState& st, GsrBlock& d) {
-  const double effectiveRate = (b.sampleRate / (double)c.sampleRate) * playbackRate;
-  const int64_t loopStart = g.loopStartFrame, loopEnd = g.loopEndFrame, durEnd = g.durationEndFrame, len = b.length;
-  const bool loop = s.loop;
-  bool hasMore = false;
-  int64_t first = -1;
-  int outIdx = 0;
-  d.pp = st.pp;
-  d.rate = effectiveRate;
-  d.pad_ = 0;
-  auto snap = [&]() {
-    for (int k = 0; k < 4; k++) d.w[k] = st.w[k];
-    d.pos = st.pos;
-    d.ready = st.ready;
-  };
-  if (effectiveRate == 1.0) {  // :186-235
-    d.copy = 1;
-    snap();
-    int64_t pos = st.pp;
-    while (outIdx < kBlock) {
-      if (loop && pos >= loopEnd) pos = loopStart;
-      if (pos >= durEnd && !loop) break;
-      int64_t endFrame = loop ? loopEnd : std::min(durEnd, len);
-      int available = (int)std::min<int64_t>(endFrame - pos, kBlock - outIdx);
-      if (available <= 0) break;
-      if (first < 0) first = pos;
-      pos += available;
-      outIdx += available;
-      hasMore = true;
-    }
-    st.pp += kBlock;
-  } else {  // :236-358
-    d.copy = 0;
-    if (s.rsChannels != b.channels) {  // `_resamplers` (re)created and cleared (:238-245)
-      st.w[0] = st.w[1] = st.w[2] = st.w[3] = -1;
-      st.pos = 0.0;
-      st.ready = 0;
-      s.rsChannels = b.channels;
-    }
-    snap();
-    int64_t pos = st.pp, consumedThis = 0;
-    int guard = 0;
-    while (outIdx < kBlock) {
-      if (++guard > 4096) fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
-      if (loop && pos >= loopEnd) pos = loopStart;
-      if (pos >= durEnd && !loop) break;
-      int64_t endFrame = loop ? loopEnd : std::min(durEnd, len);
-      int available = (int)std::min<int64_t>(endFrame - pos, len - pos);
-      if (available <= 0) {
-        if (loop) {
-          pos = loopStart;
-          consumedThis = pos - st.pp;
-          continue;
-        }
-        break;
+// general replay mode is entered for good: the state after rsBlocks blocks of a resampler trajectory becomes explicit
+static void gsrEnter(Context& c, NodeS& s, PlayBuf& b, const SrcGeom& g) {
+  if (s.gsr) return;
+  if (s.rsBlocks > 0) {
+    Resampler& rs = resamplerFor(c, s.rsRate);
+    rs.extend(s.rsBlocks + 2);
+    ResampleBlock rb = rs.blocks[s.rsBlocks];
+    // the trajectory assumes unbounded input: if the data ran out in an earlier block the true state is that block's
+    // bounded replay (later END blocks find nothing to consume, AudioBufferSourceNode.cs:267-271)
+    const int64_t avail0 = std::max<int64_t>(g.durationEndFrame - s.rsStartPos, 0);
+    if (rb.consumed >= avail0) {
+      int64_t lo = 0, hi = s.rsBlocks - 1;
+      while (lo < hi) {
+        int64_t mid = (lo + hi) >> 1;
+        if (rs.blocks[mid + 1].consumed >= avail0) hi = mid; else lo = mid + 1;
       }
-      if (first < 0) first = pos;
-      int consumed = 0, produced = 0;
-      if (loop && pos + available >= loopEnd - 4) {  // the 512-sample wrap buffer (:297-314)
-        const int64_t loopLength = loopEnd - loopStart;
-        const int fromEnd = (int)(loopEnd - pos);
-        const int needed = std::min(kBlock - outIdx + 4, 512);
-        const int head = std::min(fromEnd, needed);
-        const int tail = (int)std::min<int64_t>(std::max(needed - head, 0), loopLength);
-        gsrProcess(st, [&](int k) { return k < head ? pos + k : loopStart + (k - head); }, head + tail, kBlock - outIdx,
-                   effectiveRate, consumed, produced);
-      } else {
-        gsrProcess(st, [&](int k) { return pos + k; }, available, kBlock - outIdx, effectiveRate, consumed, produced);
-      }
-      if (produced > 0) hasMore = true;
-      int64_t newPos = pos + consumed;
-      if (loop && newPos >= loopEnd) newPos = loopStart + (newPos - loopEnd);
-      consumedThis += (newPos >= pos) ? (newPos - pos) : (loopEnd - pos + newPos - loopStart);
-      pos = newPos;
-      outIdx += produced;
-      if (consumed == 0 && produced == 0) break;
+      int produced;
+      int64_t consumedAfter;
+      double posAfter;
+      int readyAfter;
+      resampleBlockBounded(rs.blocks[lo], s.rsRate, avail0, produced, consumedAfter, &posAfter, &readyAfter);
+      rb.consumed = consumedAfter;
+      rb.pos = posAfter;
+      rb.ready = readyAfter;
     }
-    st.pp += consumedThis;
+    s.gsrPos = rb.pos;
+    s.gsrReady = rb.ready;
+    for (int k = 0; k < 4; k++) s.gsrW[3 - k] = k < rb.ready ? s.rsStartPos + rb.consumed - 1 - k : -1;
+    s.playbackPosition = s.rsStartPos + rb.consumed;  // `_playbackPosition += totalInputConsumed` (:347)
+    s.rsChannels = b.channels;
+    s.rsBlocks = 0;
   }
-  if (loop && st.pp >= loopEnd) {  // :226-234, :349-357
-    int64_t loopLength = loopEnd - loopStart;
-    if (loopLength > 0) st.pp = loopStart + ((st.pp - loopEnd) % loopLength);
-  }
-  d.next = first < 0 ? 0 : first;
-  d.produced = outIdx;
-  return !hasMore || (!loop && st.pp >= durEnd);
+  s.gsr = true;
 }
 
-SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt) {
+static void checkResamplerBuffer(NodeS& s) {
+  const bool resamplerLive = s.gsr ? s.gsrReady > 0 : s.rsBlocks > 0;
+  if (resamplerLive && s.rsBufId != s.bufId)
+    fail(GA_ERR_UNSUPPORTED, "the Buffer of a source was replaced while its resampler holds samples of the old one");
+  if (!resamplerLive) s.rsBufId = s.bufId;
+}
+
+bool rateModWalkJob(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j) {
+  const SrcStart ss = srcStart(c, s, n, bt);
+  if (!ss.plays) return false;
+  PlayBuf& b = *c.buffers[s.bufId];
+  const SrcGeom g = sourceGeom(c, s, b);
+  checkResamplerBuffer(s);
+  gsrEnter(c, s, b, g);
+  j.g = gsrGeom(c, g, s, b);
+  j.st = gsrStateOf(s);
+  j.bs = ss.bs;
+  j.nrel = n - ss.bs;
+  if (ss.kTime != kSrcInf) j.nrel = std::min(j.nrel, ss.kTime + 1);
+  j.nrates = n;
+  j.endsAtEnd = std::isnan(s.stopTime) ? 1 : 0;
+  j.pad_ = 0;
+  return true;
+}
+
+SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm) {
   SrcPlanOut po;
   s.spans.clear();
-  PlayBuf* b = s.bufId >= 0 ? c.buffers[s.bufId].get() : nullptr;
-  if (!s.hasStarted || !b || s.disposed) {
+  s.gsrDesc = nullptr;
+  s.gsrWalked = -1;
+  const SrcStart ss = srcStart(c, s, n, bt);
+  if (!ss.plays) {
     s.spans.push_back(SrcSpan{0, SRC_IDLE, 0, 0});
     return po;
   }
-  // first block with t1 > startTime
-  int64_t bs = std::upper_bound(bt.begin() + 1, bt.begin() + 1 + n, s.startTime) - (bt.begin() + 1);
-  if (bs >= n || (!std::isnan(s.stopTime) && !(bt[bs] < s.stopTime))) {
-    s.spans.push_back(SrcSpan{0, SRC_IDLE, 0, 0});
-    return po;
-  }
+  PlayBuf* b = c.buffers[s.bufId].get();
+  const int64_t bs = ss.bs;
   if (bs > 0) s.spans.push_back(SrcSpan{0, SRC_IDLE, 0, 0});
   SrcGeom g = sourceGeom(c, s, *b);
-  const int64_t INF = std::numeric_limits<int64_t>::max() / 4;
-  // kTime: relative index of the block after which Ended is raised because t1 >= stopTime
-  int64_t kTime = INF;
-  if (!std::isnan(s.stopTime)) {
-    int64_t kb = std::lower_bound(bt.begin() + 1 + bs, bt.begin() + 1 + n, s.stopTime) - (bt.begin() + 1 + bs);
-    kTime = kb;  // may be >= n - bs: not inside this chunk
-  }
+  const int64_t INF = kSrcInf;
+  const int64_t kTime = ss.kTime;
   // kData: relative index of the first END (cleared) block
   int64_t kData = INF;
   const bool rate1 = g.effectiveRate == 1.0;
   int64_t pos = s.playbackPosition;
   const bool hasTimeline = !s.params[0].events.empty();
-  const bool resamplerLive = s.gsr ? s.gsrReady > 0 : s.rsBlocks > 0;
-  if (resamplerLive && s.rsBufId != s.bufId)
-    fail(GA_ERR_UNSUPPORTED, "the Buffer of a source was replaced while its resampler holds samples of the old one");
-  if (!resamplerLive) s.rsBufId = s.bufId;
-  bool wantGsr = s.gsr || hasTimeline || (s.loop && !rate1) || (s.rsBlocks > 0 && g.effectiveRate != s.rsRate);
-  if (wantGsr) {
-    if (!s.gsr) {  // leave trajectory mode: the state after rsBlocks blocks becomes explicit
-      if (s.rsBlocks > 0) {
-        Resampler& rs = resamplerFor(c, s.rsRate);
-        rs.extend(s.rsBlocks + 2);
-        ResampleBlock rb = rs.blocks[s.rsBlocks];
-        // the trajectory assumes unbounded input: if the data ran out in an earlier block the true state is that block's
-        // bounded replay (later END blocks find nothing to consume, AudioBufferSourceNode.cs:267-271)
-        const int64_t avail0 = std::max<int64_t>(g.durationEndFrame - s.rsStartPos, 0);
-        if (rb.consumed >= avail0) {
-          int64_t lo = 0, hi = s.rsBlocks - 1;
-          while (lo < hi) {
-            int64_t mid = (lo + hi) >> 1;
-            if (rs.blocks[mid + 1].consumed >= avail0) hi = mid; else lo = mid + 1;
-          }
-          int produced;
-          int64_t consumedAfter;
-          double posAfter;
-          int readyAfter;
-          resampleBlockBounded(rs.blocks[lo], s.rsRate, avail0, produced, consumedAfter, &posAfter, &readyAfter);
-          rb.consumed = consumedAfter;
-          rb.pos = posAfter;
-          rb.ready = readyAfter;
-        }
-        s.gsrPos = rb.pos;
-        s.gsrReady = rb.ready;
-        for (int k = 0; k < 4; k++) s.gsrW[3 - k] = k < rb.ready ? s.rsStartPos + rb.consumed - 1 - k : -1;
-        s.playbackPosition = s.rsStartPos + rb.consumed;  // `_playbackPosition += totalInputConsumed` (:347)
-        s.rsChannels = b->channels;
-        s.rsBlocks = 0;
-      }
-      s.gsr = true;
-    }
-    GsrState st;
-    for (int k = 0; k < 4; k++) st.w[k] = s.gsrW[k];
-    st.pos = s.gsrPos;
-    st.ready = s.gsrReady;
-    st.pp = s.playbackPosition;
+  checkResamplerBuffer(s);
+  // (a modulated rate: every block has its own -- the general replay, on the read-back rates or from the device walk)
+  bool wantGsr = s.gsr || hasTimeline || rm || (s.loop && !rate1) || (s.rsBlocks > 0 && g.effectiveRate != s.rsRate);
+  if (wantGsr && rm && rm->walk) {
+    gsrEnter(c, s, *b, g);   // (done before the walk already: the state it started from)
+    const GsrWalkOut& w = *rm->walk;
+    if (w.err == GSR_ERR_ZERO_LOOP) fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
+    if (w.err == GSR_ERR_RESUMED) fail(GA_ERR_UNSUPPORTED, "a source resumed after an end block inside one render chunk");
+    if (w.err != GSR_OK) fail(GA_ERR_DEVICE, "internal: source replay index out of range (device walk, status " + std::to_string(w.err) + ")");
+    kData = w.endRel >= 0 ? w.endRel : INF;
+    s.gsrBlocks.clear();
+    s.gsrDesc = rm->desc;
+    s.gsrWalked = rm->nrel;
+    s.gsrTail.pp = w.st.pp;
+    for (int k = 0; k < 4; k++) s.gsrTail.w[k] = w.st.w[k];
+    s.gsrTail.pos = w.st.pos;
+    s.gsrTail.ready = w.st.ready;
+    s.rsChannels = w.st.rsChannels;
+  } else if (wantGsr) {
+    gsrEnter(c, s, *b, g);
+    GsrState st = gsrStateOf(s);
+    const GsrGeom gg = gsrGeom(c, g, s, *b);
     s.gsrBlocks.clear();
     s.gsrUploaded = false;
     int64_t maxRel = n - bs;
     if (kTime != INF) maxRel = std::min(maxRel, kTime + 1);
     for (int64_t rel = 0; rel < maxRel; rel++) {
-      float pr = hasTimeline ? param_value_at(s.params[0].events.data(), (int)s.params[0].events.size(), s.params[0].value, bt[bs + rel])
-                             : s.params[0].value;  // k-rate: GetValues()[0] at the block start (AudioParam.cs:146-165)
+      float pr = rm ? rm->rates[bs + rel]   // (the modulated value the device computed: krate_probe_kernel)
+                    : hasTimeline ? param_value_at(s.params[0].events.data(), (int)s.params[0].events.size(), s.params[0].value, bt[bs + rel])
+                                  : s.params[0].value;  // k-rate: GetValues()[0] at the block start (AudioParam.cs:146-165)
       GsrBlock d;
-      bool end = gsrReplayBlock(s, g, *b, c, pr, st, d);
+      bool end = false;
+      if (gsrReplayBlock(gg, pr, st, d, end) != GSR_OK)
+        fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
+      s.rsChannels = st.rsChannels;
       s.gsrBlocks.push_back(d);
       // END blocks keep being processed until the stop time (their state still moves: `_playbackPosition += 128` on the
       // copy path), and with unchanged controls an END block is followed by END blocks only
-      if (end && kData == INF) kData = rel;
+      if (end && kData == INF) {
+        kData = rel;
+        // (without a stop time the first END block is the source's last -- Ended and Dispose follow it: the blocks after it are never
+        // processed, whatever the rate would do there)
+        if (rm && std::isnan(s.stopTime)) break;
+      }
       if (!end && kData != INF) fail(GA_ERR_UNSUPPORTED, "a source resumed after an end block inside one render chunk");
     }
     // every index the device will touch is checked here, on the host: a wrong descriptor must be an error, not a GPU fault
     for (size_t bi = 0; bi < s.gsrBlocks.size(); bi++) {
       const GsrBlock& d = s.gsrBlocks[bi];
       if (kData != INF && (int64_t)bi >= kData) break;  // END blocks: cleared, no device reads
-      int64_t ip = d.next;
-      int64_t feeds = 0;
-      if (d.copy) {
-        feeds = d.produced;
-      } else if (d.produced > 0) {
-        for (int k = 0; k < 4; k++)
-          if (d.w[k] < -1 || d.w[k] >= b->length) fail(GA_ERR_DEVICE, "internal: source replay window index out of range");
-        feeds = 4 - d.ready;
-        double P = d.pos;
-        for (int o = 0; o < d.produced; o++) {
-          int consume = (int)P;
-          if (consume > 0) feeds += consume;
-          P -= consume;
-          P += d.rate;
-        }
-      }
-      for (int64_t f = 0; f < feeds; f++) {
-        if (ip < 0 || ip >= b->length) fail(GA_ERR_DEVICE, "internal: source replay feed index out of range");
-        ip++;
-        if (s.loop && ip >= g.loopEndFrame) ip = g.loopStartFrame;
-      }
+      const int chk = gsrCheckBlock(gg, d);
+      if (chk == GSR_ERR_WINDOW) fail(GA_ERR_DEVICE, "internal: source replay window index out of range");
+      if (chk != GSR_OK) fail(GA_ERR_DEVICE, "internal: source replay feed index out of range");
     }
     GsrBlock tail{};  // state after the last replayed block
     tail.pp = st.pp;
@@ -484,7 +422,8 @@ void Context::streamReplay(NodeS& s, int64_t nblocks, const std::vector<double>&
       rsChannels = channelCount;
     }
     // PlaybackRate.GetValues()[0]: k-rate value at the block start (the parameter is computed once per block)
-    const float playbackRate = hasTimeline ? param_value_at(s.params[0].events.data(), (int)s.params[0].events.size(), s.params[0].value, bt[blk])
+    const float playbackRate = s.stRateMod ? s.stRateMod[blk]   // (a modulated rate: the values the first stage read back)
+                               : hasTimeline ? param_value_at(s.params[0].events.data(), (int)s.params[0].events.size(), s.params[0].value, bt[blk])
                                            : s.params[0].value;
     int rendered = 0;
     const int piece0 = commit ? 0 : (int)s.stPieces.size();
