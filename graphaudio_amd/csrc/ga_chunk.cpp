@@ -119,6 +119,7 @@ void Context::chunkTopology(ChunkRun& r) {
       if (id < (int)nodes.size() && nodes[id]) nodes[id]->staleProducer = false;
     staleProducers.clear();
     std::vector<int> stack;
+    std::vector<std::pair<int, int>> entry;   // (node, the node it was reached from) in the order the walk enters them
     auto splittable = [&](const NodeS& d) {
       if (d.type != GA_NODE_DELAY || !d.params[0].events.empty() || !d.params[0].modulation.empty()) return 0;
       int dl = (int)(d.params[0].value * (float)sampleRate);   // DelayNode.cs:66 (float * int -> float, truncated)
@@ -162,6 +163,7 @@ void Context::chunkTopology(ChunkRun& r) {
         return false;
       }
       color[id] = 1;
+      entry.push_back({id, stack.empty() ? -1 : stack.back()});
       stack.push_back(id);
       NodeS& nd = *nodes[id];
       nd.reachable = true;
@@ -191,6 +193,8 @@ void Context::chunkTopology(ChunkRun& r) {
     };
     dfs(0);
     topoRefOrder = staleProducers.empty() ? std::vector<int>() : topo;   // (the reference's processing order: Context::refOrderSensitivity)
+    if (staleProducers.empty()) topoRefEntry.clear();
+    else topoRefEntry.swap(entry);   // (where the walk enters a modulator cone: runTwoStageChunk)
     // ---- loops that can be cut at a DelayNode (option "cycle_delay_split") ----
     // A DelayNode whose delay is a constant of d >= 128 K samples reads, for any K consecutive blocks, only samples its ring held
     // BEFORE those blocks: its output for the whole K-block chunk can be produced first (a gather from the history: the READER, a node
@@ -313,8 +317,6 @@ void Context::chunkTopology(ChunkRun& r) {
       if (rateCone[pm.first])
         fail(GA_ERR_UNSUPPORTED, "a modulated playbackRate depends on a source whose own playbackRate is modulated, or on its own output "
                                  "(nested modulated rates / feedback through the rate) -- not on the device path");
-    if (topoHasCycles)
-      fail(GA_ERR_UNSUPPORTED, "a modulated playbackRate in a graph with a feedback loop is not on the device path");
     for (int id : topo)
       if (rateCone[id] && nodes[id]->type == GA_NODE_CONVOLVER)
         fail(GA_ERR_UNSUPPORTED, "a ConvolverNode in front of a modulated playbackRate is not on the device path");
@@ -326,6 +328,15 @@ void Context::chunkTopology(ChunkRun& r) {
         fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
     }
     r.rateMods = topoRateMods;
+    // A feedback loop lies entirely inside the cone or entirely outside it (the cone is closed upstream; a loop through a modulated source
+    // is refused above): a loop outside is stage 2's alone, the same walk from the destination as a one-pass chunk.  A loop inside is
+    // stage 1's, and stage 1 has to enter the cone where the reference's walk does (Sim::evalProbe): the cone nodes first reached from a
+    // node outside it, in the order the walk reaches them.
+    bool coneLoop = false;
+    for (int id : staleProducers) coneLoop = coneLoop || rateCone[id];
+    if (coneLoop)
+      for (const auto& e : topoRefEntry)
+        if (rateCone[e.first] && (e.second < 0 || !rateCone[e.second])) r.coneRoots.push_back(e.first);
   }
   // automated runs that ended hand their state back to the host: only nodes whose state went to the device are looked at
   // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, NodeS::bqDynSeq / panDynSeq, not a flag to reset)
@@ -520,7 +531,7 @@ void Context::chunkSimulate(ChunkRun& r) {
       if (!replayed) {
         inRender = true;
         try {
-          if (r.stage == 1) sim.evalProbe(r.rateMods);
+          if (r.stage == 1) sim.evalProbe(r.rateMods, r.coneRoots);
           else sim.evalNode(0);
         } catch (...) {
           inRender = false;
@@ -932,6 +943,12 @@ void Context::chunkRetire(ChunkRun& r) {
 // wait, then the host reads the rates and the walk summaries back.  Stage 2 plans and runs everything else: the cone's nodes count as
 // rendered -- their per-block state comes from stage 1's simulation (Sim::restorePre), their output views from stage 1's executor.
 // Nothing of the next chunk overlaps this one's planning: the wait is on the whole of stage 1.
+// A graph with feedback: every loop lies inside the cone (stage 1's) or outside it (stage 2's), and both stages run the chunk's r.n
+// blocks -- `cycleBlocks` when every loop is cut at a DelayNode, one otherwise (chunkTopology).  A stale term resolves in the stage that
+// plans its consumer, which is its producer's stage.  The kept blocks of the stale producers and leavers of BOTH stages are seeded
+// once, in front of stage 1 (nothing has overwritten the previous chunk's slabs yet), and committed once, behind stage 2: stage 2's
+// output views hold the cone's views (and folded gains / gain curves) copied from stage 1, and its commit stamps NodeS::staleSeq with
+// the chunk number the next chunk's seed checks -- a commit in stage 1 would carry the number before and be seeded over again.
 void Context::runTwoStageChunk(ChunkRun& r) {
   // ---- stage 1: the modulator cone ----
   ChunkRun r1;
@@ -941,6 +958,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   r1.maxDepth = r.maxDepth;
   r1.maxLevel = r.maxLevel;
   r1.rateMods = r.rateMods;
+  r1.coneRoots = std::move(r.coneRoots);
   for (int id : r.topo)
     if (rateCone[id]) r1.topo.push_back(id);
   lastSegStable = false;   // (no first-block replay on either side of the split: chunkSimulate)
@@ -951,7 +969,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   r1.ex = std::make_unique<Exec>(*this, r1.n, r1.segs);
   r1.ex->outViews.resize(r1.segs.size());
   r1.ex->plan.host.resize(16);
-  chunkStaleSeed(r1);   // (nodes an edit took out of the graph keep their last block before anything overwrites the slabs)
+  chunkStaleSeed(r1);   // (both stages' stale producers, and nodes an edit took out of the graph: before anything overwrites the slabs)
   curveListTopoSize = ~(size_t)0;   // (the curve list is cached per topology: the two stages have different ones)
   chunkParamCurves(r1);
   chunkConvScratch(r1);
@@ -1008,7 +1026,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
     chunkPlanConvolvers(r, d);
   }
   chunkDelayCommit(r);
-  chunkStaleCommit(r);
+  chunkStaleCommit(r);   // (both stages' stale producers: see above)
   chunkExecute(r);
   chunkCommit(r1);   // (the cone's sources; the clock moves with stage 2's commit)
   chunkCommit(r);

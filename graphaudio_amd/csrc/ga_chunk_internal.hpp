@@ -117,8 +117,13 @@ struct Sim {
   bool restorePre(int id);
 
   // first stage of a two-stage chunk: the modulation inputs of the modulated rates, pulled as AudioParam.ComputeValues pulls them
-  // (1 channel, explicit: AudioParam.cs:68,97-101) -- everything they depend on is evaluated, nothing else
-  void evalProbe(const std::vector<std::pair<int, int>>& mods) {
+  // (1 channel, explicit: AudioParam.cs:68,97-101) -- everything they depend on is evaluated, nothing else.
+  // A cone with a feedback loop is entered where the reference's walk from the destination enters it (`roots`, ChunkRun::coneRoots):
+  // which edge of the loop reads its producer's previous block follows from that (TermS::stale).  The cone is closed upstream, so the
+  // walk between two roots only visits nodes outside it, which leave the cone's state alone.
+  void evalProbe(const std::vector<std::pair<int, int>>& mods, const std::vector<int>& roots) {
+    for (int id : roots)
+      if (!c.nodes[id]->disposed) evalNode(id);   // (a source of the cone disposed at the chunk's first block: chunkSimulate)
     for (const auto& pm : mods) {
       InSeg is;
       is.bufCh = 1;
@@ -1066,6 +1071,7 @@ struct ChunkRun {
   // two-stage chunks (sources whose playbackRate is modulated by a signal: Context::runTwoStageChunk)
   int stage = 0;                                 // 0: one pass over the graph; 1: the modulator cone; 2: everything else
   std::vector<std::pair<int, int>> rateMods;     // (source, param) of the modulated rates
+  std::vector<int> coneRoots;                    // stage 1 of a cone with a feedback loop: where the reference's walk enters the cone, in order
   struct PreOut { int bufCh; bool silent, zero; };
   std::vector<int> preRow;                       // stage 1: node id -> its first output's row in a snapshot, -1 = not in the cone
   std::vector<std::vector<PreOut>> preSnap;      // stage 1: [segment][row] the cone's output state

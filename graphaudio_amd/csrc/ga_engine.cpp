@@ -706,8 +706,9 @@ void Context::refOrderSensitivity(const std::vector<int>& topo) {
       if (nodes[id]->type == GA_NODE_CONVOLVER) nodes[id]->refSens = convRefOrder == 2;
     return;
   }
-  // (a graph with feedback: the sweep follows the reference's processing order -- the planning order may have cut loops at DelayNodes)
-  const std::vector<int>& order = (topoHasCycles && topoRefOrder.size() == topo.size()) ? topoRefOrder : topo;
+  // (a graph with feedback: the sweep follows the reference's processing order of the WHOLE graph -- the planning order may have cut
+  // loops at DelayNodes, and the second stage of a two-stage chunk plans only the nodes outside the modulator cone)
+  const std::vector<int>& order = (topoHasCycles && topoRefOrder.size() == topoCache.size()) ? topoRefOrder : topo;
   // A loop multiplies what enters it by 1 / (1 - gain): only where the estimated loop gain (Context::chunkTopology: constant gains,
   // filter boosts) comes near 1 does a last-bit difference grow -- a master echo at 0.5 doubles it and is left alone.
   const bool wildLoops = topoHasCycles && loopGainBound >= 0.7;

@@ -868,6 +868,7 @@ struct Context {
                                    // the graph): their output buffers keep the last block, which a later loop through them would read
   double loopGainBound = 0.0;   // (chunkTopology) the largest estimated gain of a feedback loop: differences that enter it grow by 1 / (1 - gain)
   std::vector<int> topoRefOrder;   // the reference-order walk of a graph with feedback (the planning order may cut loops at DelayNodes)
+  std::vector<std::pair<int, int>> topoRefEntry;   // ... the same walk's (node, the node it was first reached from, -1 = none) in entry order
   int cycleBlocks = 1;          // blocks per chunk of a graph with feedback (1 unless every loop is cut at a DelayNode)
   bool cycleDelaySplit = true;  // option "cycle_delay_split"
   // the output views of the previous chunk's last segment (and the gains folded into them): when an edit closes a cycle, the block
