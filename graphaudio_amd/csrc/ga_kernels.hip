@@ -41,6 +41,10 @@ __device__ unsigned long long* ga_tl = nullptr;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Math.Clamp(v, min, max) in the reference's comparison order: a NaN passes through (fminf / fmaxf would return a bound) and a -0.0
+// stays -0.0.  Every clamp of a parameter value goes through it except krate_probe_kernel's (see there).
+__device__ __forceinline__ float clamp_ref(float v, float mn, float mx) { return v < mn ? mn : (v > mx ? mx : v); }
+
 // =====================================================================================================
 //  256-point real FFT on one wavefront (forward: RealFourierTransform.cs:62-88; inverse: :101-131), double precision.
 //  z[n] = x[2n] + i x[2n+1] (n < 128); lane l owns z[l] (slot 0) and z[l+64] (slot 1).  One in-lane radix-2 stage
@@ -1789,8 +1793,7 @@ __global__ __launch_bounds__(256) void gain_kernel(const GainJob* __restrict job
     const int64_t f = job.f0 + i;
     float g = job.curve ? gptr(job.curve)[f] : job.gain;
     if (job.mod) {   // Math.Clamp(intrinsicValue + modulation, min, max), AudioParam.cs:129
-      g = g + gptr(job.mod)[f];
-      g = g < job.vmin ? job.vmin : (g > job.vmax ? job.vmax : g);
+      g = clamp_ref(g + gptr(job.mod)[f], job.vmin, job.vmax);
     }
     gptr(job.out)[f] = gptr(job.in)[f] * g;
   }
@@ -2818,7 +2821,9 @@ __global__ __launch_bounds__(64) void krate_probe_kernel(const KrateProbeJob* __
   const float* const* rows = (const float* const*)(base + job.rows_off);
   float v = param_value_at((const ParamEvent*)(base + job.events_off), job.nev, job.value, bt[b]);   // intrinsic value at the block start
   const float* row = rows[b];
-  if (row) v = fminf(fmaxf(v + gptr(row)[b * kBlock], job.vmin), job.vmax);   // Math.Clamp(intrinsicValue + modulation, min, max)
+  // Math.Clamp(intrinsicValue + modulation, min, max), except for a NaN: fmaxf turns it into the lower bound.  The reference converts a
+  // NaN rate with (int) / (long) casts, which have no defined result to match, and the replay needs a finite rate.
+  if (row) v = fminf(fmaxf(v + gptr(row)[b * kBlock], job.vmin), job.vmax);
   gptr(job.out)[b] = v;
 }
 void launch_krate_probe(hipStream_t s, const KrateProbeJob* jobs_dev, int njobs, const uint8_t* plan_base_dev, const double* block_times_dev,
@@ -3118,7 +3123,7 @@ __global__ __launch_bounds__(64) void stereo_panner_dynamic_kernel(const PanDynJ
   const GA_GLOBAL float* psrc = (const GA_GLOBAL float*)job.state;   // {last_pan, gain_l, gain_r, pad}
   PanState st = job.init ? job.init_state : PanState{psrc[0], psrc[1], psrc[2], psrc[3]};
   const int64_t nblk = job.n / kBlock;
-  auto panAt = [&](int64_t f) { return fminf(fmaxf(job.curve ? gptr(job.curve)[f] : job.value, -1.0f), 1.0f); };   // Math.Clamp(panValues[i], -1, 1)
+  auto panAt = [&](int64_t f) { return clamp_ref(job.curve ? gptr(job.curve)[f] : job.value, -1.0f, 1.0f); };   // Math.Clamp(panValues[i], -1, 1)
   for (int64_t g0 = 0; g0 < nblk; g0 += 64) {
     const int nb = (int)min<int64_t>(64, nblk - g0);
     const int64_t fb = job.f0 + (g0 + lane) * kBlock;
@@ -3213,7 +3218,7 @@ __global__ __launch_bounds__(256) void param_mod_kernel(const ParamModJob* __res
     const int64_t f = job.f0 + i;
     const int64_t fs = job.krate ? f - (f % kBlock) : f;   // k-rate: `_input.Buffer.GetChannelSpan(0)[0]` and the block-start value
     const float intr = job.intrinsic ? gptr(job.intrinsic)[fs] : job.value;
-    gptr(job.out)[f] = fminf(fmaxf(intr + gptr(job.mod)[fs], job.vmin), job.vmax);   // Math.Clamp(intrinsicValue + modulation, min, max)
+    gptr(job.out)[f] = clamp_ref(intr + gptr(job.mod)[fs], job.vmin, job.vmax);   // Math.Clamp(intrinsicValue + modulation, min, max)
   }
 }
 void launch_param_mod(hipStream_t s, const ParamModJob* jobs_dev, int njobs, int64_t max_n) {

@@ -253,9 +253,44 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
             dg.Connect(prm)
             if handles is not None:
                 handles.setdefault("mod_gains", []).append(dg)
+    # seeds >= 80000: a signal into voices' PlaybackRate (two-stage chunks).  Every modulator is a node of its own with no inputs, so
+    # its cone holds neither a source with a modulated rate nor a convolver, and no voice's output reaches a rate.  (Drawn from a
+    # generator of its own: older seeds keep their graphs.)
+    if seed >= RATE_MOD_SEEDS:
+        rng6 = np.random.default_rng(seed * 13 + 1)
+        for chain in voice_chains:
+            if rng6.random() < 0.6:
+                rate_modulator(ctx, rng6, chain[0], frames / SR, handles)
     if handles is not None:
         handles.update(buses=buses, shared_ir=shared_ir)
     return dest_ch
+
+
+RATE_MOD_SEEDS = 80000
+
+
+def rate_modulator(ctx, rng, s, dur, handles=None):
+    """An oscillator or a looping noise buffer through a depth gain (0.02 - 0.3) into `s.PlaybackRate`; returns the depth gain."""
+    if rng.random() < 0.6:
+        m = OscillatorNode(ctx)
+        m.Type = OscillatorType(int(rng.integers(0, 4)))
+        m.Frequency.Value = float(rng.uniform(0.5, 40.0))
+    else:
+        m = AudioBufferSourceNode(ctx)
+        m.Buffer = PlayableAudioBuffer.FromMonoArray(rng.uniform(-1, 1, int(rng.integers(64, 3000))).astype(np.float32),
+                                                     int(rng.choice([SR, 44100])))
+        m.Loop = True
+    dg = GainNode(ctx)
+    dg.Gain.Value = float(rng.uniform(0.02, 0.3))
+    m.Connect(dg)
+    dg.Connect(s.PlaybackRate)
+    when = float(rng.choice([0.0, rng.uniform(0, dur * 0.5)]))
+    m.Start(when)
+    if rng.random() < 0.2:
+        m.Stop(float(rng.uniform(when, dur)))
+    if handles is not None:
+        handles.setdefault("rate_mods", []).append((s, dg, m))
+    return dg
 
 
 def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None):
@@ -444,6 +479,60 @@ def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None)
         parked.append(n)
         return "unplug:" + type(n).__name__
 
+    # seeds >= 80000: edits of modulated playbackRates -- a modulator connected / disconnected, a loop region, a voice started with an
+    # offset and a duration, PlaybackRate.Value or automation on a modulated rate.  A generator of its own: older sessions keep theirs.
+    rng7 = np.random.default_rng(seed ^ 0x7A7E)
+    rate_mods = h.setdefault("rate_mods", [])
+
+    def buffer_sources():
+        return [x for x in sources if id(x) not in dead and x.Buffer is not None]
+
+    def rate_act(now):
+        kind = str(rng7.choice(["rate_mod_on", "rate_mod_off", "loop_region", "offset_voice", "rate_write"]))
+        live = [m for m in rate_mods if id(m[0]) not in dead]
+        if kind == "rate_mod_on":
+            cands = buffer_sources()
+            if cands:
+                rate_modulator(ctx, rng7, cands[int(rng7.integers(0, len(cands)))], 0.02, h)
+        elif kind == "rate_mod_off":
+            if live:
+                s, dg, m = live[int(rng7.integers(0, len(live)))]
+                dg.Disconnect(s.PlaybackRate)
+                rate_mods.remove((s, dg, m))
+        elif kind == "loop_region":
+            cands = buffer_sources()
+            if cands:
+                s = cands[int(rng7.integers(0, len(cands)))]
+                n, sr = s.Buffer.Length, s.Buffer.SampleRate
+                a = int(rng7.integers(0, max(1, n - 2)))
+                b = int(rng7.integers(a + 2, n + 300))   # (past the end: clamped to the buffer's length)
+                s.LoopStart = (a + 0.5) / sr
+                s.LoopEnd = (b + 0.5) / sr
+                if rng7.random() < 0.5:
+                    s.Loop = True
+        elif kind == "offset_voice":
+            s = AudioBufferSourceNode(ctx)
+            n = int(rng7.integers(300, 4000))
+            sr = int(rng7.choice([SR, 44100, 22050]))
+            s.Buffer = PlayableAudioBuffer.FromChannelArrays(
+                [(rng7.standard_normal(n) * 0.2).astype(np.float32) for _ in range(int(rng7.choice([1, 2, 3])))], sr)
+            s.Loop = bool(rng7.random() < 0.5)
+            tgt = [b for b in h["buses"] if id(b) not in dead]
+            s.Connect(tgt[0] if tgt and rng7.random() < 0.5 else ctx.Destination)
+            if rng7.random() < 0.8:
+                rate_modulator(ctx, rng7, s, 0.02, h)
+            s.Start(now + float(rng7.uniform(0, 0.01)), float(rng7.uniform(0, n / sr)), float(rng7.uniform(0.002, 0.05)))
+            sources.append(s)
+        else:
+            if live:
+                s = live[int(rng7.integers(0, len(live)))][0]
+                if rng7.random() < 0.5:
+                    s.PlaybackRate.Value = float(rng7.choice([0.5, 1.0, 1.5, 2.0]))
+                else:
+                    s.PlaybackRate.SetValueAtTime(float(rng7.uniform(0.5, 2.0)), now + float(rng7.uniform(0, 0.01)))
+                    s.PlaybackRate.LinearRampToValueAtTime(float(rng7.uniform(0.5, 2.0)), now + float(rng7.uniform(0.01, 0.04)))
+        return kind
+
     global last_pieces, details
     last_pieces = []
     details = []
@@ -466,5 +555,10 @@ def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None)
                 log.append((piece, k, None))
                 details.append((piece, k, list(detail), ctx.CurrentTime))
             except Exception as e:  # the other implementation must raise the same exception type at the same point
+                log.append((piece, "?", type(e).__name__))
+        if seed >= RATE_MOD_SEEDS and rng7.random() < 0.6:
+            try:
+                log.append((piece, rate_act(ctx.CurrentTime), None))
+            except Exception as e:
                 log.append((piece, "?", type(e).__name__))
     return out, log

@@ -122,3 +122,96 @@ def test_session_42867_with_formulation_d_forced():
     ref, ref_log, got, got_log = _session_pair(42867, coarse=1)
     assert ref_log == got_log
     assert G.rms(ref - got) <= 1e-5
+
+
+def _graph_pair(seed, coarse=0, opts=None):
+    """The graph of `seed` rendered by the oracle in one piece and by the device in uneven pieces (as test_random_graph_matches_oracle)."""
+    frames = 128 * 36
+    o = OracleContext(48000)
+    ch = build_random_graph(o, seed, frames)
+    ref = np.zeros((ch, frames), np.float32)
+    o.Render(ref, frames)
+    h = OfflineAudioContext(48000)
+    h.SetOption("max_chunk_blocks", 11)
+    h.SetOption("coarse_min_blocks", 1 if coarse else 1 << 30)
+    for k, v in (opts or {}).items():
+        h.SetOption(k, v)
+    build_random_graph(h, seed, frames)
+    got = np.zeros_like(ref)
+    pos = 0
+    rng = np.random.default_rng(1000 + seed)
+    while pos < frames:
+        n = int(min(frames - pos, rng.integers(1, 128 * 9)))
+        h.Render(got, n, pos)
+        pos += n
+    return ref, got
+
+
+# seeds >= 80000: modulated playbackRates (signals into voices' PlaybackRate, and in sessions edits of them: modulators connected and
+# disconnected, loop regions, voices started with an offset and a duration, rate writes and automation).  The generator builds none
+# of the graphs chunkTopology refuses, so a NotSupportedException is a failure here, and every seed is held to the absolute bound.
+RATE_GRAPH_SEEDS = list(range(80000, 80032))
+RATE_SESSION_SEEDS = list(range(80000, 80024))
+
+
+@pytest.mark.parametrize("coarse", [0, 1])
+@pytest.mark.parametrize("seed", RATE_GRAPH_SEEDS)
+def test_random_graph_modulated_rates_matches_oracle(seed, coarse):
+    ref, got = _graph_pair(seed, coarse)
+    assert G.rms(ref) > 1e-3
+    err = G.rms(ref - got)
+    assert err <= 1e-5, (seed, err)
+
+
+@pytest.mark.parametrize("seed", RATE_GRAPH_SEEDS[:12])
+def test_random_graph_modulated_rates_host_replay_matches_oracle(seed):
+    ref, got = _graph_pair(seed, opts={"rate_mod_walk": 0})
+    err = G.rms(ref - got)
+    assert err <= 1e-5, (seed, err)
+
+
+@pytest.mark.parametrize("coarse", [0, 1])
+@pytest.mark.parametrize("seed", RATE_SESSION_SEEDS)
+def test_random_edit_session_modulated_rates_matches_oracle(seed, coarse):
+    ref, ref_log, got, got_log = _session_pair(seed, coarse=coarse)
+    assert ref_log == got_log
+    assert G.rms(ref) > 1e-3
+    err = G.rms(ref - got)
+    assert err <= 1e-5, (seed, err)
+
+
+@pytest.mark.parametrize("seed", RATE_SESSION_SEEDS[:8])
+def test_random_edit_session_modulated_rates_host_replay_matches_oracle(seed):
+    from tests._fuzz import run_random_session
+    ref, ref_log = run_random_session(OracleContext(48000), seed)
+    h = OfflineAudioContext(48000)
+    h.SetOption("max_chunk_blocks", 11)
+    h.SetOption("rate_mod_walk", 0)
+    got, got_log = run_random_session(h, seed)
+    assert ref_log == got_log
+    err = G.rms(ref - got)
+    assert err <= 1e-5, (seed, err)
+
+
+# The deviations DESIGN.md leaves open, kept as strict xfails: each one still deviates by more than the contract, and a fix shows up
+# here on its own.  (All five deviate with every convolver formulation; they run with the default ones.)
+_DELAY_FLAG = "DESIGN.md §8 DelayNode: the predicted flag of a delay whose delay time is modulated at audio rate (\"What is left\")"
+_LIBM = "DESIGN.md §8 libm class: device (float)cos((double)x) vs the C library's cosf behind an automated biquad (tools/fuzz_libm_class.py)"
+
+
+@pytest.mark.parametrize("kind,seed", [
+    pytest.param("session", 63862, marks=pytest.mark.xfail(strict=True, reason=_DELAY_FLAG)),
+    pytest.param("session", 73560, marks=pytest.mark.xfail(strict=True, reason=_DELAY_FLAG)),
+    pytest.param("graph", 73778, marks=pytest.mark.xfail(strict=True, reason=_DELAY_FLAG)),
+    pytest.param("session", 30228, marks=pytest.mark.xfail(strict=True, reason=_LIBM)),
+    pytest.param("session", 60235, marks=pytest.mark.xfail(strict=True, reason=_LIBM)),
+])
+def test_documented_open_seed(kind, seed):
+    if kind == "graph":
+        ref, got = _graph_pair(seed)
+    else:
+        ref, ref_log, got, got_log = _session_pair(seed)
+        assert ref_log == got_log
+    err = G.rms(ref - got)
+    scale = max(G.rms(ref), 1e-3)
+    assert err <= 1e-5 * max(1.0, scale if seed >= 50000 else 1.0) and err <= 2e-5 * scale, (seed, err, scale)
