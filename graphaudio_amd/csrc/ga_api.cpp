@@ -100,6 +100,9 @@ int64_t Context::chunkLimit(int64_t) {
         int convRowsMax = 0;
         for (auto& g : groups) convRowsMax = std::max(convRowsMax, (int)((g->rows.size() + 127) / 128 * 128));
         perBlock += (double)convRowsMax * kBins * 4.0 * 4.0;
+        int tailMax = kCoarseMaxP;   // the longest carried tail stretches every Y row of its stage (Context::chunkConvScratch): counted for all slots
+        for (auto& np : nodes)
+          if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath == 4) tailMax = std::max(tailMax, np->ir->coarseP);
         for (auto& np : nodes)   // private-IR convolvers (formulations B / C): y rows + x rows in both plane pairs
           if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath == 4)
             // formulation D: X frames of the input channels + (at worst, nothing fused) Y frames of the slots: 64 KB per 8192 samples
@@ -108,7 +111,7 @@ int64_t Context::chunkLimit(int64_t) {
             // ... and per input row the P' history windows in front of the chunk + the window behind it, per slot the P' blocks of a
             // carried tail: 64 KB each, whatever the chunk's length (1 GB at 1024 voices x 8 partitions)
             const double inCh = np->isTrueStereo ? 2 : np->ir->nch, slots = np->isTrueStereo ? 4 : np->ir->nch;
-            fixedBytes += (inCh * (np->ir->coarseP + 1) + slots * (double)kCoarseMaxP) * 65536.0;
+            fixedBytes += (inCh * (np->ir->coarseP + 1) + slots * (double)tailMax) * 65536.0;
           }
           else if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath != 1)
             perBlock += (double)(np->ir->nch + 2 * (np->isTrueStereo ? 2 : np->ir->nch)) * kBins * 8.0;
@@ -384,6 +387,7 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);
     else if (k == "coarse_premix") c.coarsePremix = value != 0;
+    else if (k == "coarse_long") c.coarseLong = value != 0;
     else if (k == "coarse_ext_history") c.coarseExtHist = value != 0;
     else if (k == "coarse_wide") c.coarseWide = value != 0;
     else if (k == "gain_pass_through") c.gainPassThrough = value != 0;

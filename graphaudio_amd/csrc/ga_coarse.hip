@@ -715,6 +715,342 @@ static const char* launch_coarse_sum(hipStream_t s, const CoarseJob* jobs_dev, i
   return CW == 1 ? "coarse_sum_kernel<1>" : (CW == 2 ? "coarse_sum_kernel<2>" : "coarse_sum_kernel<4>");
 }
 
+// =====================================================================================================================
+//  Impulse responses of more than kCoarseMaxP partitions (up to kCoarseMaxParts): the partition sum in SEGMENTS.  The sum is
+//  associative over partitions,
+//        Y[t] = sum_{s < S} sum_{p < 16} X[t - 16 s - p] . H[16 s + p]          S = ceil(P' / 16),
+//  and a segment is the problem the two kernels above solve -- 16 partitions, the same LDS footprint -- with the signal's frames
+//  shifted back by 16 s and the spectra advanced by 16 s partitions.  The accumulators stay in registers across all segments (of all
+//  terms) of a job, so Y is written once whatever P' is.  The windows that exist ([u_lo, u_hi] of the job) are seen 16 s frames
+//  later by segment s: the zero rows of the staging are per segment, and segments none of whose windows exist are left out.
+//  These are kernels of their own: the instances for P' <= kCoarseMaxP compile from the code above, untouched.
+// =====================================================================================================================
+// general kernel: the planner expands every term into (term, segment) PAIRS -- CoarseTerm::frame0 = frame of the window
+// -(off + kCoarseMaxP - 1) of the signal (may lie in front of the row: such frames are never fetched), h[c] advanced by `off`
+// partitions, pad_ = off + 256 x partitions of the segment (a multiple of PB; the stored spectra are padded with zero rows).
+// One workgroup per CU at every column count (16 partitions of double-buffered spectra: 89 + 32 KB at 2 columns, 48 + 64 KB at 4): the
+// 256 registers of two waves per SIMD.
+template <int CW, int TW, int PB, int WV>
+__global__ __launch_bounds__(64 * WV, WV / 4) void coarse_mac_seg_kernel(const CoarseJob* __restrict jobs, const CoarseTerm* __restrict terms,
+                                                                                      const float2* __restrict X, float2* __restrict Y, int y_frames, int NFA) {
+  static_assert(CW <= 4, "segments: 1, 2 or 4 columns (16-column pieces are made for P' <= 4 only)");
+  extern __shared__ f2 mlds[];   // (all of the kernel's LDS is this one array)
+  const CoarseJob J = jobs[blockIdx.y];
+  const int tile = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int P = kCoarseMaxP;             // partitions of a segment: the LDS image is the one of a 16-partition job
+  const int nT = J.n_t;
+  const int NF = nT + P - 1;                 // frames of a pair: frame fr = window J.t0 - off - (P - 1) + fr
+  f2* xs0 = mlds;
+  f2* xs1 = mlds + (size_t)NFA * 64;
+  f2* hs0 = mlds + (size_t)2 * NFA * 64;
+  f2* hs1 = hs0 + (size_t)P * CW * 64;
+  const int twr = (nT + WV - 1) / WV;   // coarse blocks per wave (<= TW)
+  const int t0w = wv * twr;
+  const bool special = tile == 0;
+  const bool lane0 = special && lane == 0;
+  const size_t binoff = (size_t)tile * 64;
+  typedef __attribute__((address_space(3))) void* lds_t;
+  constexpr int XR = ((WV * TW + kCoarseMaxP) * 32 + (64 * WV) - 1) / (64 * WV);
+  // staging of one pair: zero rows for the windows that do not exist FOR THIS PAIR, the others global memory -> LDS directly
+  // (the zero rows are written BEFORE the pair's direct-to-LDS loads are issued: a plain LDS store behind them would wait for them)
+  auto zero_x = [&](const CoarseTerm& T, f2* xs) {
+    const int w0 = J.t0 - (T.pad_ & 255) - (P - 1);
+    const int fr_lo = max(0, J.u_lo - w0), fr_hi = min(NF - 1, J.u_hi - w0);
+    for (int idx = tid; idx < NF * 32; idx += (64 * WV)) {
+      const int fr = idx >> 5;
+      if (fr < fr_lo || fr > fr_hi) *reinterpret_cast<v4f*>(xs + fr * 64 + 2 * (idx & 31)) = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  auto issue_x = [&](const CoarseTerm& T, f2* xs) {
+    const int w0 = J.t0 - (T.pad_ & 255) - (P - 1);
+    const int fr_lo = max(0, J.u_lo - w0), fr_hi = min(NF - 1, J.u_hi - w0);
+#pragma unroll
+    for (int r = 0; r < XR; r++) {
+      const int fr0 = ((64 * WV) / 32) * r + 2 * wv;   // (uniform)
+      const int fr = fr0 + (lane >> 5), of = lane & 31;
+      if (fr >= fr_lo && fr <= fr_hi)
+        __builtin_amdgcn_global_load_lds(gptr(X + (size_t)(T.frame0 + J.t0 + fr) * kCoarseBins + binoff + 2 * of), (lds_t)(xs + fr0 * 64), 16, 0, 0);
+    }
+  };
+  auto issue_h = [&](const CoarseTerm& T, f2* hs) {   // (partitions of the pair) x CW rows of 512 bytes
+    const int np = T.pad_ >> 8;
+    for (int pc0 = 2 * wv; pc0 < np * CW; pc0 += 2 * WV) {
+      const int pc = pc0 + (lane >> 5), of = lane & 31;
+      const int pA = pc0 / CW, cA = pc0 % CW, pB = (pc0 + 1) / CW, cB = (pc0 + 1) % CW;
+      const float2* rowA = T.h[cA] + (size_t)pA * kCoarseBins;
+      const float2* rowB = pc0 + 1 < np * CW ? T.h[cB] + (size_t)pB * kCoarseBins : rowA;
+      if (pc < np * CW)
+        __builtin_amdgcn_global_load_lds(gptr(((lane >> 5) ? rowB : rowA) + binoff + 2 * of), (lds_t)(hs + pc0 * 64), 16, 0, 0);
+    }
+  };
+
+  f2 acc[TW][CW];
+#pragma unroll
+  for (int tt = 0; tt < TW; tt++)
+#pragma unroll
+    for (int c = 0; c < CW; c++) acc[tt][c] = f2{0.f, 0.f};
+
+  const CoarseTerm* __restrict T = terms + J.term0;
+  zero_x(T[0], xs0);
+  issue_x(T[0], xs0);
+  issue_h(T[0], hs0);
+  __syncthreads();   // (waits for the workgroup's direct-to-LDS loads: the barrier's fence includes vmcnt(0))
+  for (int i = 0; i < J.n_terms; i++) {
+    f2* xs = (i & 1) ? xs1 : xs0;
+    f2* hs = (i & 1) ? hs1 : hs0;
+    // the next pair lands in the other buffers while this one is accumulated (their last readers passed the barrier below)
+    if (i + 1 < J.n_terms) {
+      zero_x(T[i + 1], (i & 1) ? xs0 : xs1);
+      issue_h(T[i + 1], (i & 1) ? hs0 : hs1);
+      issue_x(T[i + 1], (i & 1) ? xs0 : xs1);
+    }
+    if (t0w < nT) {
+      const int off = T[i].pad_ & 255, np = T[i].pad_ >> 8;
+      auto sweep = [&](auto sp) {   // the sweep of coarse_mac_kernel (operands of partition block b + 1 requested before the fmas of block b)
+        constexpr bool SP = decltype(sp)::value;
+        constexpr int PBX = PB, NX = TW + PBX - 1, NH = PBX * CW;
+        auto fma1 = [&](int tt, int c, f2 x, f2 h) {
+          if constexpr (!SP) {
+            acc[tt][c] = cfmap(x, h, acc[tt][c]);
+          } else {
+            const f2 gen = cfmap(x, h, acc[tt][c]);
+            const f2 pk = __builtin_elementwise_fma(x, h, acc[tt][c]);   // two real bins side by side
+            acc[tt][c] = lane0 ? pk : gen;
+          }
+        };
+        f2 hA[NH], xA[NX], hB[NH], xB[NX];
+        auto fetch = [&](int pb, f2* h, f2* x) {
+          lds_rd_seq<512>(h, lds_addr(hs + pb * CW * 64 + lane), std::make_integer_sequence<int, NH>{});
+          lds_rd_seq<512>(x, lds_addr(xs + (t0w + (P - 1) - pb - (PBX - 1)) * 64 + lane), std::make_integer_sequence<int, NX>{});
+        };
+        auto arrive = [&](f2* h, f2* x) {
+          lds_wait_all();
+          lds_pin<NH>(h);
+          lds_pin<NX>(x);
+        };
+        auto fmas = [&](const f2* h, const f2* x) {
+#pragma unroll
+          for (int j = 0; j < PBX; j++)
+#pragma unroll
+            for (int tt = 0; tt < TW; tt++)
+#pragma unroll
+              for (int c = 0; c < CW; c++) fma1(tt, c, x[tt - j + (PBX - 1)], h[j * CW + c]);
+        };
+        // partition blocks whose windows u = J.t0 + t0w + tt - off - p all lie outside [u_lo, u_hi] multiply zero rows: skipped
+        const int tw0 = J.t0 + t0w - off;
+        const int pbLo = max(0, (tw0 - J.u_hi) / PBX * PBX), pbHi = min(np, tw0 + TW - J.u_lo);
+        if (pbLo < pbHi) {
+          fetch(pbLo, hA, xA);
+          for (int pb = pbLo; pb < pbHi; pb += 2 * PBX) {
+            arrive(hA, xA);
+            const bool second = pb + PBX < pbHi;
+            if (second) fetch(pb + PBX, hB, xB);
+            fmas(hA, xA);
+            if (!second) break;
+            arrive(hB, xB);
+            if (pb + 2 * PBX < pbHi) fetch(pb + 2 * PBX, hA, xA);
+            fmas(hB, xB);
+          }
+        }
+      };
+      if (special) sweep(std::true_type{});
+      else sweep(std::false_type{});
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int tt = 0; tt < TW; tt++) {
+    const int t = t0w + tt;
+    if (tt < twr && t < nT) {
+#pragma unroll
+      for (int c = 0; c < CW; c++)
+        stg2(Y + ((size_t)(J.yrow0 + c) * y_frames + J.t0 + t) * kCoarseBins + binoff + lane, v2f{acc[tt][c].x, acc[tt][c].y});
+    }
+  }
+}
+
+// reduction kernel (one impulse response for all terms of the job): the streaming reduction of the terms' frames into the sum tile
+// followed by one sweep is repeated per segment, y[][] is kept.  CoarseTerm::frame0 = frame of the window u = 0 of the signal here
+// (segment s reads the windows J.t0 - 16 s - 15 .. of every term), J.P = P' (all of them).  Two waves per SIMD -- ONE workgroup of
+// 512 threads per CU -- and so up to 256 registers (150 - 174 used): the accumulators, the reduction's words in flight and the sweep's
+// window fit without scratch.
+template <int CW>
+__global__ __launch_bounds__(kSumThreads, 2) void coarse_sum_seg_kernel(const CoarseJob* __restrict jobs, const CoarseTerm* __restrict terms,
+                                                                        const float2* __restrict X, float2* __restrict Y, int y_frames, int NFA) {
+  constexpr int TW = kCoarseSumJobBlocks(CW) / kSumWaves;
+  constexpr int XR = ((kCoarseSumJobBlocks(CW) + kCoarseMaxP) * 32 + kSumThreads - 1) / kSumThreads;
+  constexpr int PS = kCoarseMaxP;         // partitions of a segment
+  extern __shared__ f2 mlds[];
+  const CoarseJob J = jobs[blockIdx.y];
+  const int tile = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nT = J.n_t, NF = nT + PS - 1, nterms = J.n_terms;
+  const int twr = (nT + kSumWaves - 1) / kSumWaves, t0w = wv * twr;
+  const bool lane0 = tile == 0 && lane == 0;
+  const size_t binoff = (size_t)tile * 64;
+  f2* S = mlds;                           // NFA frames x 64 bins: the summed spectra of the segment's windows
+  f2* hs = mlds + (size_t)NFA * 64;       // 16 x CW rows of 64 bins
+  typedef __attribute__((address_space(3))) void* lds_t;
+  const CoarseTerm* __restrict T = terms + J.term0;
+  static_assert(kCoarseJobTerms <= 64, "one lane per term");
+  const int f0v = lane < nterms ? T[lane].frame0 : 0;
+  f2 y[TW][CW];
+#pragma unroll
+  for (int tt = 0; tt < TW; tt++)
+#pragma unroll
+    for (int c = 0; c < CW; c++) y[tt][c] = f2{0.f, 0.f};
+  for (int p0 = 0; p0 < J.P; p0 += PS) {
+    const int np = min(PS, J.P - p0);
+    const int w0 = J.t0 - p0 - (PS - 1);   // window of frame 0 of this segment
+    const int fr_lo = max(0, J.u_lo - w0), fr_hi = min(NF - 1, J.u_hi - w0);
+    const int nvf = fr_hi - fr_lo + 1;
+    if (nvf <= 0) continue;                // (uniform: none of the segment's windows exists)
+    const int nw = (nvf * 32 + kSumThreads - 1) / kSumThreads;
+    __syncthreads();                       // the previous segment's sweep has read S and hs
+    for (int pc0 = 2 * wv; pc0 < np * CW; pc0 += 2 * kSumWaves) {
+      const int pc = pc0 + (lane >> 5), of = lane & 31;
+      if (pc < np * CW)
+        __builtin_amdgcn_global_load_lds(gptr(T[0].h[pc % CW] + (size_t)(p0 + pc / CW) * kCoarseBins + binoff + 2 * of), (lds_t)(hs + pc0 * 64), 16, 0, 0);
+    }
+    int64_t woff[XR];
+    v4f acc[XR];
+#pragma unroll
+    for (int r = 0; r < XR; r++) {
+      const int idx = tid + kSumThreads * r;
+      const int fr = fr_lo + min(idx >> 5, nvf - 1), of = idx & 31;
+      woff[r] = (int64_t)(w0 + fr) * kCoarseBins + (int64_t)binoff + 2 * of;   // (from the term's window 0)
+      acc[r] = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    auto stream = [&](auto nwc) {
+      constexpr int NW = decltype(nwc)::value;
+      constexpr int AH = NW >= 6 ? 3 : kSumAhead;
+      int i = 0;
+      for (; i + AH <= nterms; i += AH) {
+        v4f ld[AH][NW];
+#pragma unroll
+        for (int u = 0; u < AH; u++) {
+          const float2* __restrict Xt = X + (int64_t)__builtin_amdgcn_readlane(f0v, i + u) * kCoarseBins;
+#pragma unroll
+          for (int r = 0; r < NW; r++) ld[u][r] = ldg4(Xt + woff[r]);
+        }
+#pragma unroll
+        for (int u = 0; u < AH; u++)
+#pragma unroll
+          for (int r = 0; r < NW; r++) acc[r] += ld[u][r];
+      }
+      for (; i < nterms; i++) {
+        const float2* __restrict Xt = X + (int64_t)__builtin_amdgcn_readlane(f0v, i) * kCoarseBins;
+#pragma unroll
+        for (int r = 0; r < NW; r++) acc[r] += ldg4(Xt + woff[r]);
+      }
+    };
+    static_assert(XR <= 6, "one case per word count below");
+    switch (nw) {   // (uniform)
+      case 1: stream(std::integral_constant<int, 1>{}); break;
+      case 2: stream(std::integral_constant<int, 2>{}); break;
+      case 3: stream(std::integral_constant<int, XR >= 3 ? 3 : XR>{}); break;
+      case 4: stream(std::integral_constant<int, XR >= 4 ? 4 : XR>{}); break;
+      case 5: stream(std::integral_constant<int, XR >= 5 ? 5 : XR>{}); break;
+      case 6: stream(std::integral_constant<int, XR >= 6 ? 6 : XR>{}); break;
+      default: break;
+    }
+    for (int idx = tid; idx < NF * 32; idx += kSumThreads) {
+      const int fr = idx >> 5;
+      if (fr < fr_lo || fr > fr_hi) *reinterpret_cast<v4f*>(S + fr * 64 + 2 * (idx & 31)) = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int r = 0; r < XR; r++) {
+      const int idx = tid + kSumThreads * r;
+      const int fv = idx >> 5, of = idx & 31;
+      if (fv < nvf) *reinterpret_cast<v4f*>(S + (fr_lo + fv) * 64 + 2 * of) = acc[r];
+    }
+    __syncthreads();   // (its fence also waits for the spectra's direct-to-LDS loads)
+    if (t0w < nT) {
+      // y[tt][c] += sum_{p < np} S[t0w + tt - p] H_c[p0 + p]; tile 0, lane 0 (two real bins) multiplies element-wise
+      const f2* __restrict xb = S + (t0w + (PS - 1)) * 64 + lane;   // frame of (tt = 0, p = 0)
+      f2 xv[TW];
+#pragma unroll
+      for (int q = 1; q < TW; q++) xv[q] = xb[q * 64];
+      for (int p = 0; p < np; p++) {
+#pragma unroll
+        for (int q = TW - 1; q > 0; q--) xv[q] = p == 0 ? xv[q] : xv[q - 1];
+        xv[0] = xb[-p * 64];
+        f2 h[CW];
+#pragma unroll
+        for (int c = 0; c < CW; c++) h[c] = hs[(p * CW + c) * 64 + lane];
+#pragma unroll
+        for (int tt = 0; tt < TW; tt++)
+#pragma unroll
+          for (int c = 0; c < CW; c++) {
+            const f2 gen = cfmap(xv[tt], h[c], y[tt][c]);
+            const f2 pk = __builtin_elementwise_fma(xv[tt], h[c], y[tt][c]);
+            y[tt][c] = lane0 ? pk : gen;
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int tt = 0; tt < TW; tt++) {
+    const int t = t0w + tt;
+    if (tt < twr && t < nT) {
+#pragma unroll
+      for (int c = 0; c < CW; c++)
+        stg2(Y + ((size_t)(J.yrow0 + c) * y_frames + J.t0 + t) * kCoarseBins + binoff + lane, v2f{y[tt][c].x, y[tt][c].y});
+    }
+  }
+}
+
+// frames the sweep of the last active wave touches: t0w + TW + P - 1 with t0w = (active waves - 1) * ceil(n_t / waves)
+static int coarse_seg_frames(int max_t, int waves, int tw) {
+  int NFA = 0;
+  for (int nt = 1; nt <= max_t; nt++) {
+    const int twr = (nt + waves - 1) / waves, wl = (nt + twr - 1) / twr - 1;
+    NFA = std::max(NFA, wl * twr + tw + kCoarseMaxP - 1);
+  }
+  return NFA;
+}
+template <int CW>
+static const char* launch_coarse_sum_seg(hipStream_t s, const CoarseJob* jobs_dev, int njobs, const CoarseTerm* terms_dev, const float2* X, float2* Y,
+                                         int y_frames, int max_t) {
+  const int NFA = coarse_seg_frames(max_t, kSumWaves, kCoarseSumJobBlocks(CW) / kSumWaves);
+  const size_t lds = ((size_t)NFA * 64 + (size_t)kCoarseMaxP * CW * 64) * sizeof(float2);
+  if (lds > 160 * 1024) launch_fail("coarse multiply-accumulate: staging does not fit the LDS");
+  static LdsLimit lim;
+  lim.raise((const void*)coarse_sum_seg_kernel<CW>, lds, "cannot raise the dynamic LDS limit of the coarse multiply-accumulate");
+  for (int j0 = 0; j0 < njobs; j0 += 32768)
+    hipLaunchKernelGGL((coarse_sum_seg_kernel<CW>), dim3(kCoarseBins / 64, std::min(32768, njobs - j0)), dim3(kSumThreads), lds, s, jobs_dev + j0, terms_dev,
+                       X, Y, y_frames, NFA);
+  return CW == 1 ? "coarse_sum_seg_kernel<1>" : (CW == 2 ? "coarse_sum_seg_kernel<2>" : "coarse_sum_seg_kernel<4>");
+}
+template <int CW, int TW>
+static const char* launch_coarse_mac_seg(hipStream_t s, const CoarseJob* jobs_dev, int njobs, const CoarseTerm* terms_dev, const float2* X, float2* Y,
+                                         int y_frames, int max_t) {
+  constexpr int PB = 4;   // (the planner rounds a segment's partitions up to a multiple of 4: zero rows of the stored spectra)
+  const int NFA = coarse_seg_frames(max_t, kMacWaves, TW);
+  const size_t lds = ((size_t)2 * NFA * 64 + (size_t)2 * kCoarseMaxP * CW * 64) * sizeof(float2);
+  if (lds > 160 * 1024) launch_fail("coarse multiply-accumulate: staging does not fit the LDS");
+  static LdsLimit lim;
+  lim.raise((const void*)coarse_mac_seg_kernel<CW, TW, PB, kMacWaves>, lds, "cannot raise the dynamic LDS limit of the coarse multiply-accumulate");
+  for (int j0 = 0; j0 < njobs; j0 += 32768)
+    hipLaunchKernelGGL((coarse_mac_seg_kernel<CW, TW, PB, kMacWaves>), dim3(kCoarseBins / 64, std::min(32768, njobs - j0)), dim3(64 * kMacWaves), lds, s,
+                       jobs_dev + j0, terms_dev, X, Y, y_frames, NFA);
+  static const std::string name = "coarse_mac_seg_kernel<" + std::to_string(CW) + "," + std::to_string(TW) + "," + std::to_string(PB) + ">";
+  return name.c_str();
+}
+template <int CW>
+static const char* launch_coarse_seg_cw(hipStream_t s, const CoarseJob* jobs_dev, int njobs, const CoarseTerm* terms_dev, const float2* X, float2* Y,
+                                        int y_frames, int max_t, bool any_private) {
+  if (!any_private) return launch_coarse_sum_seg<CW>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t);
+  if (max_t <= 2 * kMacWaves) return launch_coarse_mac_seg<CW, 2>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t);
+  if constexpr (CW <= 2) {
+    if (max_t <= 8 * kMacWaves) return launch_coarse_mac_seg<CW, 8>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t);
+    return launch_coarse_mac_seg<CW, GA_MAC_TW>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t);
+  } else {
+    return launch_coarse_mac_seg<CW, GA_MAC_TW4>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t);
+  }
+}
+
 // bin 0 of the packed spectra holds the two REAL bins (X[0], X[8192]): their products are element-wise.  The 16-column instance of
 // the general kernel computes a complex product there like everywhere else; this kernel writes the right value over it:
 // thread = (output block, column) of a job, Y[c][t][0] = sum over terms, partitions of X[t - p][0] (.) H_c[p][0].
@@ -914,6 +1250,13 @@ const char* launch_coarse_mac(hipStream_t s, const CoarseJob* jobs_dev, int njob
   if (max_t > (any_private ? kCoarseJobBlocks(cw) : kCoarseSumJobBlocks(cw))) launch_fail("coarse multiply-accumulate: too many coarse blocks in a job");
   if (const char* e = expenv("GA_COARSE_PB")) pb = std::min(pb, std::max(1, atoi(e)));   // measurements only
   if (pb != 1 && pb != 2 && pb != 4 && pb != 8 && pb != 16) launch_fail("coarse multiply-accumulate: unsupported partition block");
+  if (maxP > kCoarseMaxP) {   // segmented partition sum (impulse responses of more than 131,072 taps): kernels of their own
+    if (maxP > kCoarseMaxParts) launch_fail("coarse multiply-accumulate: too many partitions");
+    if (cw == 1) return launch_coarse_seg_cw<1>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, any_private);
+    if (cw == 2) return launch_coarse_seg_cw<2>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, any_private);
+    if (cw == 4) return launch_coarse_seg_cw<4>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, any_private);
+    launch_fail("coarse multiply-accumulate: unsupported column count");
+  }
   if (cw == 1) return launch_coarse_mac_cw<1>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, maxP, any_private, pb);
   if (cw == 2) return launch_coarse_mac_cw<2>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, maxP, any_private, pb);
   if (cw == 4) return launch_coarse_mac_cw<4>(s, jobs_dev, njobs, terms_dev, X, Y, y_frames, max_t, maxP, any_private, pb);

@@ -795,7 +795,8 @@ void Context::assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks)
     IrSpectra* ir = nd.ir.get();
     const int channels = ir->nch;
     const bool pathC = useTimeFft && ir->P > 64 && ir->P <= 1024;   // FFT along the block axis (N2 <= 4096)
-    // coarse partitions (formulation D): impulse responses of 8,193 .. 131,072 taps when the render comes in long chunks --
+    // coarse partitions (formulation D): impulse responses of 8,193 .. 1,048,576 taps (beyond 131,072: the segmented partition sum,
+    // option "coarse_long") when the render comes in long chunks --
     // a short chunk would pay the transforms of the whole input history for a few blocks of output (the node keeps the
     // formulation it starts with: its state is formulation specific)
     const int coarseParts = (int)(((int64_t)ir->P * kBlock + kCoarseBlock - 1) / kCoarseBlock);
@@ -806,7 +807,7 @@ void Context::assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks)
     // 0.25 s echo: 69 ms per 10 s on formulation C, 22 ms on D).  coarse_min_blocks >= 2^29 still means "never".
     const bool manyShare = users[ir] >= 8 && nd.outputs.size() == 1 && nd.outputs[0].connectedInputs.size() == 1 && coarsePremix &&
                            coarseMinBlocks < ((int64_t)1 << 29);
-    const bool pathD = !nd.refSens && useCoarse && useTimeFft && ir->P > 64 && coarseParts <= kCoarseMaxP &&
+    const bool pathD = !nd.refSens && useCoarse && useTimeFft && ir->P > 64 && coarseParts <= (coarseLong ? kCoarseMaxParts : kCoarseMaxP) &&
                        (chunkBlocks >= coarseMinBlocks || manyShare);
     const bool pathA = !nd.refSens && !pathC && !pathD && (hasA[ir] || users[ir] >= 8);
     if (pathD) {
@@ -1076,15 +1077,20 @@ void Context::ensureCoarseSpectra(IrSpectra& ir) {
   if (!ir.taps) fail(GA_ERR_INVALID_OPERATION, "internal: impulse response without device taps");
   const int P = (int)((ir.tapsStride + kCoarseBlock - 1) / kCoarseBlock);
   ir.coarseP = P;
-  ir.coarseBytes = (size_t)ir.nch * P * kCoarseBins * sizeof(float2);
+  // more than kCoarseMaxP partitions: the sum runs in segments of kCoarseMaxP; the general kernel rounds the last segment up to its
+  // partition block of 4, so the stored rows are rounded up to whole segments -- the rows behind the response are zero rows
+  const int PS = P > kCoarseMaxP ? (P + kCoarseMaxP - 1) / kCoarseMaxP * kCoarseMaxP : P;
+  ir.coarseStride = PS;
+  ir.coarseBytes = (size_t)ir.nch * PS * kCoarseBins * sizeof(float2);
   ir.coarse = (float2*)dalloc(ir.coarseBytes);
+  if (PS != P) GA_HIP(hipMemsetAsync(ir.coarse, 0, ir.coarseBytes, stream));
   std::vector<CoarseXRow> rows(ir.nch);
   for (int c = 0; c < ir.nch; c++) {
     CoarseXRow& r = rows[c];
     r.hist = nullptr;
     r.in = ir.taps + (size_t)c * ir.tapsStride;
     r.nvalid = ir.tapsStride;
-    r.frame0 = c * P;
+    r.frame0 = c * PS;
     r.n_frames = P;
     r.u0 = 1;            // window p + 1 starts at partition p; its second half is forced to zero
     r.hist_len = 0;

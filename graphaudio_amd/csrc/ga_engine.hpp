@@ -112,11 +112,12 @@ struct IrSpectra {  // P zero-padded 256-point spectra per IR channel (Partition
   static int n2Index(int N2) { return N2 == 1024 ? 0 : N2 == 2048 ? 1 : 2; }
   size_t hBytes = 0, hspecBytes = 0;
   // formulation D: the scaled taps [nch][tapsStride] (kept for the coarse spectra, built on first use) and the packed
-  // 16,384-point spectra of the coarse partitions [nch][coarseP][kCoarseBins]
+  // 16,384-point spectra of the coarse partitions [nch][coarseStride][kCoarseBins]
   float* taps = nullptr;
   int64_t tapsStride = 0;
   size_t tapsBytes = 0;
   int coarseP = 0;
+  int coarseStride = 0;   // partitions per channel as STORED: coarseP, or (more than kCoarseMaxP partitions) rounded up to a multiple of kCoarseMaxP with zero rows
   float2* coarse = nullptr;
   size_t coarseBytes = 0;
   int64_t* devBytesRef = nullptr;   // the owning context's byte counter
@@ -710,6 +711,7 @@ struct Context {
                                    // stage saves P' - 1 windows per signal, the multiply-accumulate and inverse stages pay for the tail blocks -- 2.95 vs 2.97 ms at
                                    // 1024 voices per 10 s step, 0.50 vs 0.43 ms at 64 voices per 2.5 s call: off)
   bool coarseCarry = true;   // option "coarse_carry": the forward kernel writes the next chunk's history (0: always the copy kernel)
+  bool coarseLong = true;    // option "coarse_long": impulse responses of 131,073 .. 1,048,576 taps take formulation D (segmented partition sum); 0: A / B
   bool coarsePremix = true;  // option "coarse_premix": fused groups on ONE impulse response are summed in the time domain, in front of
                              // one set of transforms (0: every member is transformed, the spectra are summed -- coarse_sum_kernel)
   void ensureOverlapStream();

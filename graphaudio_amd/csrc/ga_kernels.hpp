@@ -133,7 +133,8 @@ void launch_tconv16(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblo
 
 // ---- convolver pipeline, formulation D: coarse partitions, consumer sum fused in the frequency domain (ga_coarse.hip) ----
 constexpr int kCoarseBlock = 8192;   // samples per coarse partition / output block
-constexpr int kCoarseMaxP = 16;      // partitions a job can slide over (impulse responses up to 131,072 taps)
+constexpr int kCoarseMaxP = 16;      // partitions a job can slide over in one sweep (131,072 taps); longer sums run in segments of this length
+constexpr int kCoarseMaxParts = 128; // partitions of the longest impulse response formulation D takes (1,048,576 taps: 8 segments)
 constexpr int kCoarseJobTerms = 32;   // terms (signals) whose products one multiply-accumulate job sums in registers
 // ... and one reduction job (coarse_sum_kernel: the terms share their impulse response): 8 waves x 9 (x 5) -- a 10 s chunk with its
 // carried tail is 59 + 8 output blocks
@@ -169,6 +170,9 @@ struct CoarseHandOver {    // a finished bus row on its way to page-locked host 
 };
 struct CoarseTerm {        // one (signal, impulse response) product feeding a job's accumulators
   int frame0;              // frame of window u = -(P - 1) of the signal
+  // jobs of more than kCoarseMaxP partitions (segmented sum): in the general kernel a term is a (signal, segment) pair, frame0 = frame of
+  // the window -(off + kCoarseMaxP - 1), h[] advanced by `off` partitions, pad_ = off + 256 x the segment's partitions; in the reduction
+  // kernel frame0 = frame of the window u = 0.  (Such frames may lie in front of the row: they are never fetched.)
   int pad_;
   const float2* h[16];     // per column: packed spectra [P][kCoarseBins] of the column's impulse-response channel
 };

@@ -208,10 +208,11 @@ struct CoarseStage {
   // launches: by column count (1, 2, 4) x (terms with their own impulse responses | one impulse response for all terms), and
   // by the group whose transforms complete the job's inputs.  Class index = 2 * column class + shared.
   static constexpr int kCwOf[4] = {1, 2, 4, 16};   // column classes of the multiply-accumulate launches
-  std::vector<CoarseJob> jobs[8][8];
-  int maxT[8] = {0, 0, 0, 0, 0, 0, 0, 0}, maxP[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int pbOf[8] = {4, 4, 4, 4, 4, 4, 4, 4};   // largest of 4, 2, 1 dividing every job's partition count (the sweep's register block)
-  double macBytes[8][8] = {}, macFlops[8][8] = {};
+  // Classes 8 .. 15: the same for jobs of more than kCoarseMaxP partitions (segmented sum: kernels of their own).
+  std::vector<CoarseJob> jobs[16][8];
+  int maxT[16] = {}, maxP[16] = {};
+  int pbOf[16] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4};   // largest of 4, 2, 1 dividing every job's partition count (the sweep's register block)
+  double macBytes[16][8] = {}, macFlops[16][8] = {};
   double pmFlops = 0, invFlops = 0;
   std::map<std::pair<int, int>, std::vector<int>> outRows;   // (leader, channel) -> Y rows to sum
   int yNext = 0;
@@ -363,7 +364,7 @@ void CoarseStage::buildRows() {
     NodeS& nd = *c.nodes[id];
     IrSpectra& ir = *nd.ir;
     const int P = ir.coarseP;
-    if (P < 1 || P > kCoarseMaxP) fail(GA_ERR_INVALID_OPERATION, "internal: coarse partition count out of range");
+    if (P < 1 || P > kCoarseMaxParts) fail(GA_ERR_INVALID_OPERATION, "internal: coarse partition count out of range");
     const int64_t hl = nd.dHistLen;
     GroupInfo& gi0 = groups[nd.dLeader >= 0 ? nd.dLeader : id];
     const bool carried = gi0.noHist;   // no windows in front of the chunk
@@ -537,12 +538,16 @@ void CoarseStage::buildJobs() {
       const int term0 = (int)terms.size();
       bool shared = true;
       int lastX = 0;
+      // more than kCoarseMaxP partitions: the sum runs in segments of kCoarseMaxP partitions inside the job (ga_coarse.hip,
+      // coarse_sum_seg_kernel / coarse_mac_seg_kernel); the accumulators stay in registers over all of them
+      const bool seg = k.P > kCoarseMaxP;
       for (size_t i = p0; i < p1; i++) {
         const Piece& pc = *pv[i];
         CoarseTerm t{};
         t.frame0 = pc.frame0 - (pc.u0 + (pc.P - 1));   // frame the window u = -(P - 1) would have (the kernels index from there)
+        if (seg) t.frame0 = pc.frame0 - pc.u0;         // segmented sum: the frame the window u = 0 would have
         for (int j = 0; j < 16; j++) t.h[j] = nullptr;
-        for (int j = 0; j < cw; j++) t.h[j] = pc.ir->coarse + (size_t)pc.irCh[j] * pc.P * kCoarseBins;
+        for (int j = 0; j < cw; j++) t.h[j] = pc.ir->coarse + (size_t)pc.irCh[j] * pc.ir->coarseStride * kCoarseBins;
         if (i > p0)
           for (int j = 0; j < cw; j++) shared = shared && (t.h[j] == terms[term0].h[j]);
         terms.push_back(t);
@@ -553,6 +558,8 @@ void CoarseStage::buildJobs() {
         for (size_t i = term0; i < terms.size(); i++)   // the matrix-core kernel addresses the columns' spectra from h[0]
           for (int j = 1; j < 16; j++) wideStrided = wideStrided && terms[i].h[j] == terms[i].h[0] + (size_t)j * k.P * kCoarseBins;
       }
+      if (seg && cw == 16) fail(GA_ERR_INVALID_OPERATION, "internal: 16-column piece with a segmented partition sum");
+      if (seg && !shared) terms.resize(term0);   // (the general kernel's terms are (signal, segment) pairs, listed per job below)
       const int grp = groupOf(lastX);
       const int yrow0 = yNext;
       yNext += cw;
@@ -571,7 +578,40 @@ void CoarseStage::buildJobs() {
         jb_.shared_h = shared ? 1 : 0;
         jb_.u_lo = gi.noHist ? 0 : -(k.P - 1);
         jb_.u_hi = gi.tail ? nT : nT - 1;
-        const int cj = 2 * ci + (shared ? 1 : 0);
+        const int cj = 2 * ci + (shared ? 1 : 0) + (seg ? 8 : 0);
+        if (seg) {
+          // per segment: the windows t - off - p the job's blocks reach, those of them that exist, the partitions multiplied
+          // (stage_bytes / stage_flops count what is executed: a segment's frames are fetched once per segment)
+          double xFrames = 0, parts = 0;
+          if (!shared) jb_.term0 = (int)terms.size();
+          int npairs = 0;
+          auto addSegment = [&](const Piece* pc, int off, bool force) {   // pc: the general kernel's (signal, segment) pair
+            const int np = pc ? std::min(kCoarseMaxP, (k.P - off + 3) / 4 * 4) : std::min(kCoarseMaxP, k.P - off);
+            const int wLo = std::max(jb_.u_lo, t0 - off - (kCoarseMaxP - 1)), wHi = std::min(jb_.u_hi, t0 + jb_.n_t - 1 - off);
+            if (!force && (wLo > wHi || t0 - off - (np - 1) > jb_.u_hi)) return;   // none of the segment's windows exists
+            xFrames += (double)std::max(0, wHi - wLo + 1) * (pc ? 1 : jb_.n_terms);
+            parts += np;
+            npairs++;
+            if (!pc) return;
+            CoarseTerm t{};
+            t.frame0 = pc->frame0 - pc->u0 - off - (kCoarseMaxP - 1);
+            t.pad_ = off + 256 * np;
+            for (int j = 0; j < 16; j++) t.h[j] = nullptr;
+            for (int j = 0; j < cw; j++) t.h[j] = pc->ir->coarse + ((size_t)pc->irCh[j] * pc->ir->coarseStride + off) * kCoarseBins;
+            terms.push_back(t);
+          };
+          for (size_t i = shared ? p1 - 1 : p0; i < p1; i++)
+            for (int off = 0; off < k.P; off += kCoarseMaxP) addSegment(shared ? nullptr : pv[i], off, false);
+          if (npairs == 0) addSegment(shared ? nullptr : pv[p0], 0, true);   // (a job of zero rows still writes its Y blocks)
+          if (!shared) jb_.n_terms = (int)terms.size() - jb_.term0;
+          jobs[cj][grp].push_back(jb_);
+          maxT[cj] = std::max(maxT[cj], jb_.n_t);
+          maxP[cj] = std::max(maxP[cj], k.P);
+          macBytes[cj][grp] += xFrames * kCoarseBins * 8.0 + (t0 == 0 ? (double)(shared ? 1 : (p1 - p0)) * k.P * cw * kCoarseBins * 8.0 : 0.0) +
+                               (double)cw * jb_.n_t * kCoarseBins * 8.0;
+          macFlops[cj][grp] += shared ? (xFrames * 2.0 + parts * jb_.n_t * cw * 8.0) * kCoarseBins : parts * jb_.n_t * cw * 8.0 * kCoarseBins;
+          continue;
+        }
         jobs[cj][grp].push_back(jb_);
         maxT[cj] = std::max(maxT[cj], jb_.n_t);
         maxP[cj] = std::max(maxP[cj], k.P);
@@ -668,9 +708,9 @@ void CoarseStage::enqueue() {
   const bool matrixCores = c.coarseMfma && wideStrided;
   std::vector<MacLaunch> macs;
   for (int g = 0; g < G; g++)
-    for (int i = 0; i < 8; i++) {
+    for (int i = 0; i < 16; i++) {
       if (jobs[i][g].empty()) continue;
-      macs.push_back(MacLaunch{ex.plan.putv(jobs[i][g]), (int)jobs[i][g].size(), kCwOf[i >> 1], maxT[i], maxP[i], pbOf[i], g, (i & 1) == 0,
+      macs.push_back(MacLaunch{ex.plan.putv(jobs[i][g]), (int)jobs[i][g].size(), kCwOf[(i & 7) >> 1], maxT[i], maxP[i], pbOf[i], g, (i & 1) == 0,
                                macBytes[i][g], macFlops[i][g]});
       c.stats.mac_launches += 1;
     }
@@ -855,7 +895,8 @@ void Context::chunkConvScratch(ChunkRun& r) {
       ensure(planes[3], yMax);
     }
     {  // formulation D: the stages of a chunk run one after the other on the stream and share the two arenas
-      std::map<int, std::pair<size_t, size_t>> perDepth;   // depth -> (X frames, Y frames upper bound)
+      std::map<int, std::pair<size_t, size_t>> perDepth;   // depth -> (X frames, Y rows upper bound)
+      std::map<int, int> tailDepth;                        // depth -> longest carried tail a group of the stage can have (coarse blocks)
       const int64_t nT = (n * kBlock + kCoarseBlock - 1) / kCoarseBlock;
       for (int id : topo) {
         NodeS& nd = *nodes[id];
@@ -863,12 +904,16 @@ void Context::chunkConvScratch(ChunkRun& r) {
         auto& pd = perDepth[nd.depth];
         pd.first += (size_t)nd.bInCh * (size_t)(nT + nd.ir->coarseP);   // (+ the window behind the chunk's last block: carried tails)
         // Y rows: one per slot unless fused; fused groups need (members / 32 + 1) x channels rows, never more than the slots
-        pd.second += (size_t)nd.bSlots * (size_t)(nT + kCoarseMaxP);
+        // Every Y row of a stage is nT + (the longest carried tail of the stage) frames long (CoarseStage::buildOutputs): ONE long group
+        // stretches the rows of every convolver at its depth, so the rows are counted per depth and multiplied by the depth's row length
+        pd.second += (size_t)nd.bSlots;
+        int& tp = tailDepth[nd.depth];
+        tp = std::max(tp, std::max(kCoarseMaxP, nd.ir->coarseP));
       }
       size_t xf = 0, yf = 0;
       for (auto& kv : perDepth) {
         xf = std::max(xf, kv.second.first);
-        yf = std::max(yf, kv.second.second);
+        yf = std::max(yf, kv.second.second * (size_t)(nT + tailDepth[kv.first]));
       }
       if (xf) {
         ensure(coarseX, xf * kCoarseBins * sizeof(float2));
