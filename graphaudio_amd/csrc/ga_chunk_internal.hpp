@@ -267,7 +267,7 @@ struct Sim {
           float nyq = c.sampleRate / 2.f;
           float f = n_.params[0].value;
           f = f < 1.f ? 1.f : (f > nyq ? nyq : f);
-          float q = std::max(0.001f, n_.params[1].value);
+          float q = max_ref(0.001f, n_.params[1].value);   // Math.Max (:124): a NaN Q stays NaN
           float gainDb = n_.params[2].value;
           // usedFreq/usedQ start every block at 1000 / 1.0 (_lastFrequency/_lastQ are never updated, :13-14,111-112)
           if (n_.coefDirty || std::fabs(f - 1000.f) > 0.001f || std::fabs(q - 1.0f) > 0.0001f) {

@@ -729,7 +729,7 @@ void Context::refOrderSensitivity(const std::vector<int>& topo) {
         const float nyq = sampleRate / 2.f;
         float f = nd.params[0].value;
         f = f < 1.f ? 1.f : (f > nyq ? nyq : f);
-        const float q = std::max(0.001f, nd.params[1].value);
+        const float q = max_ref(0.001f, nd.params[1].value);
         float o[5];
         biquadCoefficients(nd.filterType, (float)sampleRate, f, q, nd.params[2].value, o);
         s = biquadDeviation(o, 1) > convRefMinDeviation;

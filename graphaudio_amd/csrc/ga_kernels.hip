@@ -41,10 +41,6 @@ __device__ unsigned long long* ga_tl = nullptr;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Math.Clamp(v, min, max) in the reference's comparison order: a NaN passes through (fminf / fmaxf would return a bound) and a -0.0
-// stays -0.0.  Every clamp of a parameter value goes through it except krate_probe_kernel's (see there).
-__device__ __forceinline__ float clamp_ref(float v, float mn, float mx) { return v < mn ? mn : (v > mx ? mx : v); }
-
 // =====================================================================================================
 //  256-point real FFT on one wavefront (forward: RealFourierTransform.cs:62-88; inverse: :101-131), double precision.
 //  z[n] = x[2n] + i x[2n+1] (n < 128); lane l owns z[l] (slot 0) and z[l+64] (slot 1).  One in-lane radix-2 stage
@@ -2602,7 +2598,7 @@ __global__ __launch_bounds__(64) void biquad_dynamic_kernel(const BiquadDynJob* 
         float f = job->fcurve ? ldg1(job->fcurve + f0 + i) : job->fval;
         f = f < 1.f ? 1.f : (f > nyq ? nyq : f);
         float q = job->qcurve ? ldg1(job->qcurve + f0 + i) : job->qval;
-        q = q > 0.001f ? q : 0.001f;
+        q = max_ref(0.001f, q);   // Math.Max (:124): a NaN Q stays NaN -- no update unless the frequency moves, then NaN coefficients
         if (dirty || fabsf(f - usedFreq) > 0.001f || fabsf(q - usedQ) > 0.0001f) {   // usedGain == gainDb always (:113,126)
           biquad_update_coefficients(type, f, q, gainDb, sr, b0, b1, b2, a1, a2);
           usedFreq = f;

@@ -376,6 +376,12 @@ struct ParamJob {
   int64_t b0;         // first block (chunk relative)
   int64_t nblocks;
 };
+// Math.Clamp(v, min, max) in the reference's comparison order: a NaN passes through (fminf / fmaxf would return a bound) and a -0.0
+// stays -0.0.  Every clamp of a parameter value goes through it except krate_probe_kernel's (see there).
+__host__ __device__ __forceinline__ float clamp_ref(float v, float mn, float mx) { return v < mn ? mn : (v > mx ? mx : v); }
+// Math.Max(a, b): a NaN on either side is the result (fmaxf and std::max return the other operand or `a`).  The Q of a
+// BiQuadFilterNode goes through it (BiQuadFilterNode.cs:124), on the device and in the host's static-coefficient paths.
+__host__ __device__ __forceinline__ float max_ref(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
 // AudioParam.ComputeValueAtTime and helpers (AudioParam.cs:169-247), double precision, no contraction.  Host + device:
 // the device evaluates a-rate / k-rate curves; the host evaluates the k-rate playbackRate that steers source replay.
 __host__ __device__ inline float param_interp_linear(float v0, double t0, float v1, double t1, double t) {

@@ -520,6 +520,7 @@ void Context::planBiquad(NodePlanCtx& k) {
       BiquadDynState init{};
       init.b0 = nd.b0; init.b1 = nd.b1; init.b2 = nd.b2; init.a1 = nd.a1; init.a2 = nd.a2;
       init.dirty = nd.coefDirty ? 1 : 0;
+      nd.coefDirty = false;   // (while the state is on the device the host flag means: Type written since the state went there)
       GA_HIP(hipMemcpyAsync(nd.bqDyn, &init, 24, hipMemcpyHostToDevice, stream));
       GA_HIP(hipStreamSynchronize(stream));
       nd.coefOnDevice = true;

@@ -31,9 +31,11 @@
 #include <string>
 #include <vector>
 
-// The reference's MathF.Cos / Sin / Pow are the C runtime's single-precision functions: std::cos(float) etc. here.  A diagnostic
-// build (-DGAO_DOUBLE_TRIG, tools/fuzz_libm_class.py -- never the oracle the tests use) evaluates them in double and rounds once,
+// The reference's MathF.Cos / Sin / Pow are the C runtime's single-precision functions: std::cos(float) etc. here.  A second
+// build (-DGAO_DOUBLE_TRIG: libga_oracle_dtrig.so, tests/_oracle.py DtrigOracleContext) evaluates them in double and rounds once,
 // which is what the device does: a deviation between device and oracle that vanishes against that build is the last bit of libm.
+// The plain build stays THE oracle of every parity test and of the 1e-5 contract; the double-trig build is the second reference
+// that lets tests/test_gpu_param_edges.py hold the kernels of moving parameters bit for bit.
 #ifdef GAO_DOUBLE_TRIG
 static inline float gaoCos(float x) { return (float)std::cos((double)x); }
 static inline float gaoSin(float x) { return (float)std::sin((double)x); }
@@ -478,6 +480,11 @@ struct Param {
     if (v > mx) return mx;
     return v;
   }
+  static float maxf(float a, float b) {  // Math.Max(float, float): a NaN on either side is the result (std::max would return a)
+    if (a != a) return a;
+    if (b != b) return b;
+    return a > b ? a : b;
+  }
   void setValue(float v) {  // Value setter, :37-48: clamps and cancels all events
     value = clampf(v, minValue, maxValue);
     events.clear();
@@ -917,7 +924,7 @@ struct BiquadNode : Node {
       St& st = states[ch];
       for (int i = 0; i < kBlock; i++) {
         float f = Param::clampf(freqValues[i], 1.f, nyq);
-        float q = std::max(0.001f, qValues[i]);
+        float q = Param::maxf(0.001f, qValues[i]);  // Math.Max (:124): a NaN Q stays NaN
         if (coefficientsDirty || std::fabs(f - usedFreq) > 0.001f || std::fabs(q - usedQ) > 0.0001f ||
             std::fabs(gainDb - usedGain) > 0.001f) {
           updateCoefficients(f, q, gainDb);

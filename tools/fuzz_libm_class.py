@@ -4,19 +4,17 @@ The reference's MathF.Cos / Sin / Pow are the C runtime's single-precision funct
 coefficients of AUTOMATED biquads and the gains of panners in double and rounds once (ga_kernels.hip, biquad_update_coefficients) --
 the same float except where the true value lies within ~1e-9 of a rounding boundary.  A graph that quantises such a value (a delay
 time in whole samples, `pan != lastPan`) turns that last bit into a block that sounds different.  This tool renders the session
-three times: oracle, device, and a DIAGNOSTIC oracle built with -DGAO_DOUBLE_TRIG (the device's evaluation of those three functions,
-everything else the reference's): a deviation that vanishes against the third is that class and nothing else.
-    g++ -std=c++17 -O3 -mavx2 -ffp-contract=off -fno-fast-math -fPIC -DGAO_DOUBLE_TRIG -shared -o tools/variants/libga_oracle_dtrig.so oracle/ga_oracle.cpp
+three times: oracle, device, and the double-trig oracle (oracle/libga_oracle_dtrig.so, built by `make -C oracle` with
+-DGAO_DOUBLE_TRIG: the device's evaluation of those three functions, everything else the reference's): a deviation that vanishes
+against the third is that class and nothing else.
 """
-import ctypes as C, os, sys
+import sys
 import numpy as np
 sys.path.insert(0, ".")
 from graphaudio_amd import OfflineAudioContext
-from graphaudio_amd._capi import CApi
 from tests import _graphs as G
 import tests._fuzz as F
-from tests._oracle import OracleContext
-dtrig = CApi(C.CDLL(os.path.join("tools", "variants", "libga_oracle_dtrig.so")), "gao_")
+from tests._oracle import DtrigOracleContext, OracleContext
 def run(ctx, seed, graph):
     if not graph:
         return F.run_random_session(ctx, seed)[0]
@@ -36,7 +34,7 @@ for a in sys.argv[1:]:   # SEED: an edit session ; gSEED: a graph of test_random
     graph = a.startswith("g")
     seed = int(a[1:] if graph else a)
     ref = run(OracleContext(48000), seed, graph)
-    ref2 = run(OfflineAudioContext(48000, _api=dtrig), seed, graph)
+    ref2 = run(DtrigOracleContext(48000), seed, graph)
     h = OfflineAudioContext(48000)
     h.SetOption("max_chunk_blocks", 11)
     h.SetOption("coarse_min_blocks", 1)
