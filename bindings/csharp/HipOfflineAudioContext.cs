@@ -13,7 +13,7 @@
 // Destination (same traversal as GetAllNodes, AudioContextBase.cs:191-218), (3) replays what changed since the last
 // call through the flat C ABI -- O(graph delta) calls -- and (4) makes ONE ga_render call for the whole frame range.
 // Unsupported node types (anything but AudioBufferSourceNode, GainNode, BiQuadFilterNode, ConvolverNode, ChannelSplitterNode,
-// ChannelMergerNode, ConstantSourceNode, StereoPannerNode, OscillatorNode, DelayNode and the
+// ChannelMergerNode, ConstantSourceNode, StereoPannerNode, OscillatorNode, DelayNode, Hip.SpatialPannerNode and the
 // destination) make EnsureSynced throw NotSupportedException; callers fall back to the stock CPU context.
 // NOTE: not compiled in this repository's build image (no .NET); reviewed by reading.  The Python host in
 // graphaudio_amd/core.py drives the very same C ABI calls in the same order and IS tested.
@@ -42,6 +42,28 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
     /// <summary>Render of a voice-sharded graph (INTEGRATION.md section 4): this rank renders its share, the library sums the
     /// destination buses of all ranks with one RCCL reduce; <paramref name="output"/> is written on <paramref name="root"/> only.</summary>
     public void RenderReduce(float[][] output, int frameCount, int startIndex = 0, int root = 0) => RenderCore(output, frameCount, startIndex, root);
+
+    /// <summary>The listener of every SpatialPannerNode of this context: SteamAudioContext.SetListener (SteamAudioContext.cs:145-164)
+    /// -- normalise, right = forward x up, ahead = -forward -- stored in the twelve listener_* options of the native context.</summary>
+    public void SetListener(System.Numerics.Vector3 position, System.Numerics.Vector3 forward, System.Numerics.Vector3 up)
+    {
+        var f = System.Numerics.Vector3.Normalize(forward);
+        var u = System.Numerics.Vector3.Normalize(up);
+        var r = System.Numerics.Vector3.Cross(f, u);
+        SetListenerTransform(position, r, u, -f);
+    }
+
+    public void SetListenerTransform(System.Numerics.Vector3 origin, System.Numerics.Vector3 right, System.Numerics.Vector3 up, System.Numerics.Vector3 ahead)
+    {
+        var names = new[] { "origin", "right", "up", "ahead" };
+        var vecs = new[] { origin, right, up, ahead };
+        for (int v = 0; v < 4; v++)
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, $"listener_{names[v]}_x", vecs[v].X));
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, $"listener_{names[v]}_y", vecs[v].Y));
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, $"listener_{names[v]}_z", vecs[v].Z));
+        }
+    }
 
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
@@ -94,6 +116,7 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         public List<(AudioNode src, int outIdx)>[] Inputs = Array.Empty<List<(AudioNode, int)>>();
         public int[] ParamVersions = Array.Empty<int>();
         public object? Buffer;
+        public int HrirAzimuths = 1;   // SpatialPannerNode: the azimuth count last pushed to the native node
         public bool Started;
     }
 
@@ -124,6 +147,7 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
             StereoPannerNode => (GraphAudioHip.NodeStereoPanner, 0.0),
             OscillatorNode => (GraphAudioHip.NodeOscillator, 0.0),
             DelayNode d => (GraphAudioHip.NodeDelay, d.MaxDelayTimeInternal),
+            SpatialPannerNode => (GraphAudioHip.NodeSpatialPanner, 0.0),
             _ => throw new NotSupportedException($"{node.GetType().Name} is not on the HIP render path; use OfflineAudioContext"),
         };
         GraphAudioHip.Check(_native, GraphAudioHip.ga_node_create_ex(_native, type, arg, out int id));
@@ -193,6 +217,18 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
                 GraphAudioHip.Check(_native, GraphAudioHip.ga_convolver_set_enable_true_stereo(_native, id, cv.EnableTrueStereo ? 1 : 0));
                 GraphAudioHip.Check(_native, GraphAudioHip.ga_convolver_set_buffer(_native, id, cv.Buffer is null ? -1 : BufferId(cv.Buffer)));
                 sh.Buffer = cv.Buffer;
+                break;
+            case SpatialPannerNode sp:
+                GraphAudioHip.Check(_native, GraphAudioHip.ga_param_set_value(_native, id, GraphAudioHip.SpatialDistanceModel, (int)sp.DistanceModel));
+                if (!ReferenceEquals(sh.Buffer, sp.Hrir) || sh.HrirAzimuths != sp.HrirAzimuths)
+                {
+                    // azimuth count first: the set's channel count is checked against it (graphaudio_hip.h, ga_convolver_set_buffer)
+                    GraphAudioHip.Check(_native, GraphAudioHip.ga_convolver_set_buffer(_native, id, -1));
+                    GraphAudioHip.Check(_native, GraphAudioHip.ga_param_set_value(_native, id, GraphAudioHip.SpatialHrirAzimuths, sp.HrirAzimuths));
+                    GraphAudioHip.Check(_native, GraphAudioHip.ga_convolver_set_buffer(_native, id, sp.Hrir is null ? -1 : BufferId(sp.Hrir)));
+                    sh.Buffer = sp.Hrir;
+                    sh.HrirAzimuths = sp.HrirAzimuths;
+                }
                 break;
             case OscillatorNode osc:
                 GraphAudioHip.Check(_native, GraphAudioHip.ga_oscillator_set_type(_native, id, (int)osc.Type));
@@ -270,4 +306,48 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
         base.Dispose(disposing);
     }
+}
+
+/// <summary>
+/// The parameter surface of GraphAudio.SteamAudio's SpatialPannerNode (SpatialPannerNode.cs:17-47,94-114) without its Steam Audio
+/// dependency: a node of this type exists to be rendered by HipOfflineAudioContext, which runs the binaural stage on the HRIR set
+/// assigned here (DESIGN.md "SpatialPannerNode").  A Kit Sound that targets the HIP path creates this node instead (INTEGRATION.md).
+/// </summary>
+public sealed class SpatialPannerNode : AudioNode
+{
+    public enum DistanceModelType { Linear, Inverse, Exponential }
+
+    // (name, default, min, max) in the native parameter order; all k-rate
+    private static readonly (string name, float def, float min, float max)[] Table =
+    {
+        ("positionX", 0f, float.MinValue, float.MaxValue), ("positionY", 0f, float.MinValue, float.MaxValue), ("positionZ", 0f, float.MinValue, float.MaxValue),
+        ("orientationX", 1f, -1f, 1f), ("orientationY", 0f, -1f, 1f), ("orientationZ", 0f, -1f, 1f),
+        ("refDistance", 1f, 0f, float.MaxValue), ("maxDistance", 10000f, 0f, float.MaxValue), ("rolloffFactor", 1f, 0f, float.MaxValue),
+        ("coneInnerAngle", 360f, 0f, 360f), ("coneOuterAngle", 360f, 0f, 360f), ("coneOuterGain", 0f, 0f, 1f),
+        ("spatialBlend", 1f, 0f, 1f), ("occlusion", 0f, 0f, 1f),
+        ("transmissionLow", 0f, 0f, 1f), ("transmissionMid", 0f, 0f, 1f), ("transmissionHigh", 0f, 0f, 1f),
+    };
+    private readonly AudioParam[] _p = new AudioParam[Table.Length];
+
+    public AudioParam PositionX => _p[0]; public AudioParam PositionY => _p[1]; public AudioParam PositionZ => _p[2];
+    public AudioParam OrientationX => _p[3]; public AudioParam OrientationY => _p[4]; public AudioParam OrientationZ => _p[5];
+    public AudioParam RefDistance => _p[6]; public AudioParam MaxDistance => _p[7]; public AudioParam RolloffFactor => _p[8];
+    public AudioParam ConeInnerAngle => _p[9]; public AudioParam ConeOuterAngle => _p[10]; public AudioParam ConeOuterGain => _p[11];
+    public AudioParam SpatialBlend => _p[12]; public AudioParam Occlusion => _p[13];
+    public AudioParam TransmissionLow => _p[14]; public AudioParam TransmissionMid => _p[15]; public AudioParam TransmissionHigh => _p[16];
+
+    public DistanceModelType DistanceModel { get; set; } = DistanceModelType.Inverse;
+    /// <summary>2 * D channels x T frames (T at most 512): channel 2d = left ear, 2d + 1 = right ear of direction d = j * HrirAzimuths + i.</summary>
+    public PlayableAudioBuffer? Hrir { get; set; }
+    public int HrirAzimuths { get; set; } = 1;
+
+    public SpatialPannerNode(HipOfflineAudioContext context) : base(context, inputCount: 1, outputCount: 1, "SpatialPanner")
+    {
+        for (int i = 0; i < Table.Length; i++) _p[i] = CreateAudioParam(Table[i].name, Table[i].def, Table[i].min, Table[i].max, AutomationRate.KRate);
+        Inputs[0].SetChannelCount(2);
+        Inputs[0].SetChannelCountMode(ChannelCountMode.ClampedMax);
+        Inputs[0].SetChannelInterpretation(ChannelInterpretation.Speakers);
+    }
+
+    protected override void Process() => throw new NotSupportedException("SpatialPannerNode (HIP) is rendered by HipOfflineAudioContext only");
 }

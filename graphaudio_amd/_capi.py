@@ -103,6 +103,14 @@ class Stats(C.Structure):
         return d
 
 
+# GA_NODE_SPATIAL_PANNER and its pseudo-parameter indices (include/graphaudio_hip.h; no entry point of its own: the node goes through
+# node_create, param_*, convolver_set_buffer and set_option)
+NODE_SPATIAL_PANNER = 12
+SPATIAL_PARAM_COUNT = 17
+SPATIAL_DISTANCE_MODEL = 17
+SPATIAL_HRIR_AZIMUTHS = 18
+LISTENER_OPTIONS = tuple(f"listener_{v}_{a}" for v in ("origin", "right", "up", "ahead") for a in "xyz")
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 

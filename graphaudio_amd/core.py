@@ -60,10 +60,12 @@ class AutomationRate(enum.IntEnum):  # AudioParam.cs:381-392
 class PlayableAudioBuffer:
     """Immutable planar sample storage (PlayableAudioBuffer.cs:11-175).  Uploaded to a context on first use."""
 
+    _max_channels = 32
+
     def __init__(self, channels: Sequence[np.ndarray], sampleRate: int):
         if len(channels) == 0:
             raise ArgumentException("Channel data cannot be or empty")
-        if len(channels) > 32:
+        if len(channels) > self._max_channels:
             raise ArgumentOutOfRangeException("Channel count must be between 1 and 32")
         if sampleRate <= 0:
             raise ArgumentOutOfRangeException("Sample rate must be positive")
@@ -121,6 +123,21 @@ class PlayableAudioBuffer:
                     ctx._api.buffer_release(ctx._h, bid)
         except Exception:  # interpreter shutdown
             pass
+
+
+class HrirSet(PlayableAudioBuffer):
+    """A PlayableAudioBuffer that holds an HRIR set for SpatialPannerNode: 2 * D channels x T frames (1 <= T <= 512), channel 2d the
+    left ear and 2d + 1 the right ear of direction d = j * A + i (DESIGN.md "SpatialPannerNode").  Wider than audio: up to 4096
+    channels; the native library refuses such a buffer wherever it would be played or used as an impulse response."""
+    _max_channels = 4096
+
+    @staticmethod
+    def FromArray(hrir, sampleRate: int) -> "HrirSet":
+        """hrir[d][ear][k]: D directions x 2 ears x T taps."""
+        a = np.asarray(hrir, dtype=np.float32)
+        if a.ndim != 3 or a.shape[1] != 2:
+            raise ArgumentException("hrir must have shape [directions][2][taps]")
+        return HrirSet(list(a.reshape(a.shape[0] * 2, a.shape[2])), sampleRate)
 
 
 class AudioParam:
@@ -458,6 +475,68 @@ class StereoPannerNode(AudioNode):  # Nodes/StereoPannerNode.cs:9-163
         self.Pan = self._param("pan", 0.0, -1.0, 1.0, AutomationRate.ARate)
 
 
+class DistanceModelType(enum.IntEnum):  # SpatialPannerNode.cs:42-47
+    Linear = 0
+    Inverse = 1
+    Exponential = 2
+
+
+class SpatialPannerNode(AudioNode):
+    """SpatialPannerNode (GraphAudio.SteamAudio/Nodes/SpatialPannerNode.cs:10-305): the reference's parameter surface and
+    geometry; the binaural stage runs on a caller-supplied HRIR set (``Hrir`` / ``HrirAzimuths``, or the context's
+    ``SetHrir``) instead of Steam Audio's built-in HRTF -- DESIGN.md "SpatialPannerNode"."""
+    _node_type = _capi.NODE_SPATIAL_PANNER
+    _FMAX = float(np.finfo(np.float32).max)
+    # (name, default, min, max), all k-rate: SpatialPannerNode.cs:94-110 (float.MinValue is -float.MaxValue)
+    PARAMS = (("positionX", 0.0, -_FMAX, _FMAX), ("positionY", 0.0, -_FMAX, _FMAX), ("positionZ", 0.0, -_FMAX, _FMAX),
+              ("orientationX", 1.0, -1.0, 1.0), ("orientationY", 0.0, -1.0, 1.0), ("orientationZ", 0.0, -1.0, 1.0),
+              ("refDistance", 1.0, 0.0, _FMAX), ("maxDistance", 10000.0, 0.0, _FMAX), ("rolloffFactor", 1.0, 0.0, _FMAX),
+              ("coneInnerAngle", 360.0, 0.0, 360.0), ("coneOuterAngle", 360.0, 0.0, 360.0), ("coneOuterGain", 0.0, 0.0, 1.0),
+              ("spatialBlend", 1.0, 0.0, 1.0), ("occlusion", 0.0, 0.0, 1.0), ("transmissionLow", 0.0, 0.0, 1.0),
+              ("transmissionMid", 0.0, 0.0, 1.0), ("transmissionHigh", 0.0, 0.0, 1.0))
+
+    def __init__(self, context):
+        super().__init__(context, "SpatialPanner")
+        for name, default, mn, mx in self.PARAMS:   # PositionX .. TransmissionHigh, in the native parameter order
+            setattr(self, name[0].upper() + name[1:], self._param(name, default, mn, mx, AutomationRate.KRate))
+        self._distance_model = DistanceModelType.Inverse
+        self._hrir: Optional[PlayableAudioBuffer] = None
+        self._hrir_azimuths = 1
+        ctx_set = getattr(context, "_hrir", None)   # the reference holds one HRTF per context (SteamAudioContext.GetHrtf, :52)
+        if ctx_set is not None:
+            self.HrirAzimuths = ctx_set[1]
+            self.Hrir = ctx_set[0]
+
+    @property
+    def DistanceModel(self) -> DistanceModelType:  # :36-40
+        return self._distance_model
+
+    @DistanceModel.setter
+    def DistanceModel(self, value: DistanceModelType):
+        self.Context._call("param_set_value", self._id, _capi.SPATIAL_DISTANCE_MODEL, float(int(value)))
+        self._distance_model = DistanceModelType(int(value))
+
+    @property
+    def HrirAzimuths(self) -> int:
+        return self._hrir_azimuths
+
+    @HrirAzimuths.setter
+    def HrirAzimuths(self, value: int):
+        self.Context._call("param_set_value", self._id, _capi.SPATIAL_HRIR_AZIMUTHS, float(int(value)))
+        self._hrir_azimuths = int(value)
+
+    @property
+    def Hrir(self) -> Optional[PlayableAudioBuffer]:
+        return self._hrir
+
+    @Hrir.setter
+    def Hrir(self, value: Optional[PlayableAudioBuffer]):
+        """The HRIR set: 2 * D channels (D a multiple of HrirAzimuths -- set that first) x T <= 512 frames at the context's rate."""
+        bid = -1 if value is None else value._native_id(self.Context)
+        self.Context._call("convolver_set_buffer", self._id, bid)
+        self._hrir = value
+
+
 class OscillatorNode(_ScheduledSource):  # Nodes/OscillatorNode.cs:12-214
     _node_type = 9
 
@@ -560,6 +639,34 @@ class AudioContextBase:
             self._async = bool(value)   # asynchronous renders: output arrays are kept alive until Synchronize()
             if not value:
                 self._pending_outputs = []
+
+    # ---- listener and HRTF of the context (GraphAudio.SteamAudio/SteamAudioContext.cs) ----
+    def SetListenerTransform(self, origin, right, up, ahead):  # SteamAudioContext.cs:136-140
+        """The listener's coordinate space as SpatialPannerNode reads it (identity: right +x, up +y, ahead -z, origin 0)."""
+        vals = [np.float32(c) for v in (origin, right, up, ahead) for c in v]
+        if len(vals) != 12:
+            raise ArgumentException("origin, right, up and ahead must have three components each")
+        for key, v in zip(_capi.LISTENER_OPTIONS, vals):
+            self._call("set_option", key.encode(), float(v))
+
+    def SetListener(self, position, forward, up):  # SteamAudioContext.cs:145-164, float32 like System.Numerics
+        f32 = np.float32
+
+        def normalize(v):
+            x, y, z = (f32(c) for c in v)
+            ln = np.sqrt(f32(f32(x * x + y * y) + z * z))
+            return (f32(x / ln), f32(y / ln), f32(z / ln))
+
+        with np.errstate(all="ignore"):
+            fw, u = normalize(forward), normalize(up)
+            right = (f32(f32(fw[1] * u[2]) - f32(fw[2] * u[1])), f32(f32(fw[2] * u[0]) - f32(fw[0] * u[2])),
+                     f32(f32(fw[0] * u[1]) - f32(fw[1] * u[0])))
+            ahead = (f32(-fw[0]), f32(-fw[1]), f32(-fw[2]))
+        self.SetListenerTransform(tuple(f32(c) for c in position), right, u, ahead)
+
+    def SetHrir(self, buffer: Optional[PlayableAudioBuffer], azimuths: int = 1):
+        """The HRIR set SpatialPannerNodes created from now on start with (one HRTF per context in the reference)."""
+        self._hrir = None if buffer is None else (buffer, int(azimuths))
 
     def GetStats(self) -> dict:
         st = _capi.Stats()

@@ -404,6 +404,15 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "coarse_min_blocks") c.coarseMinBlocks = std::max<int64_t>(1, (int64_t)value);
     else if (k == "debug_tconv_n2") c.debugTconvN2 = (int)value;   // tests only: plan the block-axis FFT with this (possibly unsupported) length
     else if (k == "mem_budget_fraction") c.memBudgetFraction = std::min(0.95, std::max(0.05, value));
+    else if (k.rfind("listener_", 0) == 0) {   // IPL.CoordinateSpace3 of SteamAudioContext.cs:45-54: origin, right, up, ahead
+      static const char* const vec[4] = {"origin", "right", "up", "ahead"};
+      int slot = -1;
+      for (int v = 0; v < 4 && slot < 0; v++)
+        for (int a = 0; a < 3 && slot < 0; a++)
+          if (k == std::string("listener_") + vec[v] + "_" + "xyz"[a]) slot = v * 3 + a;
+      if (slot < 0) fail(GA_ERR_INVALID_ARGUMENT, "unknown option " + k);
+      c.listener[slot] = (float)value;
+    }
     else fail(GA_ERR_INVALID_ARGUMENT, "unknown option " + k);
   });
 }
@@ -436,7 +445,8 @@ int ga_context_set_stream(ga_context* ctx, void* hip_stream) {
 int ga_buffer_create(ga_context* ctx, const float* const* planar, int channels, int64_t frames, int sample_rate, int* out_id) {
   return guard(ctx, [&](Context& c) {
     if (!planar || !out_id) fail(GA_ERR_INVALID_ARGUMENT, "null pointer");
-    if (channels < 1 || channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
+    // (audio is 1 .. 32 channels: checked where a buffer is played or becomes an impulse response; an HRIR set is wider)
+    if (channels < 1 || channels > 4096) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 4096 (1 .. 32 for audio, more for an HRIR set)");
     if (frames < 0) fail(GA_ERR_OUT_OF_RANGE, "Length must be non-negative");
     if (sample_rate <= 0) fail(GA_ERR_OUT_OF_RANGE, "Sample rate must be positive");
     auto b = std::make_unique<PlayBuf>();
@@ -541,6 +551,26 @@ int ga_node_create_ex(ga_context* ctx, int node_type, double arg, int* out_id) {
         n->outputs.resize(1);
         n->params.push_back(makeParam(1.f, 0.001f, 1000.f, false));
         break;
+      case GA_NODE_SPATIAL_PANNER: {   // SpatialPannerNode.cs:94-114 (float.MinValue is -float.MaxValue)
+        n->inputs.resize(1);
+        n->outputs.resize(1);
+        n->inputs[0].channelCount = 2;
+        n->inputs[0].mode = GA_COUNT_MODE_CLAMPED_MAX;
+        n->inputs[0].interp = GA_INTERP_SPEAKERS;
+        for (int i = 0; i < 3; i++) n->params.push_back(makeParam(0.f, -FMAX, FMAX, false));   // positionX/Y/Z
+        n->params.push_back(makeParam(1.f, -1.f, 1.f, false));                                 // orientationX
+        n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationY
+        n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationZ
+        n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // refDistance
+        n->params.push_back(makeParam(10000.f, 0.f, FMAX, false));                             // maxDistance
+        n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // rolloffFactor
+        n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneInnerAngle
+        n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneOuterAngle
+        n->params.push_back(makeParam(0.f, 0.f, 1.f, false));                                  // coneOuterGain
+        n->params.push_back(makeParam(1.f, 0.f, 1.f, false));                                  // spatialBlend
+        for (int i = 0; i < 4; i++) n->params.push_back(makeParam(0.f, 0.f, 1.f, false));      // occlusion, transmissionLow/Mid/High
+        break;
+      }
       default: fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");
     }
     *out_id = n->id;
@@ -667,6 +697,22 @@ int ga_destination_output_channels(ga_context* ctx) {
 
 int ga_param_set_value(ga_context* ctx, int node, int param, float value) {
   return guard(ctx, [&](Context& c) {  // Value setter: clamp + cancel all events (AudioParam.cs:37-48)
+    if (NodeS* sn = c.node(node); sn->type == GA_NODE_SPATIAL_PANNER && param >= GA_SPATIAL_PARAM_COUNT) {
+      const int iv = (int)value;
+      if (param == GA_SPATIAL_DISTANCE_MODEL) {   // SpatialPannerNode.DistanceModel (:36-40): a plain property
+        if ((float)iv != value || iv < GA_DISTANCE_LINEAR || iv > GA_DISTANCE_EXPONENTIAL) fail(GA_ERR_INVALID_ARGUMENT, "distanceModel");
+        sn->distanceModel = iv;
+      } else if (param == GA_SPATIAL_HRIR_AZIMUTHS) {
+        if ((float)iv != value || iv < 1) fail(GA_ERR_INVALID_ARGUMENT, "hrirAzimuths must be an integer >= 1");
+        if (const PlayBuf* hb = sn->hrirRequested >= 0 ? c.buffer(sn->hrirRequested) : nullptr; hb && hb->channels % (2 * iv) != 0)
+          fail(GA_ERR_INVALID_OPERATION, "HRIR set channel count must be a multiple of 2 * hrirAzimuths.");
+        if (sn->hrirAzimuths != iv) sn->spPrev.valid = false;   // (the grid the previous block's indices were taken from is gone)
+        sn->hrirAzimuths = iv;
+      } else {
+        fail(GA_ERR_INVALID_ARGUMENT, "bad param index");
+      }
+      return;
+    }
     ParamS* p = c.param(node, param);
     p->value = clampf(value, p->minv, p->maxv);
     p->events.clear();
@@ -675,6 +721,10 @@ int ga_param_set_value(ga_context* ctx, int node, int param, float value) {
 int ga_param_get_value(ga_context* ctx, int node, int param, float* out) {
   return guardRO(ctx, [&](Context& c) {
     if (!out) fail(GA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (NodeS* sn = c.node(node); sn->type == GA_NODE_SPATIAL_PANNER && (param == GA_SPATIAL_DISTANCE_MODEL || param == GA_SPATIAL_HRIR_AZIMUTHS)) {
+      *out = (float)(param == GA_SPATIAL_DISTANCE_MODEL ? sn->distanceModel : sn->hrirAzimuths);
+      return;
+    }
     *out = c.param(node, param)->value;
   });
 }
@@ -735,7 +785,7 @@ int ga_param_cancel_scheduled_values(ga_context* ctx, int node, int param, doubl
 int ga_source_set_buffer(ga_context* ctx, int node, int buffer_id) {
   return guard(ctx, [&](Context& c) {
     NodeS* n = typed(c, node, GA_NODE_BUFFER_SOURCE);
-    if (buffer_id >= 0) c.buffer(buffer_id);
+    if (buffer_id >= 0 && c.buffer(buffer_id)->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
     n->bufId = buffer_id < 0 ? -1 : buffer_id;
   });
 }
@@ -830,8 +880,41 @@ int ga_convolver_set_enable_true_stereo(ga_context* ctx, int node, int enable) {
 }
 int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
   return guard(ctx, [&](Context& c) {  // ConvolverNode.Buffer setter, ConvolverNode.cs:25-79
-    NodeS* n = typed(c, node, GA_NODE_CONVOLVER);
     Context* cp = &c;
+    if (c.node(node)->type == GA_NODE_SPATIAL_PANNER) {   // the node's HRIR set (graphaudio_hip.h): checked now, applied with the queued commands
+      NodeS* sn = c.node(node);
+      if (buffer_id < 0) {
+        sn->hrirRequested = -1;
+        c.post([cp, node]() {
+          cp->nodes[node]->irBuf = -1;
+          cp->nodes[node]->spPrev.valid = false;   // (indices into the set that is gone: the next processed block does not fade)
+          cp->graphVersion++;
+        });
+        return;
+      }
+      PlayBuf* b = c.buffer(buffer_id);
+      if (b->sampleRate != c.sampleRate) fail(GA_ERR_INVALID_OPERATION, "HRIR set sample rate must match the audio context sample rate.");
+      if (b->length < 1 || b->length > kSpatialMaxTaps) fail(GA_ERR_INVALID_OPERATION, "HRIR set length must be between 1 and 512 frames.");
+      if ((b->channels & 1) || b->channels % (2 * std::max(sn->hrirAzimuths, 1)) != 0)
+        fail(GA_ERR_INVALID_OPERATION, "HRIR set channel count must be even and a multiple of 2 * hrirAzimuths.");
+      double sumMax = 1.0;   // max(1, max over directions and ears of sum |h|): what sum |F| + |D| cannot exceed
+      for (const auto& ch : b->host) {
+        double sum = 0.0;
+        for (float v : ch) sum += std::fabs((double)v);
+        sumMax = std::max(sumMax, sum);
+      }
+      const float bound = (float)sumMax;
+      sn->hrirRequested = buffer_id;
+      c.post([cp, node, buffer_id, bound]() {
+        NodeS& nd = *cp->nodes[node];
+        nd.irBuf = buffer_id;
+        nd.spGainBound = bound;
+        nd.spPrev.valid = false;   // the previous block's indices belong to the previous set: the next processed block uses its own filters alone
+        cp->graphVersion++;
+      });
+      return;
+    }
+    NodeS* n = typed(c, node, GA_NODE_CONVOLVER);
     // `if (_buffer == value) return;` (:30) compares with the buffer of the last EXECUTED swap: a swap that is still
     // queued does not count, so A -> B -> A between two blocks ends on B
     if (n->irBuf == (buffer_id < 0 ? -1 : buffer_id)) {
@@ -851,6 +934,7 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
       return;
     }
     PlayBuf* b = c.buffer(buffer_id);
+    if (b->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
     if (b->sampleRate != c.sampleRate)
       fail(GA_ERR_INVALID_OPERATION, "Impulse response buffer sample rate must match the audio context sample rate.");
     // spectra are built eagerly with the CURRENT Normalize flag (:51-56); the swap is posted (:58-77)
@@ -896,6 +980,7 @@ int ga_stream_queue_buffer(ga_context* ctx, int node, int buffer_id) {
     NodeS* n = typed(c, node, GA_NODE_STREAM_SOURCE);
     PlayBuf* b = c.buffer(buffer_id);
     if (b->channels < 1 || b->length < 1) fail(GA_ERR_INVALID_ARGUMENT, "Buffer must be initialized");
+    if (b->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
     if (c.inRender) fail(GA_ERR_INVALID_OPERATION, "QueueBuffer during a render");
     n->stQueued.push_back(buffer_id);
   });

@@ -154,6 +154,7 @@ void Context::chunkTopology(ChunkRun& r) {
               break;
             case GA_NODE_CONVOLVER: bound *= mn.normalize ? 2.0 : 1e9; break;   // (normalised responses: broadband gain well below 1, peaks unknown)
             case GA_NODE_STEREO_PANNER: bound *= 2.0; break;                    // (oL = inL + inR * gainL)
+            case GA_NODE_SPATIAL_PANNER: bound *= (double)mn.spGainBound; break;   // (sum |F| + |D| <= max(1, sum |h|): g <= 1, the weights sum to 1)
             default: break;
           }
           if (m == id) break;
@@ -261,7 +262,7 @@ void Context::chunkTopology(ChunkRun& r) {
   if (topoHasCycles) r.n = std::min<int64_t>(r.n, cycleBlocks);
   if (topoStatsVersion != graphVersion || topoStatsSize != topo.size()) {   // (cached with the order: a sweep over 28,672 node records is 0.5 ms)
     topoMaxDepth = topoMaxLevel = 0;
-    topoHasTimeNodes = topoHasConvolvers = topoHasOscillators = topoHasStreams = false;
+    topoHasTimeNodes = topoHasConvolvers = topoHasOscillators = topoHasStreams = topoHasSpatial = false;
     for (int id : topo) {
       const NodeS& nd = *nodes[id];
       topoMaxDepth = std::max(topoMaxDepth, nd.depth);
@@ -270,6 +271,7 @@ void Context::chunkTopology(ChunkRun& r) {
       if (nd.type == GA_NODE_STREAM_SOURCE) topoHasStreams = true;
       if (nd.type == GA_NODE_CONVOLVER) topoHasConvolvers = true;   // (with or without an impulse response: Buffer setters run in drain())
       if (nd.type == GA_NODE_OSCILLATOR) topoHasOscillators = true;
+      if (nd.type == GA_NODE_SPATIAL_PANNER) topoHasSpatial = true;
     }
     topoStatsVersion = graphVersion;
     topoStatsSize = topo.size();
@@ -337,6 +339,30 @@ void Context::chunkTopology(ChunkRun& r) {
     if (coneLoop)
       for (const auto& e : topoRefEntry)
         if (rateCone[e.first] && (e.second < 0 || !rateCone[e.second])) r.coneRoots.push_back(e.first);
+  }
+  // ---- SpatialPannerNode: what the device path does not render is refused here, while nothing has moved ----
+  if (topoHasSpatial) {
+    const double increment = (double)kBlock / sampleRate;
+    for (int id : topo) {
+      const NodeS& nd = *nodes[id];
+      if (nd.type != GA_NODE_SPATIAL_PANNER) continue;
+      const std::string who = "SpatialPannerNode " + std::to_string(id) + ": ";
+      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++)
+        if (!nd.params[p].modulation.empty())
+          fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to parameter " + std::to_string(p) + " (signals on the node's parameters are not on the device path)");
+      const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+      if (!hb) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
+      if ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps)
+        fail(GA_ERR_UNSUPPORTED, who + "the HRIR set does not fit hrirAzimuths (channels must be a multiple of 2 * hrirAzimuths, 1 .. 512 frames)");
+      const ParamS& oc = nd.params[13];
+      bool occluded = oc.events.empty() ? oc.value > 0.0f : false;
+      if (!oc.events.empty()) {
+        double t = currentTime;   // the accumulated block clock (AudioContextBase.cs:78-79), as chunkSimulate builds it
+        for (int64_t b = 0; b < r.n && !occluded; b++, t += increment) occluded = param_value_at(oc.events.data(), (int)oc.events.size(), oc.value, t) > 0.0f;
+      }
+      if (occluded)
+        fail(GA_ERR_UNSUPPORTED, who + "occlusion > 0 (Steam Audio's occlusion / three-band transmission filters are not known here)");
+    }
   }
   // automated runs that ended hand their state back to the host: only nodes whose state went to the device are looked at
   // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, NodeS::bqDynSeq / panDynSeq, not a flag to reset)
@@ -687,6 +713,7 @@ void Context::chunkExecute(ChunkRun& r) {
   }
   // ---- upload tables, run ----
   ex.trajOffFinal = ex.plan.putv(ex.traj);
+  ex.spatialJobsOff = ex.plan.putv(ex.spatialJobs);
   size_t tbytes = ex.plan.host.size();
   const int slot = asyncMode ? (int)(chunkSeq & 1) : 0;   // async: the other buffer may still be waiting for its upload
   void*& thost = slot ? tablesHostB : tablesHost;

@@ -369,6 +369,16 @@ struct Sim {
         }
         break;
       }
+      case GA_NODE_SPATIAL_PANNER: {  // SpatialPannerNode.cs:117-261 over SteamAudioNodeBase.cs:61-70
+        n_.outputs[0].bufCh = 2;
+        n_.outputs[0].silent = ns.ins[0].silent;
+        if (!ns.ins[0].silent && !ns.ins[0].zero) n_.everFed = true;
+        n_.outputs[0].zero = ns.ins[0].zero && !n_.everFed;   // zero input AND zero history
+        ns.panMode = ns.ins[0].bufCh == 1 ? 1 : 2;   // mono / stereo input (a change is a new segment: hashSeg)
+        // the per-block descriptors (geometry, HRIR selection, fade flag) do not cut segments: they are made per block where the
+        // node is planned (Context::planSpatialPanner), from the parameters' timelines and the descriptor of the previous block
+        break;
+      }
       case GA_NODE_DELAY: {  // DelayNode.cs:43-100
         const InSeg& in = ns.ins[0];
         const int ch = in.bufCh;
@@ -560,6 +570,10 @@ struct Exec {
   std::vector<PanJob> panJobs;
   std::vector<DelayJob> delayJobs;
   std::vector<PanDynJob> panDynJobs;
+  std::vector<SpatialJob> spatialJobs;     // one per spatial node of the chunk (all levels: SpatialWork::job indexes it) ...
+  std::vector<SpatialWork> spatialWorks;   // ... and the workgroups of the level being planned
+  size_t spatialJobsOff = 0;               // where the job table ends up (put when the chunk's tables are complete: chunkExecute)
+  double spatialFma = 0;                   // fused multiply-adds of the level's workgroups
   std::vector<ParamModJob> pmodJobs;
   std::vector<ResampleBlock> traj;  // per-chunk trajectory table (all rates + custom tail blocks)
   bool mixAligned = true;
@@ -943,6 +957,17 @@ struct Exec {
       int nj = (int)panDynJobs.size();
       hipStream_t st = c.stream;
       plan.add(LK_OTHER, [=](uint8_t* base) { launch_stereo_panner_dynamic(st, (const PanDynJob*)(base + off), nj); });
+    }
+    if (!spatialWorks.empty()) {   // all spatial panners of the level: one launch
+      size_t off = plan.putv(spatialWorks);
+      int nw = (int)spatialWorks.size();
+      hipStream_t st = c.stream;
+      c.noteKernel(LK_OTHER, "spatial_panner_kernel");
+      plan.add(LK_OTHER, [this, st, off, nw](uint8_t* base) {
+        launch_spatial_panner(st, (const SpatialWork*)(base + off), nw, (const SpatialJob*)(base + spatialJobsOff), base);
+      }, 0.0, 2.0 * spatialFma);
+      spatialWorks.clear();
+      spatialFma = 0;
     }
     if (!delayJobs.empty()) {   // after the mix jobs of this level, which append the input to the delay lines
       size_t off = plan.putv(delayJobs);

@@ -239,6 +239,8 @@ Context::~Context() {
     if (np && np->delayLine) (void)hipFree(np->delayLine);
     if (np && np->oscPhase) (void)hipFree(np->oscPhase);
     if (np && np->panDev) (void)hipFree(np->panDev);
+    if (np && np->spHist[0]) (void)hipFree(np->spHist[0]);
+    if (np && np->spHist[1]) (void)hipFree(np->spHist[1]);
   }
   for (auto& kv : tw16) (void)hipFree(kv.second);
   if (rateModDev) (void)hipFree(rateModDev);
@@ -559,6 +561,17 @@ void Context::doDispose(int id) {
     dfree(n.staleNext, (size_t)n.staleRows * kBlock * sizeof(float));
     n.staleBuf = n.staleNext = nullptr;
     n.staleRows = 0;
+  }
+  if (n.type == GA_NODE_SPATIAL_PANNER) {   // the carried input history goes with the node, the HRIR set is let go
+    if (n.spHist[0]) {
+      if (stream) (void)hipStreamSynchronize(stream);
+      for (float*& h : n.spHist) {
+        dfree(h, kSpatialMaxTaps * sizeof(float));
+        h = nullptr;
+      }
+    }
+    n.irBuf = -1;
+    n.hrirRequested = -1;
   }
   if (n.type == GA_NODE_BUFFER_SOURCE) n.bufId = -1;  // AudioBufferSourceNode.cs:412
   if (n.type == GA_NODE_STREAM_SOURCE && n.stState != GA_STREAM_STOPPED) {   // AudioStreamSourceNodeBase.cs:315-327

@@ -308,6 +308,27 @@ struct NodeS {
   // or quantises last-bit differences (Context::refOrderSensitivity, per chunk); refOrder = this chunk evaluates the node that way
   // (nodes on the B / C state layout: spectra history + overlap, which R shares)
   bool refSens = false, refOrder = false;
+  // SpatialPannerNode (SpatialPannerNode.cs; DESIGN.md "SpatialPannerNode").  The HRIR set is buffer `irBuf`.  Control plane: the
+  // descriptor of the previous PROCESSED block (spPrev, valid unless the node is new or its last input block was silent) -- it
+  // carries across chunks and render calls.  Device: the last kSpatialMaxTaps samples of the mono mix, double buffered (a chunk
+  // reads one copy and writes the other).
+  int distanceModel = GA_DISTANCE_INVERSE;
+  int hrirAzimuths = 1;
+  int hrirRequested = -1;            // the set the host assigned last (the assignment itself is a queued command): what hrirAzimuths is checked against
+  float spGainBound = 1.f;           // max(1, max over directions and ears of sum |h|): bounds sum |F| + |D| (loop-gain estimate)
+  struct SpatialPrev {
+    bool valid = false;
+    int idx[4] = {0, 0, 0, 0};
+    float w[4] = {0, 0, 0, 0};
+    float g = 0, beta = 0;
+  } spPrev;
+  float* spHist[2] = {nullptr, nullptr};   // [kSpatialMaxTaps] each
+  int spHistCur = 0;
+  // per chunk (valid while spSeq == Context::chunkSeq and spExec is the chunk's executor): where the node's tables and job live
+  uint64_t spSeq = ~0ull;
+  const void* spExec = nullptr;
+  size_t spDescOff = 0, spSegOff = 0;
+  int spJob = -1;
   // feedback cycles: a node that some consumer pulls while it is being processed keeps a copy of the block it put out last
   // (shape of its output views: one row of 128 frames per channel, per output for a ChannelSplitterNode)
   bool staleProducer = false;
@@ -767,6 +788,13 @@ struct Context {
   void planOscillator(NodePlanCtx& k);
   void planDelay(NodePlanCtx& k);
   void planStereoPanner(NodePlanCtx& k);
+  void planSpatialPanner(NodePlanCtx& k);
+  // SpatialPannerNode: geometry of one block (SpatialPannerNode.cs:133-204,263-284 in float32) -> HRIR indices, weights, g, beta
+  void spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& out) const;
+  float spatialParamAt(const NodeS& nd, int p, double t) const;   // the k-rate value of a block: sample 0 of the timeline (event values are clamped when they are scheduled)
+  // the listener transform (SteamAudioContext.cs:45-54, options listener_*): origin, right, up, ahead
+  float listener[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1};
+  bool topoHasSpatial = false;
   void planBufferSource(NodePlanCtx& k);
   void planStreamSource(NodePlanCtx& k);
   void planGain(NodePlanCtx& k);

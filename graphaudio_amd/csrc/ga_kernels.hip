@@ -3085,6 +3085,127 @@ void launch_stereo_panner(hipStream_t s, const PanJob* jobs_dev, int njobs, int6
   GA_LAUNCH_JOBS(stereo_panner_kernel, gx, 256, jobs_dev, njobs);
 }
 
+// =====================================================================================================
+//  SpatialPannerNode (DESIGN.md "SpatialPannerNode"): one workgroup = one node x a run of up to kSpatialRun blocks.
+//    1. the mono mix m of the run's frames and of the T - 1 frames in front of them -> LDS (from the input views, or from the
+//       node's carried history for frames in front of the chunk; silent blocks are zeros)
+//    2. the run's filter pairs -> LDS: slot j belongs to block b0 - 1 + j (slot 0 only when block b0 fades from it); the HRIR
+//       set is read here and nowhere else
+//    3. one wavefront per block: lane l owns samples l and l + 64 and walks k = 0 .. T - 1 in pairs for both ears (and for the
+//       previous block's pair while the block fades): per two taps, four reads of m (consecutive lanes, consecutive banks) and one
+//       16-byte broadcast read per filter pair feed 8 fma (16 while fading) -- 5 LDS reads per 8 fma, 6 per 16
+//  LDS: (kSpatialRun * 128 + 512) + (kSpatialRun + 1) * 2 * 512 floats = 24 KiB at T = 512 with a different filter in every
+//  block: six workgroups per CU by LDS (160 KiB).  Every sum is the same chain whatever the run it falls into, so the output
+//  does not depend on how a render is cut into chunks.
+// =====================================================================================================
+__device__ __forceinline__ float spatial_mix_at(const SpatialJob& job, const SpatialDesc* desc, const SpatialSeg* segs, int64_t f) {
+  if (f < 0) return f >= -(int64_t)kSpatialMaxTaps ? gptr(job.hist_in)[kSpatialMaxTaps + f] : 0.f;
+  const SpatialDesc* d = desc + 1 + (f >> 7);
+  const int sg = d->seg;
+  if (sg < 0) return 0.f;
+  const SpatialSeg s = segs[sg];
+  const float l = gptr(s.in_l)[f];
+  if (d->flags & 2) return 0.5f * (l + gptr(s.in_r)[f]);
+  return l;
+}
+__global__ __launch_bounds__(256) void spatial_panner_kernel(const SpatialWork* __restrict works, const SpatialJob* __restrict jobs,
+                                                             const uint8_t* __restrict tables) {
+  __shared__ float win[kSpatialRun * kBlock + kSpatialMaxTaps];
+  __shared__ __attribute__((aligned(16))) float filt[kSpatialRun + 1][kSpatialMaxTaps][2];   // [slot][k][ear]: taps k, k + 1 of both ears are one 16-byte read
+  const SpatialWork wk = works[blockIdx.x];
+  const SpatialJob job = jobs[wk.job];
+  const SpatialDesc* desc = (const SpatialDesc*)(tables + job.desc_off);
+  const SpatialSeg* segs = (const SpatialSeg*)(tables + job.seg_off);
+  const int tid = threadIdx.x;
+  const int T = min(max(job.taps, 1), kSpatialMaxTaps);
+  if (wk.tail) {   // the last kSpatialMaxTaps samples of m: the next chunk's history (the other copy: other workgroups still read hist_in)
+    const int64_t N = job.nblocks * kBlock;
+    for (int i = tid; i < kSpatialMaxTaps; i += 256) gptr(job.hist_out)[i] = spatial_mix_at(job, desc, segs, N - kSpatialMaxTaps + i);
+  }
+  const int nb = min(wk.nb, kSpatialRun);
+  if (nb <= 0) return;
+  const int64_t fA = (int64_t)wk.b0 * kBlock;
+  const int nfr = nb * kBlock;
+  for (int i = tid; i < nfr + T - 1; i += 256) win[i] = spatial_mix_at(job, desc, segs, fA - (T - 1) + i);   // win[i] = m[fA - (T - 1) + i]
+  for (int j = 0; j <= nb; j++) {
+    const SpatialDesc d = desc[wk.b0 + j];   // (table entry b + 1 = block b: slot j = block b0 - 1 + j)
+    if (j == 0 && !(desc[wk.b0 + 1].flags & 1)) continue;
+    if (j > 0 && d.seg < 0) continue;        // a silent block renders nothing, and the block after it does not fade
+    for (int e = tid; e < 2 * T; e += 256) {
+      const int ear = e >= T ? 1 : 0, k = e - ear * T;
+      float acc = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; q++) acc = fmaf(d.w[q], gptr(job.hrir)[(int64_t)(2 * d.idx[q] + ear) * job.hstride + k], acc);
+      filt[j][k][ear] = d.gb * acc;
+    }
+  }
+  __syncthreads();
+  // One wavefront per block of the run; lane l owns samples l and l + 64 of its block, which share the block's filters: per pair of
+  // taps one 16-byte broadcast read per filter pair and four conflict-free reads of m feed 8 fma (16 while the block fades).
+  const int bl = tid >> 6, lane = tid & 63;
+  if (bl >= nb) return;
+  const SpatialDesc d = desc[wk.b0 + 1 + bl];
+  if (d.seg < 0) return;
+  const bool fade = (d.flags & 1) != 0;
+  const float* w0 = win + (T - 1) + bl * kBlock + lane;   // w0[-k] = m[n - k] for sample n = lane; w0[64 - k] for sample lane + 64
+  const f32x4* fc = (const f32x4*)&filt[bl + 1][0][0];
+  const f32x4* fp = (const f32x4*)&filt[bl][0][0];
+  float cl0 = 0.f, cr0 = 0.f, cl1 = 0.f, cr1 = 0.f, pl0 = 0.f, pr0 = 0.f, pl1 = 0.f, pr1 = 0.f;
+  const int T2 = T & ~1;
+  if (fade) {
+#pragma unroll 2
+    for (int k = 0; k < T2; k += 2) {
+      const f32x4 c = fc[k >> 1], p = fp[k >> 1];
+      const float a0 = w0[-k], a1 = w0[-k - 1], b0 = w0[64 - k], b1 = w0[63 - k];
+      cl0 = fmaf(c.x, a0, cl0); cr0 = fmaf(c.y, a0, cr0); pl0 = fmaf(p.x, a0, pl0); pr0 = fmaf(p.y, a0, pr0);
+      cl1 = fmaf(c.x, b0, cl1); cr1 = fmaf(c.y, b0, cr1); pl1 = fmaf(p.x, b0, pl1); pr1 = fmaf(p.y, b0, pr1);
+      cl0 = fmaf(c.z, a1, cl0); cr0 = fmaf(c.w, a1, cr0); pl0 = fmaf(p.z, a1, pl0); pr0 = fmaf(p.w, a1, pr0);
+      cl1 = fmaf(c.z, b1, cl1); cr1 = fmaf(c.w, b1, cr1); pl1 = fmaf(p.z, b1, pl1); pr1 = fmaf(p.w, b1, pr1);
+    }
+  } else {
+#pragma unroll 2
+    for (int k = 0; k < T2; k += 2) {
+      const f32x4 c = fc[k >> 1];
+      const float a0 = w0[-k], a1 = w0[-k - 1], b0 = w0[64 - k], b1 = w0[63 - k];
+      cl0 = fmaf(c.x, a0, cl0); cr0 = fmaf(c.y, a0, cr0);
+      cl1 = fmaf(c.x, b0, cl1); cr1 = fmaf(c.y, b0, cr1);
+      cl0 = fmaf(c.z, a1, cl0); cr0 = fmaf(c.w, a1, cr0);
+      cl1 = fmaf(c.z, b1, cl1); cr1 = fmaf(c.w, b1, cr1);
+    }
+  }
+  if (T2 < T) {   // an odd T: the last tap on its own (the pair read would look one sample in front of the staged window)
+    const int k = T2;
+    const float a0 = w0[-k], b0 = w0[64 - k];
+    const float l = filt[bl + 1][k][0], r = filt[bl + 1][k][1];
+    cl0 = fmaf(l, a0, cl0); cr0 = fmaf(r, a0, cr0); cl1 = fmaf(l, b0, cl1); cr1 = fmaf(r, b0, cr1);
+    if (fade) {
+      const float ql = filt[bl][k][0], qr = filt[bl][k][1];
+      pl0 = fmaf(ql, a0, pl0); pr0 = fmaf(qr, a0, pr0); pl1 = fmaf(ql, b0, pl1); pr1 = fmaf(qr, b0, pr1);
+    }
+  }
+  const SpatialSeg sg = segs[d.seg];
+  const float pdry = fade ? desc[wk.b0 + bl].dry : 0.f;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int n = lane + 64 * h;
+    const int64_t f = fA + bl * kBlock + n;
+    const float xl = gptr(sg.in_l)[f];
+    const float xr = (d.flags & 2) ? gptr(sg.in_r)[f] : xl;
+    float yl = fmaf(d.dry, xl, h ? cl1 : cl0), yr = fmaf(d.dry, xr, h ? cr1 : cr0);
+    if (fade) {
+      const float wn = (float)(n + 1) * (1.0f / kBlock);
+      yl = fmaf(wn, yl, (1.0f - wn) * fmaf(pdry, xl, h ? pl1 : pl0));
+      yr = fmaf(wn, yr, (1.0f - wn) * fmaf(pdry, xr, h ? pr1 : pr0));
+    }
+    gptr(job.out_l)[f] = yl;
+    gptr(job.out_r)[f] = yr;
+  }
+}
+void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nworks, const SpatialJob* jobs_dev, const uint8_t* tables_dev) {
+  if (nworks <= 0) return;
+  hipLaunchKernelGGL(spatial_panner_kernel, dim3(nworks), dim3(256), 0, s, works_dev, jobs_dev, tables_dev);
+}
+
 
 __global__ __launch_bounds__(256) void delay_kernel(const DelayJob* __restrict jobs) {
   const DelayJob job = jobs[blockIdx.y];

@@ -632,6 +632,44 @@ struct ParamModJob {
 };
 void launch_param_mod(hipStream_t s, const ParamModJob* jobs_dev, int njobs, int64_t max_n);
 
+// SpatialPannerNode (GraphAudio.SteamAudio/Nodes/SpatialPannerNode.cs; DESIGN.md "SpatialPannerNode"): per 128-frame block a pair
+// of FIR filters F[ear][k] = gb * sum_4 w * hrir[idx][ear][k] over the mono mix m of the input, plus the dry signal times `dry`;
+// a block whose descriptor differs from the previous processed block's fades from the previous filters to its own.  The host
+// evaluates the geometry (one descriptor per block), the device does the arithmetic: ascending-k float32 fma chains.
+constexpr int kSpatialMaxTaps = 512;   // T <= 512: the carried history is the last kSpatialMaxTaps samples of m
+constexpr int kSpatialRun = 4;         // blocks per workgroup
+struct SpatialDesc {      // one per block; entry 0 of a node's table is the block in front of the chunk
+  int idx[4];             // directions (j0,i0), (j0,i1), (j1,i0), (j1,i1) of the HRIR set
+  float w[4];             // their bilinear weights
+  float gb;               // g * spatialBlend
+  float dry;              // g * (1 - spatialBlend)
+  int seg;                // index into the node's SpatialSeg table; < 0: the input block is silent
+  int flags;              // bit 0: fade from the previous block's filters ; bit 1: stereo input
+};
+struct SpatialSeg {       // the input views of one segment (chunk-frame indexed)
+  const float* in_l;
+  const float* in_r;      // null: mono input
+};
+struct SpatialJob {       // one node of one chunk
+  const float* hrir;      // channel 2d = left ear of direction d, 2d + 1 = right ear
+  int64_t hstride;        // floats between channels
+  uint64_t desc_off;      // SpatialDesc[nblocks + 1] in the chunk's tables
+  uint64_t seg_off;       // SpatialSeg[] in the chunk's tables
+  const float* hist_in;   // [kSpatialMaxTaps]: m of the frames in front of the chunk (hist_in[kSpatialMaxTaps + f], f < 0)
+  float* hist_out;        // the same for the next chunk (the other copy)
+  float* out_l;
+  float* out_r;
+  int64_t nblocks;        // blocks of the chunk
+  int taps;               // T
+  int pad_;
+};
+struct SpatialWork {      // one workgroup
+  int job;
+  int b0, nb;             // blocks [b0, b0 + nb) of the chunk, nb <= kSpatialRun (0: nothing to render)
+  int tail;               // != 0: also writes hist_out
+};
+void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nworks, const SpatialJob* jobs_dev, const uint8_t* tables_dev);
+
 // ProcessBlockInterleaved (AudioContextBase.cs:125-155): dst[(f0 + i) * channels + ch] = ch < used ? src[ch][f0 + i] : 0
 struct InterleaveSrc {
   const float* ch[32];

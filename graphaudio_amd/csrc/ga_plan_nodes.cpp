@@ -256,6 +256,196 @@ void Context::planStereoPanner(NodePlanCtx& k) {
   ov[1] = pj.out_r;
 }
 
+// ---- SpatialPannerNode (GraphAudio.SteamAudio/Nodes/SpatialPannerNode.cs; DESIGN.md "SpatialPannerNode") ----------------------
+float Context::spatialParamAt(const NodeS& nd, int p, double t) const {   // GetValues()[0] of a k-rate parameter (:119-131)
+  const ParamS& ps = nd.params[p];
+  return ps.events.empty() ? ps.value : param_value_at(ps.events.data(), (int)ps.events.size(), ps.value, t);
+}
+
+// SpatialPannerNode.cs:133-204 and ApplyDistanceModel (:263-284), float32 operation for operation; then the HRIR selection
+// (azimuth / elevation in double from the float32 direction, four bilinear weights rounded to float32).  pv = the 17 parameters.
+void Context::spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& o) const {
+  const float* L = listener;   // origin, right, up, ahead
+  float wx = pv[0] - L[0], wy = pv[1] - L[1], wz = pv[2] - L[2];
+  float distance = std::sqrt(wx * wx + wy * wy + wz * wz);
+  float dx, dy, dz;
+  if (distance > 0.0001f) {
+    const float invDist = 1.0f / distance;
+    wx *= invDist;
+    wy *= invDist;
+    wz *= invDist;
+    dx = wx * L[3] + wy * L[4] + wz * L[5];
+    dy = wx * L[6] + wy * L[7] + wz * L[8];
+    dz = wx * L[9] + wy * L[10] + wz * L[11];
+  } else {
+    dx = 0.f;
+    dy = 0.f;
+    dz = -1.f;
+    distance = 0.f;
+  }
+  float directivity = 1.0f;
+  const float innerAngle = pv[9], outerAngle = pv[10], outerGain = pv[11];
+  if (innerAngle < 360.f || outerAngle < 360.f) {
+    const float oriMag = std::sqrt(pv[3] * pv[3] + pv[4] * pv[4] + pv[5] * pv[5]);
+    if (oriMag > 0.0001f) {
+      const float invOri = 1.0f / oriMag;
+      const float nx = pv[3] * invOri, ny = pv[4] * invOri, nz = pv[5] * invOri;
+      float dot = nx * (-wx) + ny * (-wy) + nz * (-wz);
+      dot = clamp_ref(dot, -1.f, 1.f);
+      const float angleDeg = std::acos(dot) * 180.0f / 3.14159265358979323846f;
+      const float absAngle = std::fabs(angleDeg);
+      const float halfInner = innerAngle * 0.5f, halfOuter = outerAngle * 0.5f;
+      if (absAngle <= halfInner) directivity = 1.0f;
+      else if (absAngle >= halfOuter) directivity = outerGain;
+      else {
+        const float t = (absAngle - halfInner) / (halfOuter - halfInner);
+        directivity = 1.0f + t * (outerGain - 1.0f);
+      }
+    }
+  }
+  const float refDistance = pv[6], maxDistance = pv[7], rolloff = pv[8];
+  // Steam Audio's inverse-distance curve as documented, 1 / max(distance, minDistance) (the library is not available: DESIGN.md section 8)
+  const float steam = 1.0f / max_ref(distance, refDistance);
+  const float dc = clamp_ref(distance, refDistance, maxDistance);
+  float attenuation = 1.0f;
+  switch (nd.distanceModel) {
+    case GA_DISTANCE_LINEAR: attenuation = 1.f - rolloff * (dc - refDistance) / (maxDistance - refDistance); break;
+    case GA_DISTANCE_INVERSE: attenuation = steam; break;
+    case GA_DISTANCE_EXPONENTIAL: attenuation = std::pow(dc / refDistance, -rolloff); break;
+    default: break;
+  }
+  attenuation = clamp_ref(attenuation, 0.f, 1.f);
+  o.g = attenuation * (directivity < 0.999f ? directivity : 1.0f);
+  o.beta = pv[12];
+  // HRIR selection: d = j * A + i, azimuth 360 i / A degrees (0 = -z, +90 = +x), elevation -90 + 180 j / (E - 1)
+  const int A = std::max(nd.hrirAzimuths, 1), E = std::max(D / A, 1);
+  const double PI = 3.14159265358979323846;
+  double az = std::atan2((double)dx, -(double)dz) * (180.0 / PI);
+  if (!(az == az)) az = 0.0;   // (a NaN position: any direction, the gain is NaN as well)
+  if (az < 0.0) az += 360.0;
+  const double pa = az * (double)A / 360.0;
+  double fa0 = std::floor(pa);
+  const double fa = pa - fa0;
+  const int i0 = (int)((int64_t)fa0 % A), i1 = (i0 + 1) % A;
+  int j0 = 0, j1 = 0;
+  double fe = 0.0;
+  if (E > 1) {
+    const double y = dy < -1.f ? -1.0 : (dy > 1.f ? 1.0 : (double)dy);
+    double el = std::asin(y) * (180.0 / PI);
+    if (!(el == el)) el = 0.0;
+    const double pe = (el + 90.0) / 180.0 * (double)(E - 1);
+    j0 = std::min(std::max((int)std::floor(pe), 0), E - 1);
+    j1 = std::min(j0 + 1, E - 1);
+    fe = j1 == j0 ? 0.0 : pe - (double)j0;
+  }
+  o.idx[0] = j0 * A + i0;
+  o.idx[1] = j0 * A + i1;
+  o.idx[2] = j1 * A + i0;
+  o.idx[3] = j1 * A + i1;
+  o.w[0] = (float)((1.0 - fe) * (1.0 - fa));
+  o.w[1] = (float)((1.0 - fe) * fa);
+  o.w[2] = (float)(fe * (1.0 - fa));
+  o.w[3] = (float)(fe * fa);
+  o.valid = true;
+}
+
+// One descriptor per block, made here (not in the simulation, so that a moving source does not cut the chunk into one-block
+// segments for every other node), the segment's workgroups, and -- in the chunk's last segment -- the history of the next chunk.
+void Context::planSpatialPanner(NodePlanCtx& k) {
+  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t n = k.r.n;
+  PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+  if (!hb || hb->length < 1 || hb->length > kSpatialMaxTaps || (hb->channels & 1)) fail(GA_ERR_DEVICE, "internal: spatial panner without a valid HRIR set");
+  const int D = hb->channels / 2;
+  if (nd.spSeq != chunkSeq || nd.spExec != &ex) {   // the node's first segment in this chunk: its tables and its job
+    nd.spSeq = chunkSeq;
+    nd.spExec = &ex;
+    if (!nd.spHist[0]) {
+      for (int i = 0; i < 2; i++) {
+        nd.spHist[i] = (float*)dalloc(kSpatialMaxTaps * sizeof(float));
+        GA_HIP(hipMemsetAsync(nd.spHist[i], 0, kSpatialMaxTaps * sizeof(float), stream));
+      }
+      nd.spHistCur = 0;
+    }
+    std::vector<SpatialDesc> descs((size_t)n + 1);
+    std::memset(descs.data(), 0, descs.size() * sizeof(SpatialDesc));
+    for (auto& d : descs) d.seg = -1;
+    if (nd.spPrev.valid) {   // entry 0: the block in front of the chunk (read when the chunk's first block fades from it)
+      for (int q = 0; q < 4; q++) {
+        descs[0].idx[q] = std::min(std::max(nd.spPrev.idx[q], 0), D - 1);   // (spPrev is dropped when the set changes; never index past the set)
+        descs[0].w[q] = nd.spPrev.w[q];
+      }
+      descs[0].gb = nd.spPrev.g * nd.spPrev.beta;
+      descs[0].dry = nd.spPrev.g * (1.0f - nd.spPrev.beta);
+    }
+    nd.spDescOff = ex.plan.putv(descs);
+    std::vector<SpatialSeg> sgs(std::max<size_t>(ex.segs.size(), 1), SpatialSeg{nullptr, nullptr});
+    nd.spSegOff = ex.plan.putv(sgs);
+    SpatialJob j{};
+    j.hrir = hb->dev;
+    j.hstride = hb->stride;
+    j.desc_off = nd.spDescOff;
+    j.seg_off = nd.spSegOff;
+    j.hist_in = nd.spHist[nd.spHistCur];
+    j.hist_out = nd.spHist[nd.spHistCur ^ 1];
+    j.out_l = ex.nodeOut(ns.id, 0);
+    j.out_r = ex.nodeOut(ns.id, 1);
+    j.nblocks = n;
+    j.taps = (int)hb->length;
+    nd.spHistCur ^= 1;
+    nd.spJob = (int)ex.spatialJobs.size();
+    ex.spatialJobs.push_back(j);
+  }
+  bool tailDone = false;
+  if (ns.ins[0].silent) {   // SteamAudioNodeBase.cs:61-66: cleared output, nothing else runs; the history receives zeros
+    nd.spPrev.valid = false;
+  } else {
+    auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
+    const bool stereo = ns.panMode == 2;
+    SpatialSeg* sgs = (SpatialSeg*)&ex.plan.host[nd.spSegOff];
+    sgs[si].in_l = (iv.size() > 0 && iv[0]) ? iv[0] : zeros;
+    sgs[si].in_r = stereo ? ((iv.size() > 1 && iv[1]) ? iv[1] : zeros) : nullptr;
+    SpatialDesc* descs = (SpatialDesc*)&ex.plan.host[nd.spDescOff];
+    bool moving = false;
+    for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) moving = moving || !nd.params[p].events.empty();
+    NodeS::SpatialPrev cur;
+    const int T = (int)hb->length;
+    for (int64_t b = sg.b0; b < sg.b1; b++) {
+      if (moving || b == sg.b0) {
+        float pv[GA_SPATIAL_PARAM_COUNT];
+        for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) pv[p] = spatialParamAt(nd, p, k.r.bt[b]);
+        spatialGeometry(nd, pv, D, cur);
+      }
+      const NodeS::SpatialPrev& pr = nd.spPrev;
+      bool fade = false;
+      if (pr.valid) {
+        fade = !(pr.g == cur.g) || !(pr.beta == cur.beta);
+        for (int q = 0; q < 4; q++) fade = fade || pr.idx[q] != cur.idx[q] || !(pr.w[q] == cur.w[q]);
+      }
+      SpatialDesc& d = descs[b + 1];
+      for (int q = 0; q < 4; q++) {
+        d.idx[q] = std::min(std::max(cur.idx[q], 0), D - 1);
+        d.w[q] = cur.w[q];
+      }
+      d.gb = cur.g * cur.beta;
+      d.dry = cur.g * (1.0f - cur.beta);
+      d.seg = (int)si;
+      d.flags = (fade ? 1 : 0) | (stereo ? 2 : 0);
+      nd.spPrev = cur;
+      ex.spatialFma += (double)kBlock * T * (fade ? 4.0 : 2.0) + 8.0 * T;
+    }
+    for (int64_t b0 = sg.b0; b0 < sg.b1; b0 += kSpatialRun) {
+      const int nb = (int)std::min<int64_t>(kSpatialRun, sg.b1 - b0);
+      const bool tail = b0 + nb == n;
+      tailDone = tailDone || tail;
+      ex.spatialWorks.push_back(SpatialWork{nd.spJob, (int)b0, nb, tail ? 1 : 0});
+    }
+    ov[0] = ex.nodeOut(ns.id, 0);
+    ov[1] = ex.nodeOut(ns.id, 1);
+  }
+  if (sg.b1 == n && !tailDone) ex.spatialWorks.push_back(SpatialWork{nd.spJob, (int)n, 0, 1});   // the chunk ends on silence: history only
+}
+
 // The per-sample table of a resampler trajectory on the device, up to (excluding) block `upto`: what extend() left in `pending` is
 // appended (through the chunk's tables: a plan entry in front of the launches that read it), the buffer doubles when it is full.
 bool Context::ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto) {
@@ -743,6 +933,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
           case GA_NODE_OSCILLATOR: planOscillator(k); break;
           case GA_NODE_DELAY: planDelay(k); break;
           case GA_NODE_STEREO_PANNER: planStereoPanner(k); break;
+          case GA_NODE_SPATIAL_PANNER: planSpatialPanner(k); break;
           case GA_NODE_BUFFER_SOURCE: planBufferSource(k); break;
           case GA_NODE_STREAM_SOURCE: planStreamSource(k); break;
           case GA_NODE_GAIN: planGain(k); break;

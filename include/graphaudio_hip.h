@@ -72,8 +72,18 @@ enum { /* node types creatable through ga_node_create; the destination is always
   GA_NODE_OSCILLATOR = 9,       /* Nodes/OscillatorNode.cs:12      ; params: 0 = frequency (a-rate) ; scheduled source */
   GA_NODE_DELAY = 10,           /* Nodes/DelayNode.cs:9            ; params: 0 = delayTime (a-rate) ; create_ex arg = maxDelayTime */
   /* the second call site of the resampler */
-  GA_NODE_STREAM_SOURCE = 11    /* GraphAudio.IO/AudioStreamSourceNodeBase.cs:19 (AudioStreamNodeBase) ; params: 0 = playbackRate (k-rate) */
+  GA_NODE_STREAM_SOURCE = 11,   /* GraphAudio.IO/AudioStreamSourceNodeBase.cs:19 (AudioStreamNodeBase) ; params: 0 = playbackRate (k-rate) */
+  /* GraphAudio.SteamAudio/Nodes/SpatialPannerNode.cs:10 ; one input (2 channels, clamped-max, speakers), one 2-channel output.
+     params 0..16, all k-rate (:94-110): positionX/Y/Z, orientationX/Y/Z, refDistance, maxDistance, rolloffFactor, coneInnerAngle,
+     coneOuterAngle, coneOuterGain, spatialBlend, occlusion, transmissionLow/Mid/High.  Two pseudo-parameters take
+     ga_param_set_value / ga_param_get_value only (scheduling calls and ga_node_connect_param return GA_ERR_INVALID_ARGUMENT):
+     17 = distanceModel (GA_DISTANCE_*), 18 = hrirAzimuths (integer A >= 1, default 1).  The HRIR set is assigned with
+     ga_convolver_set_buffer.  The binaural stage is defined in DESIGN.md ("SpatialPannerNode"); the listener transform is the
+     twelve ga_set_option keys listener_{origin,right,up,ahead}_{x,y,z} (identity of SteamAudioContext.cs:45-54 by default). */
+  GA_NODE_SPATIAL_PANNER = 12
 };
+enum { GA_DISTANCE_LINEAR = 0, GA_DISTANCE_INVERSE = 1, GA_DISTANCE_EXPONENTIAL = 2 };   /* SpatialPannerNode.DistanceModelType, SpatialPannerNode.cs:42-47 */
+enum { GA_SPATIAL_PARAM_COUNT = 17, GA_SPATIAL_DISTANCE_MODEL = 17, GA_SPATIAL_HRIR_AZIMUTHS = 18 };
 enum { GA_STREAM_PLAYING = 0, GA_STREAM_PAUSED = 1, GA_STREAM_STOPPED = 2 };   /* StreamState, AudioStreamSourceNodeBase.cs:12-17 */
 enum { GA_FILTER_LOWPASS = 0, GA_FILTER_HIGHPASS, GA_FILTER_BANDPASS, GA_FILTER_NOTCH, GA_FILTER_ALLPASS,
        GA_FILTER_PEAKING, GA_FILTER_LOWSHELF, GA_FILTER_HIGHSHELF }; /* BiQuadFilterNode.cs:288-298 */
@@ -158,7 +168,9 @@ GA_EXPORT int64_t GA_FN(current_block)(ga_context* ctx);       /* AudioContextBa
 GA_EXPORT int GA_FN(set_option)(ga_context* ctx, const char* key, double value); /* tuning knobs, see DESIGN.md ("coarse_long", default 1: impulse responses of 131,073 .. 1,048,576 taps take the coarse-partition formulation D as well -- segmented partition sum; 0: the direct formulations, as for longer ones) */
 GA_EXPORT int GA_FN(get_stats)(ga_context* ctx, ga_stats* out);
 
-/* ---- PlayableAudioBuffer.FromChannelArrays (PlayableAudioBuffer.cs:122-145): immutable sample storage ---- */
+/* ---- PlayableAudioBuffer.FromChannelArrays (PlayableAudioBuffer.cs:122-145): immutable sample storage ----
+ * 1 .. 32 channels for audio; a buffer of up to 4096 channels can be created to hold an HRIR set (GA_NODE_SPATIAL_PANNER) and is
+ * GA_ERR_OUT_OF_RANGE wherever a buffer is played or used as an impulse response. */
 GA_EXPORT int GA_FN(buffer_create)(ga_context* ctx, const float* const* planar, int channels, int64_t frames,
                                    int sample_rate, int* out_buffer_id);
 GA_EXPORT int GA_FN(buffer_release)(ga_context* ctx, int buffer_id);
@@ -219,6 +231,11 @@ GA_EXPORT int GA_FN(biquad_set_type)(ga_context* ctx, int node, int filter_type)
 /* ---- ConvolverNode.Normalize / EnableTrueStereo / Buffer (Nodes/ConvolverNode.cs:25-95) ---- */
 GA_EXPORT int GA_FN(convolver_set_normalize)(ga_context* ctx, int node, int normalize);
 GA_EXPORT int GA_FN(convolver_set_enable_true_stereo)(ga_context* ctx, int node, int enable);
+/* On a GA_NODE_SPATIAL_PANNER the same call assigns the node's HRIR set (buffer_id < 0 clears it): a buffer of 2 * D channels x T
+   frames, 1 <= T <= 512, channel 2d = left ear and 2d + 1 = right ear of direction d = j * A + i (A = hrirAzimuths, azimuth
+   360 i / A degrees, 0 = front, +90 = right; E = D / A elevation rings from -90 to +90 degrees).  An odd channel count, a count that
+   is no multiple of 2 * A, T > 512 or a sample rate other than the context's is GA_ERR_INVALID_OPERATION from this call, as
+   ConvolverNode.Buffer reports a rate mismatch; the assignment itself is applied with the queued commands, like the convolver's. */
 GA_EXPORT int GA_FN(convolver_set_buffer)(ga_context* ctx, int node, int buffer_id); /* buffer_id < 0 = null */
 
 /* ---- AudioStreamNodeBase (GraphAudio.IO/AudioStreamSourceNodeBase.cs:19-329): a queue of PlayableAudioBuffers played back to back
