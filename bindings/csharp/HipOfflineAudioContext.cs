@@ -65,6 +65,20 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _spatialParamSignals;
+    /// <summary>Option "spatial_param_signals" (default off): signals connected to the AudioParams of a Hip.SpatialPannerNode are
+    /// rendered -- the node's per-block descriptors are then made on the device.  Off: such a connection makes Render throw
+    /// NotSupportedException before anything moves.  A signal on Occlusion is refused either way.</summary>
+    public bool SpatialParamSignals
+    {
+        get => _spatialParamSignals;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "spatial_param_signals", value ? 1 : 0));
+            _spatialParamSignals = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

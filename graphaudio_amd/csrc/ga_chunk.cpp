@@ -344,12 +344,20 @@ void Context::chunkTopology(ChunkRun& r) {
   if (topoHasSpatial) {
     const double increment = (double)kBlock / sampleRate;
     for (int id : topo) {
-      const NodeS& nd = *nodes[id];
+      NodeS& nd = *nodes[id];
       if (nd.type != GA_NODE_SPATIAL_PANNER) continue;
+      // (decided here, on the graph as the chunk finds it: a modulator that ends inside the chunk is disconnected by the simulation,
+      // and the blocks before that still read it)
+      nd.spSignals = spatialSignalDriven(nd);
       const std::string who = "SpatialPannerNode " + std::to_string(id) + ": ";
-      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++)
-        if (!nd.params[p].modulation.empty())
+      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) {
+        if (nd.params[p].modulation.empty()) continue;
+        if (!spatialParamSignals)
           fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to parameter " + std::to_string(p) + " (signals on the node's parameters are not on the device path)");
+        if (p == 13)   // (its values exist on the device alone: the host cannot show that occlusion stays at 0)
+          fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to occlusion (Steam Audio's occlusion / three-band transmission filters are not known here, "
+                                         "and a signal's values cannot be shown to stay at 0)");
+      }
       const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
       if (!hb) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
       if ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps)
@@ -369,7 +377,7 @@ void Context::chunkTopology(ChunkRun& r) {
   for (size_t i = 0; i < deviceStateNodes.size();) {
     const int id = deviceStateNodes[i];
     NodeS* np = id < (int)nodes.size() ? nodes[id].get() : nullptr;
-    if (!np || np->disposed || (!np->panOnDevice && !np->coefOnDevice)) {
+    if (!np || np->disposed || (!np->panOnDevice && !np->coefOnDevice && !np->spOnDevice)) {
       deviceStateNodes[i] = deviceStateNodes.back();
       deviceStateNodes.pop_back();
       continue;
@@ -388,6 +396,23 @@ void Context::chunkTopology(ChunkRun& r) {
       nd.panGR = tmp.gain_r;
       nd.panOnDevice = false;
       apiEpoch++;   // (host-tracked state changed: the next first block is traversed)
+    }
+    if (nd.type == GA_NODE_SPATIAL_PANNER && nd.spOnDevice && !spatialSignalDriven(nd)) {
+      // the last signal is gone: the descriptor of the previous processed block comes back once, the host path continues (and its
+      // first block fades from the descriptor the device made).  `valid` never left the host.
+      if (nd.spPrev.valid && nd.spCarry[nd.spCarryCur]) {
+        SpatialCarry tmp;
+        GA_HIP(hipStreamSynchronize(stream));
+        GA_HIP(hipMemcpy(&tmp, nd.spCarry[nd.spCarryCur], sizeof(SpatialCarry), hipMemcpyDeviceToHost));
+        for (int q = 0; q < 4; q++) {
+          nd.spPrev.idx[q] = tmp.idx[q];
+          nd.spPrev.w[q] = tmp.w[q];
+        }
+        nd.spPrev.g = tmp.g;
+        nd.spPrev.beta = tmp.beta;
+      }
+      nd.spOnDevice = false;
+      apiEpoch++;
     }
     if (nd.type == GA_NODE_BIQUAD && nd.coefOnDevice && nd.bqDyn) {
       bool automated = false;

@@ -574,6 +574,7 @@ struct Exec {
   std::vector<SpatialWork> spatialWorks;   // ... and the workgroups of the level being planned
   size_t spatialJobsOff = 0;               // where the job table ends up (put when the chunk's tables are complete: chunkExecute)
   double spatialFma = 0;                   // fused multiply-adds of the level's workgroups
+  std::vector<SpatialDescJob> spatialDescJobs;   // signal-driven spatial nodes of the level being planned (spatial_desc_kernel)
   std::vector<ParamModJob> pmodJobs;
   std::vector<ResampleBlock> traj;  // per-chunk trajectory table (all rates + custom tail blocks)
   bool mixAligned = true;
@@ -957,6 +958,16 @@ struct Exec {
       int nj = (int)panDynJobs.size();
       hipStream_t st = c.stream;
       plan.add(LK_OTHER, [=](uint8_t* base) { launch_stereo_panner_dynamic(st, (const PanDynJob*)(base + off), nj); });
+    }
+    if (!spatialDescJobs.empty()) {   // the descriptors of the level's signal-driven spatial panners: after the mixes, before the panners
+      size_t off = plan.putv(spatialDescJobs);
+      int nj = (int)spatialDescJobs.size(), mx = 0;
+      for (auto& j : spatialDescJobs) mx = std::max(mx, j.nb);
+      hipStream_t st = c.stream;
+      SpatialListener ls;
+      std::memcpy(ls.v, c.listener, sizeof(ls.v));
+      plan.add(LK_OTHER, [=](uint8_t* base) { launch_spatial_desc(st, (const SpatialDescJob*)(base + off), nj, mx, base, ls); });
+      spatialDescJobs.clear();
     }
     if (!spatialWorks.empty()) {   // all spatial panners of the level: one launch
       size_t off = plan.putv(spatialWorks);

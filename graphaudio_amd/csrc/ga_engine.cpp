@@ -241,6 +241,8 @@ Context::~Context() {
     if (np && np->panDev) (void)hipFree(np->panDev);
     if (np && np->spHist[0]) (void)hipFree(np->spHist[0]);
     if (np && np->spHist[1]) (void)hipFree(np->spHist[1]);
+    if (np && np->spCarry[0]) (void)hipFree(np->spCarry[0]);
+    if (np && np->spCarry[1]) (void)hipFree(np->spCarry[1]);
   }
   for (auto& kv : tw16) (void)hipFree(kv.second);
   if (rateModDev) (void)hipFree(rateModDev);
@@ -570,6 +572,14 @@ void Context::doDispose(int id) {
         h = nullptr;
       }
     }
+    if (n.spCarry[0]) {
+      if (stream) (void)hipStreamSynchronize(stream);
+      for (SpatialCarry*& h : n.spCarry) {
+        dfree(h, sizeof(SpatialCarry));
+        h = nullptr;
+      }
+    }
+    n.spOnDevice = false;
     n.irBuf = -1;
     n.hrirRequested = -1;
   }

@@ -324,6 +324,15 @@ struct NodeS {
   } spPrev;
   float* spHist[2] = {nullptr, nullptr};   // [kSpatialMaxTaps] each
   int spHistCur = 0;
+  // Parameters driven by signals (option "spatial_param_signals"): spatial_desc_kernel makes the descriptors, and the VALUES of
+  // spPrev (idx, w, g, beta) live on the device while spOnDevice is set -- double buffered, one job reads spCarry[spCarryCur] and
+  // writes the other.  spPrev.valid stays the host's.  Context::chunkTopology fetches the values back once when the last signal
+  // is disconnected (deviceStateNodes).
+  SpatialCarry* spCarry[2] = {nullptr, nullptr};
+  int spCarryCur = 0;
+  bool spOnDevice = false;
+  bool spSignals = false;                  // per chunk (Context::chunkTopology): this chunk's descriptors are made on the device
+  uint64_t spCurveOff[kSpatialParams] = {};   // per chunk: the per-block values of the parameters on timelines (kSpatialNoCurve: none)
   // per chunk (valid while spSeq == Context::chunkSeq and spExec is the chunk's executor): where the node's tables and job live
   uint64_t spSeq = ~0ull;
   const void* spExec = nullptr;
@@ -696,6 +705,13 @@ struct Context {
   void releaseConvState(NodeS& n);
   void refOrderSensitivity(const std::vector<int>& topo);
   bool ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto);
+  bool spatialParamSignals = false;   // option "spatial_param_signals": SpatialPannerNode parameters accept signals (spatial_desc_kernel); 0 = refused
+  bool spatialSignalDriven(const NodeS& nd) const {   // the node's descriptors are made on the device: a connected signal counts, silent or not
+    if (!spatialParamSignals || nd.type != GA_NODE_SPATIAL_PANNER) return false;
+    for (int p = 0; p < GA_SPATIAL_PARAM_COUNT && p < (int)nd.params.size(); p++)
+      if (!nd.params[p].modulation.empty()) return true;
+    return false;
+  }
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);

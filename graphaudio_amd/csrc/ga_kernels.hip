@@ -3206,6 +3206,88 @@ void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nwor
   hipLaunchKernelGGL(spatial_panner_kernel, dim3(nworks), dim3(256), 0, s, works_dev, jobs_dev, tables_dev);
 }
 
+// ======================================================================================================
+//  SpatialPannerNode descriptors of signal-driven nodes (ga_kernels.hpp, SpatialDescJob): one lane per (node, block), wave64.
+//  A lane depends on no other lane of the launch: the previous block's geometry, which decides the fade, is recomputed from that
+//  block's inputs (blocks b0 + 1 ..), or read from the carried descriptor an earlier launch or the host left (block b0).
+//  The job is read through the uniform pointer (scalar loads), the parameter loops are unrolled: no scratch.
+// ======================================================================================================
+__device__ __forceinline__ void spatial_desc_geometry(const SpatialDescJob& job, const uint8_t* tables, const SpatialListener& L, int b, SpatialGeom& o) {
+  float pv[kSpatialParams];
+#pragma unroll
+  for (int p = 0; p < kSpatialParams; p++) {
+    float v = job.curve_off[p] != kSpatialNoCurve ? gptr((const float*)(tables + job.curve_off[p]))[b] : job.value[p];
+    const float* m = job.mod[p];
+    if (m) v = clamp_ref(v + gptr(m)[(int64_t)b * kBlock], job.vmin[p], job.vmax[p]);   // Math.Clamp(intrinsicValue + modulation, min, max), sample 0
+    pv[p] = v;
+  }
+  spatial_geometry<SpatialMathDouble>(pv, L.v, job.model, job.azimuths, job.dirs, o);
+}
+__global__ __launch_bounds__(64) void spatial_desc_kernel(const SpatialDescJob* __restrict jobs, uint8_t* __restrict tables, SpatialListener L) {
+  const SpatialDescJob& job = jobs[blockIdx.y];
+  const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (i >= job.nb) return;
+  const int b = job.b0 + i;
+  GA_GLOBAL SpatialDesc* desc = gptr((SpatialDesc*)(tables + job.desc_off));
+  const int dmax = max(job.dirs, 1) - 1;
+  SpatialGeom cur, pr;
+  spatial_desc_geometry(job, tables, L, b, cur);
+  bool have = false;
+  if (i > 0) {
+    spatial_desc_geometry(job, tables, L, b - 1, pr);
+    have = true;
+  } else if (job.prev_valid) {
+    SpatialCarry c = job.prev_host;
+    if (job.prev_in) {
+      const GA_GLOBAL SpatialCarry* pc = gptr(job.prev_in);
+      for (int q = 0; q < 4; q++) {
+        c.idx[q] = pc->idx[q];
+        c.w[q] = pc->w[q];
+      }
+      c.g = pc->g;
+      c.beta = pc->beta;
+    }
+    for (int q = 0; q < 4; q++) {
+      pr.idx[q] = c.idx[q];
+      pr.w[q] = c.w[q];
+    }
+    pr.g = c.g;
+    pr.beta = c.beta;
+    have = true;
+    if (b == 0 && job.prev_in) {   // entry 0, the block in front of the chunk (the host wrote it where it holds the descriptor)
+      for (int q = 0; q < 4; q++) {
+        desc[0].idx[q] = min(max(pr.idx[q], 0), dmax);
+        desc[0].w[q] = pr.w[q];
+      }
+      desc[0].gb = pr.g * pr.beta;
+      desc[0].dry = pr.g * (1.0f - pr.beta);
+    }
+  }
+  const bool fade = have && spatial_differs(pr, cur);
+  GA_GLOBAL SpatialDesc* d = desc + b + 1;
+  for (int q = 0; q < 4; q++) {
+    d->idx[q] = min(max(cur.idx[q], 0), dmax);
+    d->w[q] = cur.w[q];
+  }
+  d->gb = cur.g * cur.beta;
+  d->dry = cur.g * (1.0f - cur.beta);
+  d->flags = (d->flags & ~1) | (fade ? 1 : 0);
+  if (i == job.nb - 1) {
+    GA_GLOBAL SpatialCarry* po = gptr(job.prev_out);
+    for (int q = 0; q < 4; q++) {
+      po->idx[q] = cur.idx[q];
+      po->w[q] = cur.w[q];
+    }
+    po->g = cur.g;
+    po->beta = cur.beta;
+  }
+}
+void launch_spatial_desc(hipStream_t s, const SpatialDescJob* jobs_dev, int njobs, int max_nb, uint8_t* tables_dev, const SpatialListener& listener) {
+  if (njobs <= 0 || max_nb <= 0) return;
+  const int gx = (max_nb + 63) / 64;
+  GA_LAUNCH_JOBS(spatial_desc_kernel, gx, 64, jobs_dev, njobs, tables_dev, listener);
+}
+
 
 __global__ __launch_bounds__(256) void delay_kernel(const DelayJob* __restrict jobs) {
   const DelayJob job = jobs[blockIdx.y];

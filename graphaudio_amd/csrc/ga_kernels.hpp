@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "ga_spatial_geom.hpp"
+
 namespace ga {
 
 // A launcher that cannot serve its arguments (a planner bug, e.g. an FFT length without a kernel) reports it as an error
@@ -669,6 +671,35 @@ struct SpatialWork {      // one workgroup
   int tail;               // != 0: also writes hist_out
 };
 void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nworks, const SpatialJob* jobs_dev, const uint8_t* tables_dev);
+
+// Descriptors made on the device (option "spatial_param_signals"; DESIGN.md "SpatialPannerNode", "Parameters driven by signals"):
+// a node with a signal connected to one of its parameters gets its SpatialDesc entries from spatial_desc_kernel -- one lane per
+// (node, block) reads the k-rate value of every parameter (AudioParam.ComputeKRate, AudioParam.cs:144-166: the intrinsic value of
+// the block, plus sample 0 of the mixed modulation input and the clamp where that input is not silent), runs the geometry of
+// ga_spatial_geom.hpp and writes idx / w / gb / dry and the fade bit of entry b + 1.  `seg` and the stereo bit are the host's.
+struct SpatialCarry {     // the previous PROCESSED block as the fade decision compares it (idx not clamped to the set)
+  int idx[4];
+  float w[4];
+  float g, beta;
+  int pad_[2];
+};
+constexpr uint64_t kSpatialNoCurve = ~0ull;
+struct SpatialDescJob {   // one signal-driven node over one segment of a chunk (the modulation inputs' silence is per segment)
+  uint64_t desc_off;      // the node's SpatialDesc[nblocks + 1] in the chunk's tables
+  int b0, nb;             // blocks [b0, b0 + nb) of the chunk: every one of them is processed (the input is not silent)
+  int azimuths, dirs;     // hrirAzimuths, directions of the set
+  int model;              // distance model
+  int prev_valid;         // block b0 has a previous processed block: the carried one (b0 - 1 is not in this job)
+  const SpatialCarry* prev_in;   // ... on the device (what an earlier launch left); null: prev_host
+  SpatialCarry* prev_out;        // receives block b0 + nb - 1 (the other copy: lane 0 of this launch reads prev_in)
+  SpatialCarry prev_host;
+  float value[kSpatialParams];          // the intrinsic value of a parameter without a timeline
+  uint64_t curve_off[kSpatialParams];   // or its per-block values float[nblocks] in the chunk's tables (kSpatialNoCurve: none)
+  const float* mod[kSpatialParams];     // channel 0 of the mixed modulation input, chunk-frame indexed (null: silent in this segment)
+  float vmin[kSpatialParams], vmax[kSpatialParams];
+};
+struct SpatialListener { float v[12]; };   // origin, right, up, ahead
+void launch_spatial_desc(hipStream_t s, const SpatialDescJob* jobs_dev, int njobs, int max_nb, uint8_t* tables_dev, const SpatialListener& listener);
 
 // ProcessBlockInterleaved (AudioContextBase.cs:125-155): dst[(f0 + i) * channels + ch] = ch < used ? src[ch][f0 + i] : 0
 struct InterleaveSrc {

@@ -262,90 +262,20 @@ float Context::spatialParamAt(const NodeS& nd, int p, double t) const {   // Get
   return ps.events.empty() ? ps.value : param_value_at(ps.events.data(), (int)ps.events.size(), ps.value, t);
 }
 
-// SpatialPannerNode.cs:133-204 and ApplyDistanceModel (:263-284), float32 operation for operation; then the HRIR selection
-// (azimuth / elevation in double from the float32 direction, four bilinear weights rounded to float32).  pv = the 17 parameters.
+// SpatialPannerNode.cs:133-204 and ApplyDistanceModel (:263-284), then the HRIR selection: the statements live in
+// ga_spatial_geom.hpp, shared with spatial_desc_kernel; the host takes acos / pow as the C library's float functions.  pv = the 17
+// parameters.
+static_assert(GA_DISTANCE_LINEAR == kSpatialLinear && GA_DISTANCE_INVERSE == kSpatialInverse && GA_DISTANCE_EXPONENTIAL == kSpatialExponential &&
+              GA_SPATIAL_PARAM_COUNT == kSpatialParams, "ga_spatial_geom.hpp restates the interface's constants");
 void Context::spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& o) const {
-  const float* L = listener;   // origin, right, up, ahead
-  float wx = pv[0] - L[0], wy = pv[1] - L[1], wz = pv[2] - L[2];
-  float distance = std::sqrt(wx * wx + wy * wy + wz * wz);
-  float dx, dy, dz;
-  if (distance > 0.0001f) {
-    const float invDist = 1.0f / distance;
-    wx *= invDist;
-    wy *= invDist;
-    wz *= invDist;
-    dx = wx * L[3] + wy * L[4] + wz * L[5];
-    dy = wx * L[6] + wy * L[7] + wz * L[8];
-    dz = wx * L[9] + wy * L[10] + wz * L[11];
-  } else {
-    dx = 0.f;
-    dy = 0.f;
-    dz = -1.f;
-    distance = 0.f;
+  SpatialGeom gm;
+  spatial_geometry<SpatialMathLibm>(pv, listener, nd.distanceModel, nd.hrirAzimuths, D, gm);
+  for (int q = 0; q < 4; q++) {
+    o.idx[q] = gm.idx[q];
+    o.w[q] = gm.w[q];
   }
-  float directivity = 1.0f;
-  const float innerAngle = pv[9], outerAngle = pv[10], outerGain = pv[11];
-  if (innerAngle < 360.f || outerAngle < 360.f) {
-    const float oriMag = std::sqrt(pv[3] * pv[3] + pv[4] * pv[4] + pv[5] * pv[5]);
-    if (oriMag > 0.0001f) {
-      const float invOri = 1.0f / oriMag;
-      const float nx = pv[3] * invOri, ny = pv[4] * invOri, nz = pv[5] * invOri;
-      float dot = nx * (-wx) + ny * (-wy) + nz * (-wz);
-      dot = clamp_ref(dot, -1.f, 1.f);
-      const float angleDeg = std::acos(dot) * 180.0f / 3.14159265358979323846f;
-      const float absAngle = std::fabs(angleDeg);
-      const float halfInner = innerAngle * 0.5f, halfOuter = outerAngle * 0.5f;
-      if (absAngle <= halfInner) directivity = 1.0f;
-      else if (absAngle >= halfOuter) directivity = outerGain;
-      else {
-        const float t = (absAngle - halfInner) / (halfOuter - halfInner);
-        directivity = 1.0f + t * (outerGain - 1.0f);
-      }
-    }
-  }
-  const float refDistance = pv[6], maxDistance = pv[7], rolloff = pv[8];
-  // Steam Audio's inverse-distance curve as documented, 1 / max(distance, minDistance) (the library is not available: DESIGN.md section 8)
-  const float steam = 1.0f / max_ref(distance, refDistance);
-  const float dc = clamp_ref(distance, refDistance, maxDistance);
-  float attenuation = 1.0f;
-  switch (nd.distanceModel) {
-    case GA_DISTANCE_LINEAR: attenuation = 1.f - rolloff * (dc - refDistance) / (maxDistance - refDistance); break;
-    case GA_DISTANCE_INVERSE: attenuation = steam; break;
-    case GA_DISTANCE_EXPONENTIAL: attenuation = std::pow(dc / refDistance, -rolloff); break;
-    default: break;
-  }
-  attenuation = clamp_ref(attenuation, 0.f, 1.f);
-  o.g = attenuation * (directivity < 0.999f ? directivity : 1.0f);
-  o.beta = pv[12];
-  // HRIR selection: d = j * A + i, azimuth 360 i / A degrees (0 = -z, +90 = +x), elevation -90 + 180 j / (E - 1)
-  const int A = std::max(nd.hrirAzimuths, 1), E = std::max(D / A, 1);
-  const double PI = 3.14159265358979323846;
-  double az = std::atan2((double)dx, -(double)dz) * (180.0 / PI);
-  if (!(az == az)) az = 0.0;   // (a NaN position: any direction, the gain is NaN as well)
-  if (az < 0.0) az += 360.0;
-  const double pa = az * (double)A / 360.0;
-  double fa0 = std::floor(pa);
-  const double fa = pa - fa0;
-  const int i0 = (int)((int64_t)fa0 % A), i1 = (i0 + 1) % A;
-  int j0 = 0, j1 = 0;
-  double fe = 0.0;
-  if (E > 1) {
-    const double y = dy < -1.f ? -1.0 : (dy > 1.f ? 1.0 : (double)dy);
-    double el = std::asin(y) * (180.0 / PI);
-    if (!(el == el)) el = 0.0;
-    const double pe = (el + 90.0) / 180.0 * (double)(E - 1);
-    j0 = std::min(std::max((int)std::floor(pe), 0), E - 1);
-    j1 = std::min(j0 + 1, E - 1);
-    fe = j1 == j0 ? 0.0 : pe - (double)j0;
-  }
-  o.idx[0] = j0 * A + i0;
-  o.idx[1] = j0 * A + i1;
-  o.idx[2] = j1 * A + i0;
-  o.idx[3] = j1 * A + i1;
-  o.w[0] = (float)((1.0 - fe) * (1.0 - fa));
-  o.w[1] = (float)((1.0 - fe) * fa);
-  o.w[2] = (float)(fe * (1.0 - fa));
-  o.w[3] = (float)(fe * fa);
+  o.g = gm.g;
+  o.beta = gm.beta;
   o.valid = true;
 }
 
@@ -367,10 +297,27 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
       }
       nd.spHistCur = 0;
     }
+    if (nd.spSignals) {   // descriptors made on the device: the carried descriptor's two copies, the per-block values of the timelines
+      if (!nd.spCarry[0]) {
+        for (int i = 0; i < 2; i++) {
+          nd.spCarry[i] = (SpatialCarry*)dalloc(sizeof(SpatialCarry));
+          GA_HIP(hipMemsetAsync(nd.spCarry[i], 0, sizeof(SpatialCarry), stream));
+        }
+        nd.spCarryCur = 0;
+      }
+      std::vector<float> curve;
+      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) {
+        nd.spCurveOff[p] = kSpatialNoCurve;
+        if (nd.params[p].events.empty()) continue;
+        curve.resize((size_t)n);
+        for (int64_t b = 0; b < n; b++) curve[(size_t)b] = spatialParamAt(nd, p, k.r.bt[b]);
+        nd.spCurveOff[p] = ex.plan.putv(curve);
+      }
+    }
     std::vector<SpatialDesc> descs((size_t)n + 1);
     std::memset(descs.data(), 0, descs.size() * sizeof(SpatialDesc));
     for (auto& d : descs) d.seg = -1;
-    if (nd.spPrev.valid) {   // entry 0: the block in front of the chunk (read when the chunk's first block fades from it)
+    if (nd.spPrev.valid && !nd.spOnDevice) {   // entry 0: the block in front of the chunk (read when the chunk's first block fades from it)
       for (int q = 0; q < 4; q++) {
         descs[0].idx[q] = std::min(std::max(nd.spPrev.idx[q], 0), D - 1);   // (spPrev is dropped when the set changes; never index past the set)
         descs[0].w[q] = nd.spPrev.w[q];
@@ -406,11 +353,56 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
     sgs[si].in_l = (iv.size() > 0 && iv[0]) ? iv[0] : zeros;
     sgs[si].in_r = stereo ? ((iv.size() > 1 && iv[1]) ? iv[1] : zeros) : nullptr;
     SpatialDesc* descs = (SpatialDesc*)&ex.plan.host[nd.spDescOff];
+    if (nd.spSignals) {
+      // One job of spatial_desc_kernel for this segment.  The modulation inputs are mixed by this level's mix jobs; the kernel reads
+      // sample 0 of every block (no per-frame curve is made for these k-rate parameters).  Signals on occlusion (refused) and on
+      // transmissionLow / Mid / High (no effect while occlusion is 0) are not resolved: the geometry reads parameters 0 .. 12.
+      SpatialDescJob dj{};
+      dj.desc_off = nd.spDescOff;
+      dj.b0 = (int)sg.b0;
+      dj.nb = (int)(sg.b1 - sg.b0);
+      dj.azimuths = nd.hrirAzimuths;
+      dj.dirs = D;
+      dj.model = nd.distanceModel;
+      dj.prev_valid = nd.spPrev.valid ? 1 : 0;
+      dj.prev_in = nd.spOnDevice ? nd.spCarry[nd.spCarryCur] : nullptr;
+      dj.prev_out = nd.spCarry[nd.spCarryCur ^ 1];
+      for (int q = 0; q < 4; q++) {
+        dj.prev_host.idx[q] = nd.spPrev.idx[q];
+        dj.prev_host.w[q] = nd.spPrev.w[q];
+      }
+      dj.prev_host.g = nd.spPrev.g;
+      dj.prev_host.beta = nd.spPrev.beta;
+      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) {
+        const ParamS& ps = nd.params[p];
+        dj.value[p] = ps.value;
+        dj.curve_off[p] = nd.spCurveOff[p];
+        dj.vmin[p] = ps.minv;
+        dj.vmax[p] = ps.maxv;
+        dj.mod[p] = nullptr;
+        if (p <= 12 && !ns.pinSilent(p)) {
+          auto mv = ex.resolveInSeg((int)si, ns.id, -1 - p, ns.pins[p], false, nullptr);
+          dj.mod[p] = (!mv.empty() && mv[0]) ? mv[0] : nullptr;
+        }
+      }
+      descs = (SpatialDesc*)&ex.plan.host[nd.spDescOff];   // (resolveInSeg does not touch the plan's tables; taken again all the same)
+      const int T = (int)hb->length;
+      for (int64_t b = sg.b0; b < sg.b1; b++) {
+        descs[b + 1].seg = (int)si;
+        descs[b + 1].flags = stereo ? 2 : 0;   // (the fade bit is the kernel's; the launch is accounted as if every block faded)
+        ex.spatialFma += (double)kBlock * T * 4.0 + 8.0 * T;
+      }
+      ex.spatialDescJobs.push_back(dj);
+      nd.spCarryCur ^= 1;
+      if (!nd.spOnDevice) deviceStateNodes.push_back(ns.id);
+      nd.spOnDevice = true;
+      nd.spPrev.valid = true;
+    }
     bool moving = false;
     for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) moving = moving || !nd.params[p].events.empty();
     NodeS::SpatialPrev cur;
     const int T = (int)hb->length;
-    for (int64_t b = sg.b0; b < sg.b1; b++) {
+    for (int64_t b = sg.b0; b < sg.b1 && !nd.spSignals; b++) {
       if (moving || b == sg.b0) {
         float pv[GA_SPATIAL_PARAM_COUNT];
         for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) pv[p] = spatialParamAt(nd, p, k.r.bt[b]);

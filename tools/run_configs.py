@@ -83,6 +83,35 @@ elif which == "spatial":   # SpatialPannerNode at scale: every voice through its
         s.Connect(p).Connect(ctx.Destination)
         s.Start()
     ch = 2
+elif which == "spatial_signals":   # the scene above with every orbit driven by two oscillators (option spatial_param_signals): descriptors made on the device
+    import math
+    from graphaudio_amd import AudioBufferSourceNode, GainNode, HrirSet, OscillatorNode, PlayableAudioBuffer, SpatialPannerNode
+    ctx.SetOption("spatial_param_signals", 1)
+    n_voices = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
+    T, A, E = 256, 24, 7
+    k = np.arange(T)
+    hrir = (np.random.default_rng(5).standard_normal((A * E, 2, T)) * np.exp(-6.9 * k / T) * 0.1).astype(np.float32)
+    ctx.SetHrir(HrirSet.FromArray(hrir, SR), A)
+    period = 5.0
+    for v in range(n_voices):
+        s = AudioBufferSourceNode(ctx)
+        s.Buffer = PlayableAudioBuffer.FromMonoArray(G.voice(v, frames + 256, 1.0 / 64.0), SR)
+        p = SpatialPannerNode(ctx)
+        radius, freq = 1.5 + 2.0 * (v % 17) / 17.0, (1.0 + (v % 7) / 50.0) / period
+        p.PositionY.Value = -1.0 + 2.0 * (v % 5) / 4.0
+        # x = r sin(w t); z = r sin(w (t - T / 4)) = -r cos(w t) from a quarter period on (0 before: the orbit opens along x).  A
+        # GainNode's stereo output reaches the parameter as (L + R) / sqrt(2): its gain is r / sqrt(2).
+        for param, when in ((p.PositionX, 0.0), (p.PositionZ, 0.25 / freq)):
+            o = OscillatorNode(ctx)
+            o.Frequency.Value = freq
+            g = GainNode(ctx)
+            g.Gain.Value = radius / math.sqrt(2.0)
+            o.Connect(g)
+            g.Connect(param)
+            o.Start(when)
+        s.Connect(p).Connect(ctx.Destination)
+        s.Start()
+    ch = 2
 else:
     raise SystemExit("unknown config")
 print(f"build {time.time() - t0:.1f} s")
@@ -96,7 +125,7 @@ for rep in range(4):   # the first pieces carry one-time costs (formulation assi
 st = ctx.GetStats()
 print(json.dumps({k: st[k] for k in ("chunks", "segments", "kernel_launches", "device_ms_total", "mac_ms_total", "fft_ms_total", "other_ms_total", "device_bytes_in_use")}))
 print("rms", G.rms(out))
-if which == "spatial":   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
+if which in ("spatial", "spatial_signals"):   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
     ms, flops = st["stage_ms"][0], st["stage_flops"][0]
     print(f"stage other ({st['stage_kernel'][0]}): {ms:.2f} ms over {st['profiled_chunks']} chunks, {flops / 2 / 1e9:.1f} G fma, "
           f"{flops / 2 / max(ms, 1e-9) / 1e9:.2f} T fma/s = {flops / 2 / max(ms, 1e-9) / 1e9 / 78.65 * 100:.1f} % of the fp32 vector peak (all 'other' kernels in the time)")
