@@ -7,10 +7,15 @@ namespace ga {
 // ======================================================================================================
 // slabs: chunk-frame indexed float arrays handed to node outputs / mixed inputs for the duration of a chunk
 // ======================================================================================================
+// slabs are allocated in blocks of about 1 GiB: how many slabs of `slabBytes` one block holds
+size_t slabsPerBlock(size_t slabBytes) {
+  return slabBytes ? std::max<size_t>(8, std::min<size_t>(1024, ((size_t)1 << 30) / slabBytes)) : 0;
+}
+
 float* getSlab(Context& c) {
   if (c.slabFree.empty()) {
     size_t slabBytes = (size_t)c.slabFrames * sizeof(float);
-    size_t count = std::max<size_t>(8, std::min<size_t>(1024, ((size_t)1 << 30) / slabBytes));
+    size_t count = slabsPerBlock(slabBytes);
     char* blk = (char*)c.dalloc(slabBytes * count);
     c.slabBlocks.push_back(blk);
     for (size_t i = 0; i < count; i++) {
@@ -29,8 +34,7 @@ void resetSlabs(Context& c, int64_t frames) {
   if (need > c.slabFrames) {
     GA_HIP(hipStreamSynchronize(c.stream));
     size_t oldBytes = (size_t)c.slabFrames * sizeof(float);
-    size_t perBlock = oldBytes ? std::max<size_t>(8, std::min<size_t>(1024, ((size_t)1 << 30) / oldBytes)) : 0;
-    for (void* p : c.slabBlocks) c.dfree(p, oldBytes * perBlock);
+    for (void* p : c.slabBlocks) c.dfree(p, oldBytes * slabsPerBlock(oldBytes));
     c.slabBlocks.clear();
     c.slabAll.clear();
     c.slabFrames = need;
@@ -79,16 +83,7 @@ void Context::runChunk(int64_t n, float* const* bus) {
 
 // pass 1: reachability, level and convolver depth of every node; state handed back by automated runs that ended
 void Context::chunkTopology(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
   std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
   // ---- reachability, level, convolver depth on the graph as it stands after the queued commands ----
   // (cached while no connection, disposal or impulse response changed since the last chunk)
   // (a graph with feedback is walked again every chunk: whether its loops can be cut at their DelayNodes depends on the delay
@@ -276,8 +271,8 @@ void Context::chunkTopology(ChunkRun& r) {
     topoStatsVersion = graphVersion;
     topoStatsSize = topo.size();
   }
-  maxDepth = topoMaxDepth;
-  maxLevel = topoMaxLevel;
+  r.maxDepth = topoMaxDepth;
+  r.maxLevel = topoMaxLevel;
   // ---- playbackRate modulated by a signal (AudioBufferSourceNode / AudioStreamSourceNode): a two-stage chunk (runTwoStageChunk) ----
   // The rate decides how many samples each block consumes and where a one-shot source ends, and the planner needs that before it can
   // plan the rest: the modulation inputs' cone is rendered first.  The cases that cannot be split so are refused here, before any state
@@ -433,15 +428,11 @@ void Context::chunkTopology(ChunkRun& r) {
 
 // pass 2: block clock, source timelines, control-plane simulation -> segments (from here on control state moves)
 void Context::chunkSimulate(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
   std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  int64_t& n = r.n;
+  std::vector<double>& bt = r.bt;
+  std::vector<int>& srcIds = r.srcIds;
+  std::vector<SrcPlanOut>& srcPlans = r.srcPlans;
   r.tmTopo = nowMs();
   // ---- block clock (accumulated, AudioContextBase.cs:78-79) ----
   bt.assign(n + 1, 0.0);
@@ -506,7 +497,7 @@ void Context::chunkSimulate(ChunkRun& r) {
     uint64_t prevHash = lastHash;
     const size_t kMaxSegs = 96;
     while (b < n) {
-      if (segs.size() >= kMaxSegs && r.stage != 2) {  // too fragmented: stop the chunk here, the caller continues with a new one
+      if (r.segs.size() >= kMaxSegs && r.stage != 2) {  // too fragmented: stop the chunk here, the caller continues with a new one
         // (not in the second stage of a two-stage chunk: the first stage has rendered its blocks)
         n = b;
         break;
@@ -626,7 +617,7 @@ void Context::chunkSimulate(ChunkRun& r) {
         minDestCh = std::min(minDestCh, sg.nodes.back().outCh);
       }
       b = sg.b1;
-      segs.push_back(std::move(sg));
+      r.segs.push_back(std::move(sg));
     }
     lastHash = prevHash;
     if (n < (int64_t)bt.size() - 1) {
@@ -642,23 +633,14 @@ void Context::chunkSimulate(ChunkRun& r) {
 
 // pass 3: per-chunk device resources (delay lines, slabs, zero page, bus)
 void Context::chunkResources(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
-  std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  const int64_t frames = r.n * kBlock;
   // ---- DelayNode state: history [rings][maxDelay] (persistent) and the chunk's line [rings][maxDelay + frames] ----
-  for (int id : topo) {
+  for (int id : r.topo) {
     NodeS& nd = *nodes[id];
     if (nd.type != GA_NODE_DELAY) continue;
     nd.delayLoaded = false;
     int rings = std::max(nd.delayRings, 2);
-    for (const Segment& sg : segs)
+    for (const Segment& sg : r.segs)
       for (const NodeSeg& ns : sg.nodes)
         if (ns.id == id) rings = std::max(rings, ns.ins[0].bufCh);   // EnsureChannelCount (:102-113): new rings start empty
     nd.delayRings = rings;
@@ -708,7 +690,7 @@ void Context::chunkResources(ChunkRun& r) {
   while ((int)busSlabs.size() < 32 && (int)busSlabs.size() < std::max(destOutCh, 2)) busSlabs.push_back((float*)dalloc((size_t)busCapFrames * 4));
   {
     int mx = 0;
-    for (auto& sg : segs)
+    for (auto& sg : r.segs)
       if (r.stage != 1) mx = std::max(mx, sg.nodes.back().outCh);
     while ((int)busSlabs.size() < mx) busSlabs.push_back((float*)dalloc((size_t)busCapFrames * 4));
   }
@@ -717,15 +699,7 @@ void Context::chunkResources(ChunkRun& r) {
 
 // pass 9: upload the job tables, enqueue every recorded launch in order, profile events
 void Context::chunkExecute(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  int64_t& n = r.n;
   Exec& ex = *r.ex;
   r.tmPlan = nowMs();
   if (!pendingHandOver.empty()) {   // no pre-mix launch in this chunk took the previous chunk's hand-over along: copies in front
@@ -820,19 +794,13 @@ void Context::chunkExecute(ChunkRun& r) {
 
 // pass 10: commit the control state (source positions, Ended / Dispose bookkeeping, block clock) to the end of the chunk
 void Context::chunkCommit(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  int64_t& n = r.n;
+  std::vector<double>& bt = r.bt;
+  std::vector<int>& srcIds = r.srcIds;
   // ---- commit the control state to the end of the chunk ----
   for (size_t i = 0; i < srcIds.size(); i++) {
     NodeS& s = *nodes[srcIds[i]];
-    SrcPlanOut& po = srcPlans[i];
+    SrcPlanOut& po = r.srcPlans[i];
     if (s.type != GA_NODE_BUFFER_SOURCE) {  // ConstantSourceNode / OscillatorNode: only the Ended + Dispose bookkeeping
       if (po.gone && po.goneAt <= n) {
         if (!s.endedRaised) endedQueue.push_back(srcIds[i]);
@@ -897,10 +865,10 @@ void Context::chunkCommit(ChunkRun& r) {
   currentTime = bt[n];
   stats.blocks_rendered = currentBlock;
   stats.chunks++;
-  stats.segments += (int64_t)segs.size();
+  stats.segments += (int64_t)r.segs.size();
   chunkBlocksDone = n;
   chunkSegCh.clear();
-  for (const Segment& sg : segs) chunkSegCh.push_back(SegCh{sg.b0, sg.b1, sg.nodes.back().outCh});
+  for (const Segment& sg : r.segs) chunkSegCh.push_back(SegCh{sg.b0, sg.b1, sg.nodes.back().outCh});
 }
 
 void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
@@ -1180,14 +1148,10 @@ void Context::chunkRateProbe(ChunkRun& r) {
     pj.pad_ = 0;
     pj.out = ratesDev + (size_t)k * n;
   }
-  const size_t pjOff = ex.plan.putv(pjobs), btOff = ex.plan.putv(r.bt);
+  const size_t btOff = ex.plan.putv(r.bt);
   hipStream_t st = stream;
-  ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_krate_probe(st, (const KrateProbeJob*)(base + pjOff), nm, base, (const double*)(base + btOff), n); });
-  if (!walks.empty()) {
-    const size_t wOff = ex.plan.putv(walks);
-    const int nw = (int)walks.size();
-    ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_gsr_walk(st, (const GsrWalkJob*)(base + wOff), nw); });
-  }
+  ex.flush(pjobs, LK_OTHER, nullptr, [=](const KrateProbeJob* t, int nj, int64_t, uint8_t* base) { launch_krate_probe(st, t, nj, base, (const double*)(base + btOff), n); });
+  ex.flush(walks, LK_OTHER, nullptr, [=](const GsrWalkJob* t, int nw, int64_t, uint8_t*) { launch_gsr_walk(st, t, nw); });
   void* hostDst = rateModHost;
   const void* devSrc = rateModDev;
   ex.plan.add(LK_OTHER, [=](uint8_t*) { GA_HIP(hipMemcpyAsync(hostDst, devSrc, readBytes, hipMemcpyDeviceToHost, st)); });

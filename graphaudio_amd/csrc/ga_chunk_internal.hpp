@@ -50,6 +50,7 @@ struct Plan {
 };
 
 // slabs: chunk-frame indexed float arrays handed to node outputs / mixed inputs for the duration of a chunk (ga_chunk.cpp)
+size_t slabsPerBlock(size_t slabBytes);
 float* getSlab(Context& c);
 void resetSlabs(Context& c, int64_t frames);
 
@@ -126,18 +127,24 @@ struct Sim {
       if (!c.nodes[id]->disposed) evalNode(id);   // (a source of the cone disposed at the chunk's first block: chunkSimulate)
     for (const auto& pm : mods) {
       InSeg is;
-      is.bufCh = 1;
-      is.silent = true;
-      for (auto& m : c.nodes[pm.first]->params[pm.second].modulation) {
-        evalNode(m.first);
-        const NodeS& pn = *c.nodes[m.first];
-        const OutputS& o = pn.outputs[m.second];
-        if (o.bufCh != 0 && !o.silent) {
-          is.terms.push_back(TermS{m.first, m.second, o.bufCh, pn.isProcessing});
-          is.silent = false;
-        }
-      }
+      pullMod(c.nodes[pm.first]->params[pm.second], is);
       cur->probe.push_back(std::move(is));
+    }
+  }
+
+  // the modulation input of a parameter as AudioParam.ComputeValues pulls it: 1 channel, explicit, a term for every non-silent
+  // producer (AudioParam.cs:68,97-101)
+  void pullMod(ParamS& ps, InSeg& is) {
+    is.bufCh = 1;
+    is.silent = true;
+    for (auto& m : ps.modulation) {
+      evalNode(m.first);
+      const NodeS& pn = *c.nodes[m.first];
+      const OutputS& o = pn.outputs[m.second];
+      if (o.bufCh != 0 && !o.silent) {
+        is.terms.push_back(TermS{m.first, m.second, o.bufCh, pn.isProcessing});
+        is.silent = false;
+      }
     }
   }
 
@@ -216,21 +223,7 @@ struct Sim {
     bool anyMod = false;
     for (auto& ps : n_.params) anyMod = anyMod || !ps.modulation.empty();
     if (anyMod) ns.pins.resize(n_.params.size());
-    for (int p = 0; anyMod && p < (int)n_.params.size(); p++) {
-      auto& mod = n_.params[p].modulation;
-      InSeg& is = ns.pins[p];
-      is.bufCh = 1;
-      is.silent = true;
-      for (auto& m : mod) {
-        evalNode(m.first);
-        const NodeS& pn = *c.nodes[m.first];
-        const OutputS& o = pn.outputs[m.second];
-        if (o.bufCh != 0 && !o.silent) {
-          is.terms.push_back(TermS{m.first, m.second, o.bufCh, pn.isProcessing});
-          is.silent = false;
-        }
-      }
-    }
+    for (int p = 0; anyMod && p < (int)n_.params.size(); p++) pullMod(n_.params[p], ns.pins[p]);
     for (int i = 0; i < (int)n_.inputs.size(); i++) pull(n_, i, ns.ins[i]);
     process(n_, ns);
     n_.isProcessing = false;
@@ -578,7 +571,6 @@ struct Exec {
   std::vector<ParamModJob> pmodJobs;
   std::vector<ResampleBlock> traj;  // per-chunk trajectory table (all rates + custom tail blocks)
   bool mixAligned = true;
-  // conv inputs: node -> slot -> per segment view
   // conv inputs: node -> per segment views of its input channels (a dense table: one lookup per convolver and pass)
   struct ConvInRow {   // the per-segment views of one node (a window of ConvIn::flat)
     Views* p = nullptr;
@@ -817,25 +809,49 @@ struct Exec {
     return pj.out;
   }
 
+  // One queue of jobs -> one recorded launch: the table is uploaded, `launch(table, jobs, extent, base)` is recorded, the queue is
+  // cleared (an empty queue records nothing).  `extent` names the member that holds a job's length (n, nblocks, nb); the launch
+  // gets the largest, or 0 for nullptr.
+  template <class J, class E>
+  static int64_t maxExtent(const std::vector<J>& q, E J::*extent) {
+    int64_t mx = 0;
+    for (const J& j : q) mx = std::max<int64_t>(mx, j.*extent);
+    return mx;
+  }
+  template <class J>
+  static int64_t maxExtent(const std::vector<J>&, std::nullptr_t) { return 0; }
+  template <class J, class Ext, class Launch>
+  void flush(std::vector<J>& q, int kind, Ext extent, Launch launch, double bytes = 0.0, double flops = 0.0) {
+    if (q.empty()) return;
+    const size_t off = plan.putv(q);
+    const int nj = (int)q.size();
+    const int64_t mx = maxExtent(q, extent);
+    plan.add(kind, [=](uint8_t* base) { launch((const J*)(base + off), nj, mx, base); }, bytes, flops);
+    q.clear();
+  }
+
+  static double mixBytes(const std::vector<MixJob>& q) {
+    double b = 0;
+    for (auto& j : q) b += 4.0 * (double)(j.nterms + 1) * (double)j.n;
+    return b;
+  }
+
+  // the queues of one level, in launch order (everything in one level is independent; a queue's table is uploaded where it is launched)
   void flushLevel() {
-    // order: down-mix -> mix -> sources -> gain -> biquad (everything in one level is independent)
-    size_t termsOff = plan.putv(terms);
+    const size_t termsOff = plan.putv(terms);
     termGains.resize(terms.size(), 1.f);
     termCurves.resize(terms.size(), nullptr);
     const bool scaled = anyTermGain;
     const size_t gainsOff = scaled ? plan.putv(termGains) : 0;
     const bool curved = anyTermCurve;
     const size_t curvesOff = curved ? plan.putv(termCurves) : 0;
-    if (!dmJobs.empty()) {
-      size_t off = plan.putv(dmJobs);
-      int nj = (int)dmJobs.size();
-      int64_t mx = 0;
-      for (auto& j : dmJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) {
-        launch_downmix(st, (const DownmixJob*)(base + off), nj, (const float* const*)(base + termsOff), mx, scaled ? (const float*)(base + gainsOff) : nullptr);
-      });
-    }
+    const hipStream_t st = c.stream;
+    auto termTable = [=](uint8_t* base) { return (const float* const*)(base + termsOff); };
+    auto gainTable = [=](uint8_t* base) { return scaled ? (const float*)(base + gainsOff) : nullptr; };
+    auto curveTable = [=](uint8_t* base) { return curved ? (const float* const*)(base + curvesOff) : nullptr; };
+    flush(dmJobs, LK_OTHER, &DownmixJob::n, [=](const DownmixJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_downmix(st, t, nj, termTable(base), mx, gainTable(base));
+    });
     // buses of many terms go to the wide kernel while there are few of them (ga_kernels.hip, mix_wide_kernel)
     std::vector<MixJob> wideJobs;
     {
@@ -848,173 +864,57 @@ struct Exec {
         mixJobs.swap(rest);
       }
     }
-    if (!wideJobs.empty()) {
-      size_t off = plan.putv(wideJobs);
-      int nj = (int)wideJobs.size();
-      int64_t mx = 0;
-      double mixBytes = 0;
-      for (auto& j : wideJobs) {
-        mx = std::max(mx, j.n);
-        mixBytes += 4.0 * (double)(j.nterms + 1) * (double)j.n;
-      }
-      hipStream_t st = c.stream;
-      plan.add(LK_MIX, [=](uint8_t* base) {
-        launch_mix_wide(st, (const MixJob*)(base + off), nj, (const float* const*)(base + termsOff), mx, scaled ? (const float*)(base + gainsOff) : nullptr,
-                        curved ? (const float* const*)(base + curvesOff) : nullptr);
-      }, mixBytes);
-    }
-    if (!mixJobs.empty()) {
-      size_t off = plan.putv(mixJobs);
-      int nj = (int)mixJobs.size();
-      int64_t mx = 0;
-      for (auto& j : mixJobs) mx = std::max(mx, j.n);
-      bool v4 = mixAligned;
-      hipStream_t st = c.stream;
-      double mixBytes = 0;
-      for (auto& j : mixJobs) mixBytes += 4.0 * (double)(j.nterms + 1) * (double)j.n;
-      plan.add(LK_MIX, [=](uint8_t* base) {
-        launch_mix(st, (const MixJob*)(base + off), nj, (const float* const*)(base + termsOff), mx, v4, scaled ? (const float*)(base + gainsOff) : nullptr,
-                   curved ? (const float* const*)(base + curvesOff) : nullptr);
-      }, mixBytes);
-    }
-    if (!pmodJobs.empty()) {   // after the mixes (the modulation inputs), before the nodes that read the parameter
-      size_t off = plan.putv(pmodJobs);
-      int nj = (int)pmodJobs.size();
-      int64_t mx = 0;
-      for (auto& j : pmodJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_param_mod(st, (const ParamModJob*)(base + off), nj, mx); });
-    }
-    if (!loopJobs.empty()) {
-      size_t off = plan.putv(loopJobs);
-      int nj = (int)loopJobs.size();
-      int64_t mx = 0;
-      for (auto& j : loopJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_loop_source(st, (const LoopJob*)(base + off), nj, mx); });
-    }
-    if (!rsJobs.empty()) {
-      size_t off = plan.putv(rsJobs);
-      int nj = (int)rsJobs.size();
-      int64_t mx = 0;
-      for (auto& j : rsJobs) mx = std::max(mx, j.nblocks);
-      hipStream_t st = c.stream;
-      rsLaunches.push_back(RsLaunch{off, nj, mx});
-      plan.add(LK_OTHER, [this, st, idx = rsLaunches.size() - 1](uint8_t* base) {
-        const RsLaunch& r = rsLaunches[idx];
-        launch_resample(st, (const ResampleJob*)(base + r.off), r.nj, (const ResampleBlock*)(base + trajOffFinal), r.mx);
-      });
-    }
-    if (!rsFastJobs.empty()) {
-      size_t off = plan.putv(rsFastJobs);
-      int nj = (int)rsFastJobs.size();
-      int64_t mx = 0;
-      for (auto& j : rsFastJobs) mx = std::max(mx, j.nblocks);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_resample_fast(st, (const ResampleFastJob*)(base + off), nj, mx); });
-    }
-    if (!gsrJobs.empty()) {
-      size_t off = plan.putv(gsrJobs);
-      int nj = (int)gsrJobs.size();
-      int64_t mx = 0;
-      for (auto& j : gsrJobs) mx = std::max(mx, j.nblocks);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_gsr(st, (const GsrJob*)(base + off), nj, base, mx); });
-    }
-    if (!streamJobs.empty()) {
-      size_t off = plan.putv(streamJobs);
-      int nj = (int)streamJobs.size();
-      int64_t mx = 0;
-      for (auto& j : streamJobs) mx = std::max(mx, j.nblocks);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_stream(st, (const StreamJob*)(base + off), nj, base, mx); });
-    }
-    if (!constJobs.empty()) {
-      size_t off = plan.putv(constJobs);
-      int nj = (int)constJobs.size();
-      int64_t mx = 0;
-      for (auto& j : constJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_const_source(st, (const ConstJob*)(base + off), nj, mx); });
-    }
-    if (!oscJobs.empty()) {
-      size_t off = plan.putv(oscJobs);
-      int nj = (int)oscJobs.size();
-      hipStream_t st = c.stream;
-      bool anyCurve = false;
-      for (auto& j : oscJobs) anyCurve = anyCurve || j.curve != nullptr;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_oscillator(st, (const OscJob*)(base + off), nj, anyCurve); });
-    }
-    if (!panJobs.empty()) {
-      size_t off = plan.putv(panJobs);
-      int nj = (int)panJobs.size();
-      int64_t mx = 0;
-      for (auto& j : panJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_stereo_panner(st, (const PanJob*)(base + off), nj, mx); });
-    }
-    if (!panDynJobs.empty()) {
-      size_t off = plan.putv(panDynJobs);
-      int nj = (int)panDynJobs.size();
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_stereo_panner_dynamic(st, (const PanDynJob*)(base + off), nj); });
-    }
-    if (!spatialDescJobs.empty()) {   // the descriptors of the level's signal-driven spatial panners: after the mixes, before the panners
-      size_t off = plan.putv(spatialDescJobs);
-      int nj = (int)spatialDescJobs.size(), mx = 0;
-      for (auto& j : spatialDescJobs) mx = std::max(mx, j.nb);
-      hipStream_t st = c.stream;
-      SpatialListener ls;
-      std::memcpy(ls.v, c.listener, sizeof(ls.v));
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_spatial_desc(st, (const SpatialDescJob*)(base + off), nj, mx, base, ls); });
-      spatialDescJobs.clear();
-    }
-    if (!spatialWorks.empty()) {   // all spatial panners of the level: one launch
-      size_t off = plan.putv(spatialWorks);
-      int nw = (int)spatialWorks.size();
-      hipStream_t st = c.stream;
-      c.noteKernel(LK_OTHER, "spatial_panner_kernel");
-      plan.add(LK_OTHER, [this, st, off, nw](uint8_t* base) {
-        launch_spatial_panner(st, (const SpatialWork*)(base + off), nw, (const SpatialJob*)(base + spatialJobsOff), base);
-      }, 0.0, 2.0 * spatialFma);
-      spatialWorks.clear();
-      spatialFma = 0;
-    }
-    if (!delayJobs.empty()) {   // after the mix jobs of this level, which append the input to the delay lines
-      size_t off = plan.putv(delayJobs);
-      int nj = (int)delayJobs.size();
-      int64_t mx = 0;
-      for (auto& j : delayJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_delay(st, (const DelayJob*)(base + off), nj, mx); });
-    }
-    if (!gainJobs.empty()) {
-      size_t off = plan.putv(gainJobs);
-      int nj = (int)gainJobs.size();
-      int64_t mx = 0;
-      for (auto& j : gainJobs) mx = std::max(mx, j.n);
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_gain(st, (const GainJob*)(base + off), nj, mx); });
-    }
-    {
+    flush(wideJobs, LK_MIX, &MixJob::n, [=](const MixJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_mix_wide(st, t, nj, termTable(base), mx, gainTable(base), curveTable(base));
+    }, mixBytes(wideJobs));
+    const bool v4 = mixAligned;
+    flush(mixJobs, LK_MIX, &MixJob::n, [=](const MixJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_mix(st, t, nj, termTable(base), mx, v4, gainTable(base), curveTable(base));
+    }, mixBytes(mixJobs));
+    // after the mixes (the modulation inputs), before the nodes that read the parameter
+    flush(pmodJobs, LK_OTHER, &ParamModJob::n, [=](const ParamModJob* t, int nj, int64_t mx, uint8_t*) { launch_param_mod(st, t, nj, mx); });
+    flush(loopJobs, LK_OTHER, &LoopJob::n, [=](const LoopJob* t, int nj, int64_t mx, uint8_t*) { launch_loop_source(st, t, nj, mx); });
+    // (the trajectory table is put when the chunk's tables are complete: its offset is read when the launch runs -- chunkExecute)
+    flush(rsJobs, LK_OTHER, &ResampleJob::nblocks, [this, st](const ResampleJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_resample(st, t, nj, (const ResampleBlock*)(base + trajOffFinal), mx);
+    });
+    flush(rsFastJobs, LK_OTHER, &ResampleFastJob::nblocks, [=](const ResampleFastJob* t, int nj, int64_t mx, uint8_t*) { launch_resample_fast(st, t, nj, mx); });
+    flush(gsrJobs, LK_OTHER, &GsrJob::nblocks, [=](const GsrJob* t, int nj, int64_t mx, uint8_t* base) { launch_gsr(st, t, nj, base, mx); });
+    flush(streamJobs, LK_OTHER, &StreamJob::nblocks, [=](const StreamJob* t, int nj, int64_t mx, uint8_t* base) { launch_stream(st, t, nj, base, mx); });
+    flush(constJobs, LK_OTHER, &ConstJob::n, [=](const ConstJob* t, int nj, int64_t mx, uint8_t*) { launch_const_source(st, t, nj, mx); });
+    bool anyCurve = false;
+    for (auto& j : oscJobs) anyCurve = anyCurve || j.curve != nullptr;
+    flush(oscJobs, LK_OTHER, nullptr, [=](const OscJob* t, int nj, int64_t, uint8_t*) { launch_oscillator(st, t, nj, anyCurve); });
+    flush(panJobs, LK_OTHER, &PanJob::n, [=](const PanJob* t, int nj, int64_t mx, uint8_t*) { launch_stereo_panner(st, t, nj, mx); });
+    flush(panDynJobs, LK_OTHER, nullptr, [=](const PanDynJob* t, int nj, int64_t, uint8_t*) { launch_stereo_panner_dynamic(st, t, nj); });
+    // the descriptors of the level's signal-driven spatial panners: after the mixes, before the panners
+    SpatialListener ls;
+    std::memcpy(ls.v, c.listener, sizeof(ls.v));
+    flush(spatialDescJobs, LK_OTHER, &SpatialDescJob::nb, [=](const SpatialDescJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_spatial_desc(st, t, nj, (int)mx, base, ls);
+    });
+    // all spatial panners of the level: one launch (the job table is put when the chunk's tables are complete: chunkExecute)
+    if (!spatialWorks.empty()) c.noteKernel(LK_OTHER, "spatial_panner_kernel");
+    flush(spatialWorks, LK_OTHER, nullptr, [this, st](const SpatialWork* t, int nw, int64_t, uint8_t* base) {
+      launch_spatial_panner(st, t, nw, (const SpatialJob*)(base + spatialJobsOff), base);
+    }, 0.0, 2.0 * spatialFma);
+    spatialFma = 0;
+    // after the mix jobs of this level, which append the input to the delay lines
+    flush(delayJobs, LK_OTHER, &DelayJob::n, [=](const DelayJob* t, int nj, int64_t mx, uint8_t*) { launch_delay(st, t, nj, mx); });
+    flush(gainJobs, LK_OTHER, &GainJob::n, [=](const GainJob* t, int nj, int64_t mx, uint8_t*) { launch_gain(st, t, nj, mx); });
+    {   // the biquad queues (one per cascade length) share one section table
       bool any = false;
       for (int k = 1; k <= kMaxBiquadSections; k++) any = any || !bqJobs[k].empty();
       if (any) {
-        size_t soff = plan.putv(bqSecs);
-        for (int k = 1; k <= kMaxBiquadSections; k++) {
-          if (bqJobs[k].empty()) continue;
-          size_t off = plan.putv(bqJobs[k]);
-          int nj = (int)bqJobs[k].size();
-          hipStream_t st = c.stream;
-          plan.add(LK_OTHER, [=](uint8_t* base) {
-            launch_biquad(st, (const BiquadJob*)(base + off), nj, (const BiquadSection*)(base + soff), k);
+        const size_t soff = plan.putv(bqSecs);
+        for (int k = 1; k <= kMaxBiquadSections; k++)
+          flush(bqJobs[k], LK_OTHER, nullptr, [=](const BiquadJob* t, int nj, int64_t, uint8_t* base) {
+            launch_biquad(st, t, nj, (const BiquadSection*)(base + soff), k);
           });
-        }
       }
     }
     if (bqG > 1) {   // cascades split along time: expand the pieces, zero their states, pass A, scan, pass B
       const size_t soff = plan.putv(bqSecs);
-      hipStream_t st = c.stream;
       Context* cp = &c;
       const int G = bqG;
       const int64_t K = bqK;
@@ -1052,41 +952,15 @@ struct Exec {
       bqG = 0;
       bqK = 0;
     }
-    if (!bqDynJobs.empty()) {
-      size_t off = plan.putv(bqDynJobs);
-      int nj = (int)bqDynJobs.size();
-      hipStream_t st = c.stream;
-      plan.add(LK_OTHER, [=](uint8_t* base) { launch_biquad_dynamic(st, (const BiquadDynJob*)(base + off), nj); });
-    }
-    bqDynJobs.clear();
+    flush(bqDynJobs, LK_OTHER, nullptr, [=](const BiquadDynJob* t, int nj, int64_t, uint8_t*) { launch_biquad_dynamic(st, t, nj); });
+    // what is left are tables, not queues
+    bqSecs.clear();
     terms.clear();
     termGains.clear();
     termCurves.clear();
     anyTermGain = anyTermCurve = false;
-    mixJobs.clear();
-    dmJobs.clear();
-    gainJobs.clear();
-    for (auto& v : bqJobs) v.clear();
-    bqSecs.clear();
-    loopJobs.clear();
-    rsJobs.clear();
-    rsFastJobs.clear();
-    gsrJobs.clear();
-    streamJobs.clear();
-    constJobs.clear();
-    oscJobs.clear();
-    panJobs.clear();
-    delayJobs.clear();
-    panDynJobs.clear();
-    pmodJobs.clear();
     mixAligned = true;
   }
-  struct RsLaunch {
-    size_t off;
-    int nj;
-    int64_t mx;
-  };
-  std::vector<RsLaunch> rsLaunches;
   size_t trajOffFinal = 0;
 };
 

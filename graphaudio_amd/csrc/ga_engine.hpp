@@ -199,9 +199,6 @@ struct NodeS {
   PanState* panDev = nullptr;      // device copy of the three, authoritative while pan is automated (panOnDevice)
   bool panOnDevice = false;
   uint64_t bqDynSeq = ~0ull, panDynSeq = ~0ull;   // (chunk in which the node ran its per-sample kernel: Context::chunkSeq)
-  bool bqDynChunk_unused = false;         // the same for a biquad whose parameter modulation falls silent inside a chunk (coefficient state on the device)
-  bool panDynChunk_unused = false;        // (control plane) evaluated by the dynamic kernel in an earlier segment of THIS chunk: the gains in force live on the
-                                   // device until the chunk ends, so the rest of the chunk stays on that kernel (a modulation input that falls silent)
   // DelayNode (DelayNode.cs:13-15)
   int maxDelaySamples = 0;
   int delayCh = 0;                 // channels of `_outputBuffer` (re-rented, i.e. silent again, when the count changes)

@@ -2669,6 +2669,17 @@ void launch_loop_source(hipStream_t s, const LoopJob* jobs_dev, int njobs, int64
 //  outputs of its block with exactly the reference's per-sample arithmetic.  64 consecutive blocks of one job per
 //  wavefront; outputs go through LDS so the HBM stores are coalesced.
 // =====================================================================================================
+// CubicResampler.cs:52-57, the reference's expression tree (the build has -ffp-contract=off: the tree is the result)
+__device__ __forceinline__ float cubic_interp(float S0, float S1, float S2, float S3, float t) {
+  return S1 + t * (0.5f * (S2 - S0) + t * ((S0 - 2.5f * S1 + 2.f * S2 - 0.5f * S3) + t * (0.5f * (S3 - S0) + 1.5f * (S1 - S2))));
+}
+// the tile of a workgroup (one row per lane's block) -> `nb` consecutive blocks of `out`, coalesced
+__device__ __forceinline__ void store_tile(const float (&tile)[64][kBlock + 1], GA_GLOBAL float* __restrict out, int nb, int lane) {
+  for (int r = 0; r < nb; r++) {
+    out[(int64_t)r * kBlock + lane] = tile[r][lane];
+    out[(int64_t)r * kBlock + 64 + lane] = tile[r][64 + lane];
+  }
+}
 __global__ __launch_bounds__(64) void resample_kernel(const ResampleJob* __restrict jobs, const ResampleBlock* __restrict traj) {
   __shared__ float tile[64][kBlock + 1];
   const ResampleJob job = jobs[blockIdx.y];
@@ -2700,7 +2711,7 @@ __global__ __launch_bounds__(64) void resample_kernel(const ResampleJob* __restr
         for (int i = 0; i < consume; i++) { S0 = S1; S1 = S2; S2 = S3; S3 = in[ip++]; }
         Pos -= consume;
         float t = (float)Pos;
-        tile[lane][outp] = S1 + t * (0.5f * (S2 - S0) + t * ((S0 - 2.5f * S1 + 2.f * S2 - 0.5f * S3) + t * (0.5f * (S3 - S0) + 1.5f * (S1 - S2))));
+        tile[lane][outp] = cubic_interp(S0, S1, S2, S3, t);
         Pos += job.rate;
       }
     }
@@ -2709,10 +2720,7 @@ __global__ __launch_bounds__(64) void resample_kernel(const ResampleJob* __restr
   __syncthreads();
   const int nb = (int)min<int64_t>(64, job.nblocks - bl0);
   GA_GLOBAL float* __restrict out = gptr(job.out) + (job.b0 + bl0) * kBlock;
-  for (int r = 0; r < nb; r++) {
-    out[(int64_t)r * kBlock + lane] = tile[r][lane];
-    out[(int64_t)r * kBlock + 64 + lane] = tile[r][64 + lane];
-  }
+  store_tile(tile, out, nb, lane);
 }
 __global__ __launch_bounds__(256) void resample_fast_kernel(const ResampleFastJob* __restrict jobs) {
   const ResampleFastJob job = jobs[blockIdx.y];
@@ -2725,8 +2733,7 @@ __global__ __launch_bounds__(256) void resample_fast_kernel(const ResampleFastJo
     const GA_GLOBAL float* __restrict w = in + (int64_t)__float_as_uint(e.x) - 4;
     const float S0 = w[0], S1 = w[1], S2 = w[2], S3 = w[3];
     const float t = e.y;
-    // CubicResampler.cs:52-57, the reference's expression tree
-    out[i] = S1 + t * (0.5f * (S2 - S0) + t * ((S0 - 2.5f * S1 + 2.f * S2 - 0.5f * S3) + t * (0.5f * (S3 - S0) + 1.5f * (S1 - S2))));
+    out[i] = cubic_interp(S0, S1, S2, S3, t);
   }
 }
 void launch_resample_fast(hipStream_t s, const ResampleFastJob* jobs_dev, int njobs, int64_t max_blocks) {
@@ -2784,7 +2791,7 @@ __global__ __launch_bounds__(64) void gsr_kernel(const GsrJob* __restrict jobs, 
           for (int i = 0; i < consume; i++) { S0 = S1; S1 = S2; S2 = S3; S3 = feed(); }
           Pos -= consume;
           float t = (float)Pos;
-          tile[lane][outp] = S1 + t * (0.5f * (S2 - S0) + t * ((S0 - 2.5f * S1 + 2.f * S2 - 0.5f * S3) + t * (0.5f * (S3 - S0) + 1.5f * (S1 - S2))));
+          tile[lane][outp] = cubic_interp(S0, S1, S2, S3, t);
           Pos += d.rate;
         }
       }
@@ -2794,10 +2801,7 @@ __global__ __launch_bounds__(64) void gsr_kernel(const GsrJob* __restrict jobs, 
   __syncthreads();
   const int nb = (int)min<int64_t>(64, job.nblocks - bl0);
   GA_GLOBAL float* __restrict out = gptr(job.out) + (job.b0 + bl0) * kBlock;
-  for (int r = 0; r < nb; r++) {
-    out[(int64_t)r * kBlock + lane] = tile[r][lane];
-    out[(int64_t)r * kBlock + 64 + lane] = tile[r][64 + lane];
-  }
+  store_tile(tile, out, nb, lane);
 }
 void launch_gsr(hipStream_t s, const GsrJob* jobs_dev, int njobs, const uint8_t* plan_base_dev, int64_t max_blocks) {
   if (njobs <= 0 || max_blocks <= 0) return;
@@ -2929,7 +2933,7 @@ __global__ __launch_bounds__(64) void stream_kernel(const StreamJob* __restrict 
             for (int i = 0; i < consume; i++) { S0 = S1; S1 = S2; S2 = S3; S3 = in[ip++]; }
             Pos -= consume;
             float t = (float)Pos;
-            tile[lane][outp] = S1 + t * (0.5f * (S2 - S0) + t * ((S0 - 2.5f * S1 + 2.f * S2 - 0.5f * S3) + t * (0.5f * (S3 - S0) + 1.5f * (S1 - S2))));
+            tile[lane][outp] = cubic_interp(S0, S1, S2, S3, t);
             Pos += d.rate;
           }
         }
@@ -2939,10 +2943,7 @@ __global__ __launch_bounds__(64) void stream_kernel(const StreamJob* __restrict 
   __syncthreads();
   const int nb = (int)min<int64_t>(64, job.nblocks - bl0);
   GA_GLOBAL float* __restrict out = gptr(job.out) + (job.b0 + bl0) * kBlock;
-  for (int r = 0; r < nb; r++) {
-    out[(int64_t)r * kBlock + lane] = tile[r][lane];
-    out[(int64_t)r * kBlock + 64 + lane] = tile[r][64 + lane];
-  }
+  store_tile(tile, out, nb, lane);
   if (job.win_out && blockIdx.x == 0 && lane < 4) gptr(job.win_out)[lane] = sample(job.wend_seg[lane], job.wend[lane]);
 }
 void launch_stream(hipStream_t s, const StreamJob* jobs_dev, int njobs, const uint8_t* plan_base_dev, int64_t max_blocks) {

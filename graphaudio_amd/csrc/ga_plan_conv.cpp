@@ -837,16 +837,9 @@ void Context::aliasBusToLeader(ChunkRun& r) {
 
 // pass 5: convolver formulations of new nodes, fusion groups, scratch arenas (sized before any recorded launch captures them)
 void Context::chunkConvScratch(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
   std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  int64_t& n = r.n;
+  int& bHistMax = r.bHistMax;
   // resampler trajectories used in this chunk go into one device table
   for (auto& kv : resamplers) kv.second->devOffset = -1;
 
@@ -859,7 +852,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
       NodeS& nd = *nodes[id];
       if (nd.type == GA_NODE_CONVOLVER) nd.refOrder = nd.refSens && nd.ir && (nd.convPath == 2 || nd.convPath == 3);
     }
-    planCoarseFusion(topo, segs);
+    planCoarseFusion(topo, r.segs);
     for (int id : topo)
       if (nodes[id]->type == GA_NODE_CONVOLVER) nodes[id]->dGroupSize = 0;
     for (int id : topo) {
@@ -965,19 +958,10 @@ void Context::chunkConvScratch(ChunkRun& r) {
 
 // formulation A: convolvers that share an impulse-response channel run as one group per (impulse response, channel) -- the
 // banded-Toeplitz matrix-core kernel or the block-axis transforms over all their rows (PartitionedConvolver.cs:104-223)
-void Context::planConvolversShared(ChunkRun& r, int d, ConvPlanCtx& k) {
-  Context& c_ = *this; (void)c_;
-  std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
+  int64_t& n = r.n;
+  std::vector<Segment>& segs = r.segs;
   Exec& ex = *r.ex;
-  (void)d; (void)topo;
   auto& active = k.active; auto& tsTemps = k.tsTemps; auto& prevIns = k.prevIns; int& prevP = k.prevP; int& prevRp = k.prevRp; int& prevRows = k.prevRows;
   for (auto& kv : active) {
     ConvGroup& g = *kv.first;
@@ -1085,21 +1069,12 @@ void Context::planConvolversShared(ChunkRun& r, int d, ConvPlanCtx& k) {
 }
 
 // formulations B / C: nodes with an impulse response of their own (per-node planes; block-axis FFT segments or the direct sum)
-void Context::planConvolversPrivate(ChunkRun& r, int d, ConvPlanCtx& k, bool refOrder) {
-  Context& c_ = *this; (void)c_;
-  std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+void Context::planConvolversPrivate(ChunkRun& r, int /*d*/, ConvPlanCtx& k, bool refOrder) {
+  int64_t& n = r.n;
+  std::vector<Segment>& segs = r.segs;
   Exec& ex = *r.ex;
-  (void)d; (void)topo;
   const std::vector<int>& bNodes = k.bNodes; auto& tsTemps = k.tsTemps;
-  const int hist = (int)roundup(bHistMax, 4);   // plane time origin, 16-byte aligned rows
+  const int hist = (int)roundup(r.bHistMax, 4);   // plane time origin, 16-byte aligned rows
   const int txb = hist + (int)roundup(n, 16) + 16, tyb = (int)roundup(n, 256);
   // rows of this depth start after the rows of the depths before it: a node's spectra stay intact for the next chunk
   const size_t rowX0 = bRowX, rowY0 = bRowY;
@@ -1349,66 +1324,56 @@ void Context::planConvolversPrivate(ChunkRun& r, int d, ConvPlanCtx& k, bool ref
 
 // pass 7 (per convolver depth d): the convolvers whose inputs are complete, once per chunk over all blocks
 void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
-  Context& c_ = *this; (void)c_;
-  std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
   Exec& ex = *r.ex;
-    // ---- convolvers whose inputs are complete (depth d): once per chunk over all blocks ----
-    // group -> (node, slot); ordered by (IR buffer, IR channel) so groups fed by the same inputs are adjacent
-    ConvPlanCtx k;
-    auto& active = k.active;
-    std::vector<int>& bNodes = k.bNodes;  // formulation B / C nodes of this depth
-    std::vector<int>& dNodes = k.dNodes;  // formulation D nodes of this depth
-    for (int id : topo) {
-      NodeS& nd = *nodes[id];
-      if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.depth != d) continue;
-      if (!ex.convIn.has(id)) continue;
-      if (nd.convPath == 4) {
-        dNodes.push_back(id);
-        continue;
-      }
-      if (nd.convPath >= 2) {
-        bNodes.push_back(id);
-        continue;
-      }
-      for (int slot = 0; slot < (int)nd.convRows.size(); slot++) active[nd.convRows[slot].group].push_back({id, slot});
+  // ---- convolvers whose inputs are complete (depth d): once per chunk over all blocks ----
+  // group -> (node, slot); ordered by (IR buffer, IR channel) so groups fed by the same inputs are adjacent
+  ConvPlanCtx k;
+  auto& active = k.active;
+  std::vector<int>& bNodes = k.bNodes;  // formulation B / C nodes of this depth
+  std::vector<int>& dNodes = k.dNodes;  // formulation D nodes of this depth
+  for (int id : r.topo) {
+    NodeS& nd = *nodes[id];
+    if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.depth != d) continue;
+    if (!ex.convIn.has(id)) continue;
+    if (nd.convPath == 4) {
+      dNodes.push_back(id);
+      continue;
     }
-    if (!active.empty()) planConvolversShared(r, d, k);
-    // ---- formulation D: coarse partitions, consumer sums fused in the frequency domain ----
-    if (!dNodes.empty()) planCoarseStage(*this, ex, dNodes, n);
-    // ---- formulations B / C: nodes with a private impulse response ----
-    // (those that this chunk evaluates in the reference's own order -- formulation R -- in a pass of their own: double-precision
-    // transforms and launch_refmac instead of the matrix-core / block-axis-FFT partition sums)
-    if (!bNodes.empty()) {
-      std::vector<int> plain, ref;
-      for (int id : bNodes) (nodes[id]->refOrder ? ref : plain).push_back(id);
-      if (!plain.empty()) {
-        bNodes = plain;
-        planConvolversPrivate(r, d, k, false);
-      }
-      if (!ref.empty()) {
-        bNodes = ref;
-        planConvolversPrivate(r, d, k, true);
-      }
+    if (nd.convPath >= 2) {
+      bNodes.push_back(id);
+      continue;
     }
-    auto& tsTemps = k.tsTemps;
-    // true stereo: outL = conv0(L) + conv2(R) ; outR = conv1(L) + conv3(R)  (ConvolverNode.cs:127-144)
-    for (auto& kv : tsTemps) {
-      hipStream_t st = stream;
-      int64_t fr = frames;
-      for (int o = 0; o < 2; o++) {
-        float* out = ex.nodeOut(kv.first, o);
-        float *a = kv.second[o], *b2 = kv.second[o + 2];
-        if (a && b2) ex.plan.add(LK_OTHER, [=](uint8_t*) { launch_pair_sum(st, out, a, b2, fr); });
-      }
+    for (int slot = 0; slot < (int)nd.convRows.size(); slot++) active[nd.convRows[slot].group].push_back({id, slot});
+  }
+  if (!active.empty()) planConvolversShared(r, d, k);
+  // ---- formulation D: coarse partitions, consumer sums fused in the frequency domain ----
+  if (!dNodes.empty()) planCoarseStage(*this, ex, dNodes, r.n);
+  // ---- formulations B / C: nodes with a private impulse response ----
+  // (those that this chunk evaluates in the reference's own order -- formulation R -- in a pass of their own: double-precision
+  // transforms and launch_refmac instead of the matrix-core / block-axis-FFT partition sums)
+  if (!bNodes.empty()) {
+    std::vector<int> plain, ref;
+    for (int id : bNodes) (nodes[id]->refOrder ? ref : plain).push_back(id);
+    if (!plain.empty()) {
+      bNodes = plain;
+      planConvolversPrivate(r, d, k, false);
     }
+    if (!ref.empty()) {
+      bNodes = ref;
+      planConvolversPrivate(r, d, k, true);
+    }
+  }
+  auto& tsTemps = k.tsTemps;
+  // true stereo: outL = conv0(L) + conv2(R) ; outR = conv1(L) + conv3(R)  (ConvolverNode.cs:127-144)
+  for (auto& kv : tsTemps) {
+    hipStream_t st = stream;
+    int64_t fr = r.n * kBlock;
+    for (int o = 0; o < 2; o++) {
+      float* out = ex.nodeOut(kv.first, o);
+      float *a = kv.second[o], *b2 = kv.second[o + 2];
+      if (a && b2) ex.plan.add(LK_OTHER, [=](uint8_t*) { launch_pair_sum(st, out, a, b2, fr); });
+    }
+  }
 }
 
 }  // namespace ga

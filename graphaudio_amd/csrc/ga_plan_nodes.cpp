@@ -6,85 +6,72 @@ namespace ga {
 
 // pass 4: AudioParam timelines -> device curves
 void Context::chunkParamCurves(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
   std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
   Exec& ex = *r.ex;
   // ---- AudioParam curves (AudioParam.cs:93-166) for automated gain params: one launch for the whole chunk ----
-  {
-    // Which parameters of the reachable nodes carry a timeline?  The list stands while no API call, no drained command and no graph
-    // edit happened (apiEpoch / graphVersion): a sweep over the parameter vectors of 28,672 nodes per chunk was 1.5 - 2 ms.
-    if (curveListEpoch != apiEpoch || curveListGraphVersion != graphVersion || curveListTopoSize != topo.size()) {
-      for (auto& e : curveList)   // (curves handed out for the previous list)
-        if (e.first < (int)nodes.size() && nodes[e.first] && e.second < (int)nodes[e.first]->params.size()) nodes[e.first]->params[e.second].curve = nullptr;
-      curveList.clear();
-      for (int id : topo) {
-        NodeS& nd = *nodes[id];
-        for (auto& p : nd.params) p.curve = nullptr;
-        if (nd.type != GA_NODE_GAIN && nd.type != GA_NODE_BIQUAD && nd.type != GA_NODE_CONSTANT_SOURCE && nd.type != GA_NODE_OSCILLATOR &&
-            nd.type != GA_NODE_DELAY && nd.type != GA_NODE_STEREO_PANNER)
-          continue;
-        for (int pi = 0; pi < (int)nd.params.size(); pi++)
-          if (!nd.params[pi].events.empty()) curveList.push_back({id, pi});
-      }
-      curveListEpoch = apiEpoch;
-      curveListGraphVersion = graphVersion;
-      curveListTopoSize = topo.size();
+  // Which parameters of the reachable nodes carry a timeline?  The list stands while no API call, no drained command and no graph
+  // edit happened (apiEpoch / graphVersion): a sweep over the parameter vectors of 28,672 nodes per chunk was 1.5 - 2 ms.
+  if (curveListEpoch != apiEpoch || curveListGraphVersion != graphVersion || curveListTopoSize != topo.size()) {
+    for (auto& e : curveList)   // (curves handed out for the previous list)
+      if (e.first < (int)nodes.size() && nodes[e.first] && e.second < (int)nodes[e.first]->params.size()) nodes[e.first]->params[e.second].curve = nullptr;
+    curveList.clear();
+    for (int id : topo) {
+      NodeS& nd = *nodes[id];
+      for (auto& p : nd.params) p.curve = nullptr;
+      if (nd.type != GA_NODE_GAIN && nd.type != GA_NODE_BIQUAD && nd.type != GA_NODE_CONSTANT_SOURCE && nd.type != GA_NODE_OSCILLATOR &&
+          nd.type != GA_NODE_DELAY && nd.type != GA_NODE_STEREO_PANNER)
+        continue;
+      for (int pi = 0; pi < (int)nd.params.size(); pi++)
+        if (!nd.params[pi].events.empty()) curveList.push_back({id, pi});
     }
-    std::vector<ParamJob> pjobs;
-    std::vector<ParamEvent> events;
-    // identical timelines (same events, value and rate -- e.g. the same fade on every voice) share one curve: hash of the bytes,
-    // verified against the job that owns the curve
-    std::unordered_multimap<uint64_t, int> jobOf;
-    auto sameTimeline = [&](const ParamJob& pj, const ParamS& p) {
-      return pj.nev == (int)p.events.size() && pj.value == p.value && pj.arate == (p.arate ? 1 : 0) &&
-             std::memcmp(&events[pj.ev0], p.events.data(), p.events.size() * sizeof(ParamEvent)) == 0;
-    };
-    for (auto& e : curveList) {
-      ParamS& p = nodes[e.first]->params[e.second];
-      p.curve = nullptr;
-      uint64_t h = 1469598103934665603ull;
-      const uint64_t* w = (const uint64_t*)p.events.data();
-      for (size_t i = 0; i < p.events.size() * sizeof(ParamEvent) / 8; i++) h = (h ^ w[i]) * 1099511628211ull;
-      uint32_t vb;
-      std::memcpy(&vb, &p.value, 4);
-      h = (h ^ vb ^ (p.arate ? 0x100000000ull : 0)) * 1099511628211ull;
-      auto range = jobOf.equal_range(h);
-      for (auto it = range.first; it != range.second && !p.curve; ++it)
-        if (sameTimeline(pjobs[it->second], p)) p.curve = pjobs[it->second].out;
-      if (p.curve) continue;
-      p.curve = getSlab(*this);
-      ParamJob pj;
-      pj.out = p.curve;
-      pj.ev0 = (int)events.size();
-      pj.nev = (int)p.events.size();
-      pj.value = p.value;
-      pj.arate = p.arate ? 1 : 0;
-      pj.b0 = 0;
-      pj.nblocks = n;
-      events.insert(events.end(), p.events.begin(), p.events.end());
-      jobOf.emplace(h, (int)pjobs.size());
-      pjobs.push_back(pj);
-    }
-    if (!pjobs.empty()) {
-      size_t jo = ex.plan.putv(pjobs), eo = ex.plan.putv(events), bo = ex.plan.putv(bt);
-      int nj = (int)pjobs.size();
-      double dt = 1.0 / sampleRate;
-      hipStream_t st = stream;
-      int64_t nn = n;
-      ex.plan.add(LK_OTHER, [=](uint8_t* base) {
-        launch_param_curve(st, (const ParamJob*)(base + jo), nj, (const ParamEvent*)(base + eo), (const double*)(base + bo), dt, nn);
-      });
-    }
+    curveListEpoch = apiEpoch;
+    curveListGraphVersion = graphVersion;
+    curveListTopoSize = topo.size();
   }
-
+  std::vector<ParamJob> pjobs;
+  std::vector<ParamEvent> events;
+  // identical timelines (same events, value and rate -- e.g. the same fade on every voice) share one curve: hash of the bytes,
+  // verified against the job that owns the curve
+  std::unordered_multimap<uint64_t, int> jobOf;
+  auto sameTimeline = [&](const ParamJob& pj, const ParamS& p) {
+    return pj.nev == (int)p.events.size() && pj.value == p.value && pj.arate == (p.arate ? 1 : 0) &&
+           std::memcmp(&events[pj.ev0], p.events.data(), p.events.size() * sizeof(ParamEvent)) == 0;
+  };
+  for (auto& e : curveList) {
+    ParamS& p = nodes[e.first]->params[e.second];
+    p.curve = nullptr;
+    uint64_t h = 1469598103934665603ull;
+    const uint64_t* w = (const uint64_t*)p.events.data();
+    for (size_t i = 0; i < p.events.size() * sizeof(ParamEvent) / 8; i++) h = (h ^ w[i]) * 1099511628211ull;
+    uint32_t vb;
+    std::memcpy(&vb, &p.value, 4);
+    h = (h ^ vb ^ (p.arate ? 0x100000000ull : 0)) * 1099511628211ull;
+    auto range = jobOf.equal_range(h);
+    for (auto it = range.first; it != range.second && !p.curve; ++it)
+      if (sameTimeline(pjobs[it->second], p)) p.curve = pjobs[it->second].out;
+    if (p.curve) continue;
+    p.curve = getSlab(*this);
+    ParamJob pj;
+    pj.out = p.curve;
+    pj.ev0 = (int)events.size();
+    pj.nev = (int)p.events.size();
+    pj.value = p.value;
+    pj.arate = p.arate ? 1 : 0;
+    pj.b0 = 0;
+    pj.nblocks = r.n;
+    events.insert(events.end(), p.events.begin(), p.events.end());
+    jobOf.emplace(h, (int)pjobs.size());
+    pjobs.push_back(pj);
+  }
+  if (!pjobs.empty()) {
+    size_t eo = ex.plan.putv(events), bo = ex.plan.putv(r.bt);
+    double dt = 1.0 / sampleRate;
+    hipStream_t st = stream;
+    int64_t nn = r.n;
+    ex.flush(pjobs, LK_OTHER, nullptr, [=](const ParamJob* t, int nj, int64_t, uint8_t* base) {
+      launch_param_curve(st, t, nj, (const ParamEvent*)(base + eo), (const double*)(base + bo), dt, nn);
+    });
+  }
 }
 
 void Context::ensureBiquadState(NodeS& bn) {
@@ -104,8 +91,8 @@ void Context::ensureBiquadState(NodeS& bn) {
 
 // ConstantSourceNode.Process (ConstantSourceNode.cs:76-141)
 void Context::planConstantSource(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf;
   if (ns.srcPhase != SRC_PLAY) return;
   ConstJob cj;
   cj.curve = ex.paramView((int)si, ns, 0);
@@ -122,8 +109,8 @@ void Context::planConstantSource(NodePlanCtx& k) {
 
 // OscillatorNode.Process (OscillatorNode.cs:91-196)
 void Context::planOscillator(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf;
   if (ns.srcPhase != SRC_PLAY) return;
   OscJob oj;
   oj.curve = ex.paramView((int)si, ns, 0);
@@ -143,8 +130,8 @@ void Context::planOscillator(NodePlanCtx& k) {
 
 // DelayNode.Process (DelayNode.cs:43-100): the segment's input appended to the rings, then a gather
 void Context::planDelay(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf;
   const int ch = ns.ins[0].bufCh;
   const int maxD = nd.maxDelaySamples;
   const size_t pitch = (size_t)maxD + (size_t)nd.delayCap;
@@ -213,8 +200,8 @@ void Context::planDelay(NodePlanCtx& k) {
 
 // StereoPannerNode.Process (StereoPannerNode.cs:36-153)
 void Context::planStereoPanner(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf;
   if (ns.ins[0].silent) return;   // cleared 2-channel output (:49-54)
   auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
   if (ns.panDyn) {
@@ -473,8 +460,8 @@ bool Context::ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto) {
 
 // AudioBufferSourceNode.Process (AudioBufferSourceNode.cs:150-260): zero-copy windows, loop walks, resampler jobs, general replay
 void Context::planBufferSource(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb;
   const std::vector<int>& srcIds = k.r.srcIds; const std::vector<SrcPlanOut>& srcPlans = k.r.srcPlans;
   if (ns.srcPhase != SRC_PLAY) return;  // silent: ZERO views
   PlayBuf& pb = *buffers[ns.srcBuf];
@@ -579,8 +566,8 @@ void Context::planBufferSource(NodePlanCtx& k) {
 
 // AudioStreamSourceNodeBase.Process (AudioStreamSourceNodeBase.cs:132-301), replayed by the host (streamReplay)
 void Context::planStreamSource(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t nb = k.nb;
   if (ns.outSilent) return;   // ProduceSilence / nothing rendered: cleared buffer
   if (!nd.stUploaded) {
     nd.stBlocksOff = ex.plan.putv(nd.stBlocks);
@@ -616,8 +603,8 @@ void Context::planStreamSource(NodePlanCtx& k) {
 
 // GainNode.Process (GainNode.cs:36-80)
 void Context::planGain(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  const int64_t f0 = k.f0, nf = k.nf;
   const float* gmod = nullptr;   // audio-rate modulation of gain: mixed to 1 channel (AudioParam.cs:68-70,123-135)
   if (!ns.pins.empty() && !ns.pins[0].silent) gmod = ex.resolveInSeg((int)si, ns.id, -1, ns.pins[0], false, nullptr)[0];
   auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
@@ -665,7 +652,7 @@ void Context::planGain(NodePlanCtx& k) {
 // BiQuadFilterNode.Process (BiQuadFilterNode.cs:96-143): automated parameters, fused constant-coefficient cascades, cascades split along time
 void Context::planBiquad(NodePlanCtx& k) {
   Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
-  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb; (void)si; (void)sg; (void)nb; (void)nd; (void)f0; (void)nf;
+  const int64_t f0 = k.f0, nf = k.nf, nb = k.nb;
   const DenseSeg& segNode = k.segNode; const DenseInt& absorbedBy = k.absorbedBy; const int levelBqHeads = k.levelBqHeads;
   if (!ns.bqActive) {  // silent input: cleared output, state frozen (BiQuadFilterNode.cs:103-108)
     ex.resolveInput((int)si, ns, 0, false, nullptr);
@@ -796,177 +783,169 @@ void Context::planBiquad(NodePlanCtx& k) {
 
 // pass 6 (per convolver depth d): every segment, level by level -- node launches are batched per (level, type)
 void Context::chunkPlanNodes(ChunkRun& r, int d) {
-  Context& c_ = *this; (void)c_;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
+  int& maxLevel = r.maxLevel;
   Exec& ex = *r.ex;
-    for (size_t si = 0; si < segs.size(); si++) {
-      Segment& sg = segs[si];
-      if (ex.outViews[si].empty()) {
-        if (!viewsPool.empty()) {
-          ex.outViews[si] = std::move(viewsPool.back());
-          viewsPool.pop_back();
-          for (Views& v : ex.outViews[si]) v.clear();
-        }
-        ex.outViews[si].resize(nodes.size());
+  for (size_t si = 0; si < r.segs.size(); si++) {
+    Segment& sg = r.segs[si];
+    if (ex.outViews[si].empty()) {
+      if (!viewsPool.empty()) {
+        ex.outViews[si] = std::move(viewsPool.back());
+        viewsPool.pop_back();
+        for (Views& v : ex.outViews[si]) v.clear();
       }
-      const int64_t f0 = sg.b0 * kBlock, nf = (sg.b1 - sg.b0) * kBlock, nb = sg.b1 - sg.b0;
-      // nodes of this stage ordered by level
-      // (a stable counting sort: with tens of thousands of nodes a comparison sort that chases two node pointers per comparison
-      // was a quarter of the host time of a chunk)
-      std::vector<const NodeSeg*> todo;
-      {
-        std::vector<std::pair<int, const NodeSeg*>> mine;
-        std::vector<int> count(maxLevel + 2, 0);
-        for (const NodeSeg& ns : sg.nodes) {
-          if (ns.depth != d) continue;
-          const int lv = std::min(std::max((int)ns.level, 0), maxLevel);
-          mine.push_back({lv, &ns});
-          count[lv + 1]++;
-        }
-        for (int lv = 0; lv <= maxLevel; lv++) count[lv + 1] += count[lv];
-        todo.resize(mine.size());
-        for (auto& m : mine) todo[count[m.first]++] = m.second;
+      ex.outViews[si].resize(nodes.size());
+    }
+    const int64_t f0 = sg.b0 * kBlock, nf = (sg.b1 - sg.b0) * kBlock, nb = sg.b1 - sg.b0;
+    // nodes of this stage ordered by level
+    // (a stable counting sort: with tens of thousands of nodes a comparison sort that chases two node pointers per comparison
+    // was a quarter of the host time of a chunk)
+    std::vector<const NodeSeg*> todo;
+    {
+      std::vector<std::pair<int, const NodeSeg*>> mine;
+      std::vector<int> count(maxLevel + 2, 0);
+      for (const NodeSeg& ns : sg.nodes) {
+        if (ns.depth != d) continue;
+        const int lv = std::min(std::max((int)ns.level, 0), maxLevel);
+        mine.push_back({lv, &ns});
+        count[lv + 1]++;
       }
-      // biquad cascade fusion: A is absorbed by B when B's only input term is A, A's only consumer is B and both run
-      // (non-silent) with the same channel count; chains are capped at kMaxBiquadSections
-      // (dense tables indexed by node id, validated by a per-(stage, segment) stamp: no hashing on the per-node path)
-      if (fuseStamp.size() < nodes.size()) {
-        fuseStamp.assign(nodes.size(), 0);
-        fuseSeg.assign(nodes.size(), nullptr);
-        fuseAbs.assign(nodes.size(), -1);
-        fuseLen.assign(nodes.size(), 0);
-      }
-      const uint32_t stamp = ++fuseEpoch;
-      DenseSeg segNode{fuseStamp, fuseSeg, stamp};
-      for (const NodeSeg* nsp : todo) {
-        fuseStamp[nsp->id] = stamp;
-        fuseSeg[nsp->id] = nsp;
-        fuseAbs[nsp->id] = -1;
-        fuseLen[nsp->id] = 0;
-      }
-      DenseInt absorbedBy{fuseStamp, fuseAbs, stamp, -1}, chainLen{fuseStamp, fuseLen, stamp, 0};
-      for (const NodeSeg* nsp : todo) {
-        const NodeSeg& b_ = *nsp;
-        if (b_.type != GA_NODE_BIQUAD || !b_.bqActive || b_.bqDynamic) continue;
-        fuseLen[b_.id] = 1;
-        if (b_.ins[0].terms.size() != 1) continue;
-        const TermS& t = b_.ins[0].terms[0];
-        const NodeSeg* ia = segNode.find(t.node);
-        if (!ia) continue;
-        const NodeSeg& a_ = *ia;
-        if (a_.type != GA_NODE_BIQUAD || !a_.bqActive || a_.bqDynamic || t.ch != b_.ins[0].bufCh || a_.outCh != b_.outCh) continue;
-        if (!a_.fan1) continue;
-        int la_ = chainLen.get(a_.id) ? chainLen.get(a_.id) : 1;
-        if (la_ >= kMaxBiquadSections) continue;
-        fuseAbs[a_.id] = b_.id;
-        fuseLen[b_.id] = la_ + 1;
-      }
-      int curLevel = -1, levelBqHeads = 0;
-      if (d == 0 && topoHasCycles && cycleBlocks > 1) {   // the readers of the DelayNodes at which this chunk's loops are cut: sources
-        for (const NodeSeg& ns : sg.nodes) {
-          NodeS& nd = *nodes[ns.id];
-          if (nd.type != GA_NODE_DELAY || !nd.delaySplit) continue;
-          auto& ov = ex.outViews[si][ns.id];
-          ov.assign(std::max(ns.outCh, 1), nullptr);
-          NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, 0};
-          k.delayPhase = 1;
-          planDelay(k);
-        }
-        ex.flushLevel();
-      }
-      for (size_t ti = 0; ti < todo.size(); ti++) {
-        const NodeSeg* nsp = todo[ti];
-        if (ti + 4 < todo.size()) {   // (the sweep is bound by cache misses on the node records)
-          const char* nx = (const char*)nodes[todo[ti + 4]->id].get();
-          __builtin_prefetch(nx);
-          __builtin_prefetch(nx + 64);
-          __builtin_prefetch(nx + 128);
-        }
-        const NodeSeg& ns = *nsp;
+      for (int lv = 0; lv <= maxLevel; lv++) count[lv + 1] += count[lv];
+      todo.resize(mine.size());
+      for (auto& m : mine) todo[count[m.first]++] = m.second;
+    }
+    // biquad cascade fusion: A is absorbed by B when B's only input term is A, A's only consumer is B and both run
+    // (non-silent) with the same channel count; chains are capped at kMaxBiquadSections
+    // (dense tables indexed by node id, validated by a per-(stage, segment) stamp: no hashing on the per-node path)
+    if (fuseStamp.size() < nodes.size()) {
+      fuseStamp.assign(nodes.size(), 0);
+      fuseSeg.assign(nodes.size(), nullptr);
+      fuseAbs.assign(nodes.size(), -1);
+      fuseLen.assign(nodes.size(), 0);
+    }
+    const uint32_t stamp = ++fuseEpoch;
+    DenseSeg segNode{fuseStamp, fuseSeg, stamp};
+    for (const NodeSeg* nsp : todo) {
+      fuseStamp[nsp->id] = stamp;
+      fuseSeg[nsp->id] = nsp;
+      fuseAbs[nsp->id] = -1;
+      fuseLen[nsp->id] = 0;
+    }
+    DenseInt absorbedBy{fuseStamp, fuseAbs, stamp, -1}, chainLen{fuseStamp, fuseLen, stamp, 0};
+    for (const NodeSeg* nsp : todo) {
+      const NodeSeg& b_ = *nsp;
+      if (b_.type != GA_NODE_BIQUAD || !b_.bqActive || b_.bqDynamic) continue;
+      fuseLen[b_.id] = 1;
+      if (b_.ins[0].terms.size() != 1) continue;
+      const TermS& t = b_.ins[0].terms[0];
+      const NodeSeg* ia = segNode.find(t.node);
+      if (!ia) continue;
+      const NodeSeg& a_ = *ia;
+      if (a_.type != GA_NODE_BIQUAD || !a_.bqActive || a_.bqDynamic || t.ch != b_.ins[0].bufCh || a_.outCh != b_.outCh) continue;
+      if (!a_.fan1) continue;
+      int la_ = chainLen.get(a_.id) ? chainLen.get(a_.id) : 1;
+      if (la_ >= kMaxBiquadSections) continue;
+      fuseAbs[a_.id] = b_.id;
+      fuseLen[b_.id] = la_ + 1;
+    }
+    int curLevel = -1, levelBqHeads = 0;
+    if (d == 0 && topoHasCycles && cycleBlocks > 1) {   // the readers of the DelayNodes at which this chunk's loops are cut: sources
+      for (const NodeSeg& ns : sg.nodes) {
         NodeS& nd = *nodes[ns.id];
-        if (ns.level != curLevel) {
-          ex.flushLevel();
-          curLevel = ns.level;
-          levelBqHeads = 0;   // constant-coefficient cascade outputs of this level (all levels' biquad launches are separate)
-          for (size_t tj = ti; tj < todo.size() && todo[tj]->level == curLevel; tj++) {
-            const NodeSeg& o = *todo[tj];
-            if (o.type == GA_NODE_BIQUAD && o.bqActive && !o.bqDynamic && absorbedBy.get(o.id) < 0) levelBqHeads += std::max(o.outCh, 1);
-          }
-        }
+        if (nd.type != GA_NODE_DELAY || !nd.delaySplit) continue;
         auto& ov = ex.outViews[si][ns.id];
-        const bool cutDelay = nd.type == GA_NODE_DELAY && nd.delaySplit && topoHasCycles && cycleBlocks > 1;   // (its reader set the views)
-        if (!cutDelay) ov.assign(nd.type == GA_NODE_CHANNEL_SPLITTER ? (int)nd.outputs.size() : std::max(ns.outCh, 1), nullptr);
-        NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, levelBqHeads};
-        if (cutDelay) k.delayPhase = 2;
-        switch (nd.type) {
-          case GA_NODE_CHANNEL_SPLITTER: {   // zero-copy: output o IS channel o of the mixed input
-            if (!ns.outMask) break;
-            auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
-            for (int o = 0; o < (int)nd.outputs.size(); o++)
-              if ((ns.outMask >> o) & 1) ov[o] = iv[o];
-            break;
-          }
-          case GA_NODE_CHANNEL_MERGER: {     // zero-copy: channel i IS channel 0 of input i
-            for (int i = 0; i < (int)ns.ins.size(); i++) {
-              if (!((ns.outMask >> i) & 1)) continue;
-              auto iv = ex.resolveInput((int)si, ns, i, false, nullptr);
-              ov[i] = iv.empty() ? nullptr : iv[0];
-            }
-            break;
-          }
-          case GA_NODE_CONSTANT_SOURCE: planConstantSource(k); break;
-          case GA_NODE_OSCILLATOR: planOscillator(k); break;
-          case GA_NODE_DELAY: planDelay(k); break;
-          case GA_NODE_STEREO_PANNER: planStereoPanner(k); break;
-          case GA_NODE_SPATIAL_PANNER: planSpatialPanner(k); break;
-          case GA_NODE_BUFFER_SOURCE: planBufferSource(k); break;
-          case GA_NODE_STREAM_SOURCE: planStreamSource(k); break;
-          case GA_NODE_GAIN: planGain(k); break;
-          case GA_NODE_BIQUAD: planBiquad(k); break;
-          case GA_NODE_CONVOLVER: {
-            auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
-            if (!nd.ir) break;  // no IR: cleared output (ConvolverNode.cs:107-119)
-            ex.convIn[ns.id][si] = iv;
-            // formulation D: the outputs of a fused group are summed as spectra; the sum is the LEADER's output, the other
-            // members hand their consumer a null (= contributes nothing) view (Context::planCoarseFusion)
-            if (nd.convPath == 4 && nd.dLeader >= 0 && nd.dLeader != ns.id) break;
-            // Nothing has reached this convolver since its delay line was created: the reference's partition sum is a sum of
-            // exact zeros (PartitionedConvolver.cs:154-223), and consumers that compare values -- StereoPannerNode's `pan !=
-            // _lastPan` (StereoPannerNode.cs:92-99), DelayNode's (int)(delayTime * sampleRate) -- see that.  The transform
-            // formulations (C, D) leave ~1e-9 of circular rounding in front of an onset inside the same window, so the blocks
-            // before the onset are served from the zero page instead of the output slab (fuzz session 42867).  The leader of a
-            // fused group carries the other members' sum and keeps its slab.
-#ifdef GA_EXPERIMENTS
-            static const bool noZeroPage = getenv("GA_NO_ZERO_PAGE") != nullptr;   // (to show that the regression tests catch the defect)
-#else
-            constexpr bool noZeroPage = false;
-#endif
-            if (!noZeroPage && ns.outZero && !(nd.convPath == 4 && nd.dGroupSize > 1)) {
-              for (int ch = 0; ch < ns.outCh; ch++) ov[ch] = zeros;
-              break;
-            }
-            for (int ch = 0; ch < ns.outCh; ch++) ov[ch] = ex.nodeOut(ns.id, ch);
-            break;
-          }
-          case GA_NODE_DESTINATION: {
-            // the destination aliases its input buffer (AudioDestinationNode.cs:44-50): mix straight into the bus
-            SmallVec<float*, 4> forced((size_t)std::max(ns.ins[0].bufCh, 1), nullptr);
-            for (int ch = 0; ch < ns.ins[0].bufCh && ch < (int)busSlabs.size(); ch++) forced[ch] = busTarget[ch] ? busTarget[ch] : busSlabs[ch];
-            ex.resolveInput((int)si, ns, 0, true, forced.data());
-            break;
-          }
-          default: break;
-        }
+        ov.assign(std::max(ns.outCh, 1), nullptr);
+        NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, 0};
+        k.delayPhase = 1;
+        planDelay(k);
       }
       ex.flushLevel();
     }
+    for (size_t ti = 0; ti < todo.size(); ti++) {
+      const NodeSeg* nsp = todo[ti];
+      if (ti + 4 < todo.size()) {   // (the sweep is bound by cache misses on the node records)
+        const char* nx = (const char*)nodes[todo[ti + 4]->id].get();
+        __builtin_prefetch(nx);
+        __builtin_prefetch(nx + 64);
+        __builtin_prefetch(nx + 128);
+      }
+      const NodeSeg& ns = *nsp;
+      NodeS& nd = *nodes[ns.id];
+      if (ns.level != curLevel) {
+        ex.flushLevel();
+        curLevel = ns.level;
+        levelBqHeads = 0;   // constant-coefficient cascade outputs of this level (all levels' biquad launches are separate)
+        for (size_t tj = ti; tj < todo.size() && todo[tj]->level == curLevel; tj++) {
+          const NodeSeg& o = *todo[tj];
+          if (o.type == GA_NODE_BIQUAD && o.bqActive && !o.bqDynamic && absorbedBy.get(o.id) < 0) levelBqHeads += std::max(o.outCh, 1);
+        }
+      }
+      auto& ov = ex.outViews[si][ns.id];
+      const bool cutDelay = nd.type == GA_NODE_DELAY && nd.delaySplit && topoHasCycles && cycleBlocks > 1;   // (its reader set the views)
+      if (!cutDelay) ov.assign(nd.type == GA_NODE_CHANNEL_SPLITTER ? (int)nd.outputs.size() : std::max(ns.outCh, 1), nullptr);
+      NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, levelBqHeads};
+      if (cutDelay) k.delayPhase = 2;
+      switch (nd.type) {
+        case GA_NODE_CHANNEL_SPLITTER: {   // zero-copy: output o IS channel o of the mixed input
+          if (!ns.outMask) break;
+          auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
+          for (int o = 0; o < (int)nd.outputs.size(); o++)
+            if ((ns.outMask >> o) & 1) ov[o] = iv[o];
+          break;
+        }
+        case GA_NODE_CHANNEL_MERGER: {     // zero-copy: channel i IS channel 0 of input i
+          for (int i = 0; i < (int)ns.ins.size(); i++) {
+            if (!((ns.outMask >> i) & 1)) continue;
+            auto iv = ex.resolveInput((int)si, ns, i, false, nullptr);
+            ov[i] = iv.empty() ? nullptr : iv[0];
+          }
+          break;
+        }
+        case GA_NODE_CONSTANT_SOURCE: planConstantSource(k); break;
+        case GA_NODE_OSCILLATOR: planOscillator(k); break;
+        case GA_NODE_DELAY: planDelay(k); break;
+        case GA_NODE_STEREO_PANNER: planStereoPanner(k); break;
+        case GA_NODE_SPATIAL_PANNER: planSpatialPanner(k); break;
+        case GA_NODE_BUFFER_SOURCE: planBufferSource(k); break;
+        case GA_NODE_STREAM_SOURCE: planStreamSource(k); break;
+        case GA_NODE_GAIN: planGain(k); break;
+        case GA_NODE_BIQUAD: planBiquad(k); break;
+        case GA_NODE_CONVOLVER: {
+          auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
+          if (!nd.ir) break;  // no IR: cleared output (ConvolverNode.cs:107-119)
+          ex.convIn[ns.id][si] = iv;
+          // formulation D: the outputs of a fused group are summed as spectra; the sum is the LEADER's output, the other
+          // members hand their consumer a null (= contributes nothing) view (Context::planCoarseFusion)
+          if (nd.convPath == 4 && nd.dLeader >= 0 && nd.dLeader != ns.id) break;
+          // Nothing has reached this convolver since its delay line was created: the reference's partition sum is a sum of
+          // exact zeros (PartitionedConvolver.cs:154-223), and consumers that compare values -- StereoPannerNode's `pan !=
+          // _lastPan` (StereoPannerNode.cs:92-99), DelayNode's (int)(delayTime * sampleRate) -- see that.  The transform
+          // formulations (C, D) leave ~1e-9 of circular rounding in front of an onset inside the same window, so the blocks
+          // before the onset are served from the zero page instead of the output slab (fuzz session 42867).  The leader of a
+          // fused group carries the other members' sum and keeps its slab.
+#ifdef GA_EXPERIMENTS
+          static const bool noZeroPage = getenv("GA_NO_ZERO_PAGE") != nullptr;   // (to show that the regression tests catch the defect)
+#else
+          constexpr bool noZeroPage = false;
+#endif
+          if (!noZeroPage && ns.outZero && !(nd.convPath == 4 && nd.dGroupSize > 1)) {
+            for (int ch = 0; ch < ns.outCh; ch++) ov[ch] = zeros;
+            break;
+          }
+          for (int ch = 0; ch < ns.outCh; ch++) ov[ch] = ex.nodeOut(ns.id, ch);
+          break;
+        }
+        case GA_NODE_DESTINATION: {
+          // the destination aliases its input buffer (AudioDestinationNode.cs:44-50): mix straight into the bus
+          SmallVec<float*, 4> forced((size_t)std::max(ns.ins[0].bufCh, 1), nullptr);
+          for (int ch = 0; ch < ns.ins[0].bufCh && ch < (int)busSlabs.size(); ch++) forced[ch] = busTarget[ch] ? busTarget[ch] : busSlabs[ch];
+          ex.resolveInput((int)si, ns, 0, true, forced.data());
+          break;
+        }
+        default: break;
+      }
+    }
+    ex.flushLevel();
+  }
 }
 
 // feedback cycles, first chunk after an edit closed a loop: the reference's consumer finds the block the producer put out BEFORE the
@@ -979,7 +958,7 @@ void Context::chunkStaleSeed(ChunkRun& r) {
   std::vector<StaleJob> jobs;
   auto alive = [&](const float* p) {
     if (!p) return false;
-    const size_t blockBytes = (size_t)slabFrames * sizeof(float) * std::max<size_t>(8, std::min<size_t>(1024, ((size_t)1 << 30) / std::max<size_t>((size_t)slabFrames * sizeof(float), 1)));
+    const size_t slabBytes = (size_t)slabFrames * sizeof(float), blockBytes = slabBytes * slabsPerBlock(slabBytes);
     for (void* b : slabBlocks)
       if ((const char*)p >= (const char*)b && (const char*)p + kBlock * sizeof(float) <= (const char*)b + blockBytes) return true;
     for (const auto& np : nodes) {
@@ -1038,11 +1017,8 @@ void Context::chunkStaleSeed(ChunkRun& r) {
     if (any || nd.staleBuf) keepLastBlock(nd);   // (silent and never kept: nothing to remember -- a later seed reads zeros)
   }
   staleLeavers.clear();
-  if (jobs.empty()) return;
-  const size_t off = ex.plan.putv(jobs);
-  const int nj = (int)jobs.size();
   hipStream_t st = stream;
-  ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_stale_copy(st, (const StaleJob*)(base + off), nj); });
+  ex.flush(jobs, LK_OTHER, nullptr, [=](const StaleJob* t, int nj, int64_t, uint8_t*) { launch_stale_copy(st, t, nj); });
 }
 
 // pass 8b: feedback cycles -- what every stale producer put out in this (one-block) chunk is what the consumers that pull it while
@@ -1077,27 +1053,15 @@ void Context::chunkStaleCommit(ChunkRun& r) {
     std::swap(nd.staleBuf, nd.staleNext);
     nd.staleSeq = chunkSeq;
   }
-  const size_t off = ex.plan.putv(jobs);
-  const int nj = (int)jobs.size();
   hipStream_t st = stream;
-  ex.plan.add(LK_OTHER, [=](uint8_t* base) { launch_stale_copy(st, (const StaleJob*)(base + off), nj); });
+  ex.flush(jobs, LK_OTHER, nullptr, [=](const StaleJob* t, int nj, int64_t, uint8_t*) { launch_stale_copy(st, t, nj); });
 }
 
 // pass 8: delay-line histories of the next chunk
 void Context::chunkDelayCommit(ChunkRun& r) {
-  Context& c_ = *this; (void)c_;
-  std::vector<int>& topo = r.topo;
-  int& maxDepth = r.maxDepth; int& maxLevel = r.maxLevel; (void)maxDepth; (void)maxLevel;
-  int64_t& n = r.n; (void)n;
-  std::vector<double>& bt = r.bt; (void)bt;
-  std::vector<int>& srcIds = r.srcIds; (void)srcIds;
-  std::vector<SrcPlanOut>& srcPlans = r.srcPlans; (void)srcPlans;
-  std::vector<Segment>& segs = r.segs; (void)segs;
-  const int64_t frames = r.n * kBlock; (void)frames;
-  int& bHistMax = r.bHistMax; (void)bHistMax;
   Exec& ex = *r.ex;
   // DelayNode: the last maxDelay samples every ring has seen become the history of the next chunk
-  for (int id : topo) {
+  for (int id : r.topo) {
     NodeS& nd = *nodes[id];
     if (nd.type != GA_NODE_DELAY || !nd.delayLoaded) continue;
     const size_t maxD = (size_t)nd.maxDelaySamples, pitch = maxD + (size_t)nd.delayCap;
@@ -1109,7 +1073,6 @@ void Context::chunkDelayCommit(ChunkRun& r) {
       ex.plan.add(LK_OTHER, [=](uint8_t*) { GA_HIP(hipMemcpyAsync(dst, src, maxD * sizeof(float), hipMemcpyDeviceToDevice, st)); });
     }
   }
-
 }
 
 }  // namespace ga
