@@ -1,5 +1,7 @@
 // biquad_pipe_kernel<NSEC> against the lane-per-cascade kernel, bit for bit, for every cascade length and ragged sizes (frames that
 // are no multiple of anything, fewer cascades than a wave holds, cascades of different lengths in one wave, non-zero start states).
+// (A bench tool, kernel against kernel.  The suite holds these shapes -- every cascade length, every wave packing, ragged and
+// unaligned rows -- against the CPU oracle: tests/test_gpu_biquad_cascades.py.)
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I graphaudio_amd/csrc tools/micro/bq_pipe_check.hip -o tools/micro/bq_pipe_check
 #include "../../graphaudio_amd/csrc/ga_kernels.hip"
 #include <vector>
