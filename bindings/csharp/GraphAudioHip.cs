@@ -46,6 +46,8 @@ internal static unsafe partial class GraphAudioHip
         public long ref_order_rows;
         public long sim_replays;
         public long twin_rows;
+        public long delay_flags_read;
+        public long delay_flags_predicted;
     }
 
     [LibraryImport(Lib, EntryPoint = "ga_strerror")] [UnmanagedCallConv(CallConvs = new[] { typeof(CallConvCdecl) })]

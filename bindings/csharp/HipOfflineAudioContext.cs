@@ -79,6 +79,21 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _delayFlagExact;
+    /// <summary>Option "delay_flag_exact" (default off): the non-silent flag of a DelayNode's output is read from the rendered samples
+    /// (the first sample != 0f, as DelayNode.Process raises it) instead of being predicted from the flags of its input blocks.  Costs
+    /// one stream wait in the chunks in which a delay's flag may rise; a delay on a feedback loop, behind another undecided delay, behind
+    /// a source with a modulated playbackRate or behind a ConvolverNode keeps the prediction (Stats.delay_flags_predicted).</summary>
+    public bool DelayFlagExact
+    {
+        get => _delayFlagExact;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "delay_flag_exact", value ? 1 : 0));
+            _delayFlagExact = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

@@ -84,6 +84,9 @@ void Context::runChunk(int64_t n, float* const* bus) {
 // pass 1: reachability, level and convolver depth of every node; state handed back by automated runs that ended
 void Context::chunkTopology(ChunkRun& r) {
   std::vector<int>& topo = r.topo;
+  for (int id : probeDelays)   // (the previous chunk's choice, if a failure kept it from being cleared: runTwoStageChunk)
+    if (id < (int)nodes.size() && nodes[id]) nodes[id]->delayProbe = false;
+  probeDelays.clear();
   // ---- reachability, level, convolver depth on the graph as it stands after the queued commands ----
   // (cached while no connection, disposal or impulse response changed since the last chunk)
   // (a graph with feedback is walked again every chunk: whether its loops can be cut at their DelayNodes depends on the delay
@@ -99,6 +102,7 @@ void Context::chunkTopology(ChunkRun& r) {
     np->level = 0;
     np->depth = 0;
     np->delaySplit = false;
+    np->delayOnLoop = false;
   }
   cycleBlocks = 1;
   loopGainBound = 0.0;
@@ -132,7 +136,8 @@ void Context::chunkTopology(ChunkRun& r) {
         double bound = 1.0;   // an upper estimate of the loop's gain: what a last-bit difference that enters it is multiplied by per turn
         for (size_t q = stack.size(); q-- > 0;) {
           const int m = stack[q];
-          const NodeS& mn = *nodes[m];
+          NodeS& mn = *nodes[m];
+          mn.delayOnLoop = true;   // (read for DelayNodes only: option "delay_flag_exact", below)
           if (splittable(mn) >= 2) {
             candidate[m] = 1;
             any = true;
@@ -325,15 +330,72 @@ void Context::chunkTopology(ChunkRun& r) {
         fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
     }
     r.rateMods = topoRateMods;
-    // A feedback loop lies entirely inside the cone or entirely outside it (the cone is closed upstream; a loop through a modulated source
-    // is refused above): a loop outside is stage 2's alone, the same walk from the destination as a one-pass chunk.  A loop inside is
-    // stage 1's, and stage 1 has to enter the cone where the reference's walk does (Sim::evalProbe): the cone nodes first reached from a
-    // node outside it, in the order the walk reaches them.
+    r.stage1 = rateCone;
+  }
+  // ---- DelayNodes whose output flag this chunk reads from their samples (option "delay_flag_exact"; runTwoStageChunk) ----
+  // The flag rises at the first output SAMPLE that is != 0f (DelayNode.cs:72,92,96-97), which the host cannot see: it predicts the flag
+  // from the flags of the blocks that went into the ring (Sim::process), never late, sometimes early.  A delay whose cone can be
+  // rendered ahead of the rest is rendered in stage 1 instead, and the block in which its samples raise the flag is read back
+  // (delay_onset_kernel).  Accepted, per chunk, while nothing has moved: a reachable DelayNode whose flag is down, that is on no
+  // feedback loop (not among the nodes of a back edge's loop, NodeS::delayOnLoop, and not reached by its own cone: deciding it would
+  // split the reference's walk inside a block), with no other DelayNode whose flag is down in front
+  // of it (the control state of the nodes in between would be undecided: more than two stages), no source with a modulated
+  // playbackRate in front of it and not in front of one (stage 1 plans both from the state before the chunk), and no ConvolverNode
+  // in front of it (stage 1 plans no convolvers: their fusion groups and scratch planes belong to one pass over the whole graph).
+  // Every other delay keeps the prediction (ga_stats.delay_flags_predicted).
+  if (delayFlagExact && topoHasTimeNodes) {
+    std::vector<int> seen, stack, cone;
+    for (int id : topo) {
+      NodeS& d = *nodes[id];
+      if (d.type != GA_NODE_DELAY || d.delayAudible || d.delayOnLoop || d.delaySplit) continue;
+      if (!topoRateMods.empty() && rateCone[id]) continue;
+      if (seen.empty()) seen.assign(nodes.size(), -1);
+      bool ok = true;
+      cone.clear();
+      stack.assign(1, id);
+      seen[id] = id;
+      while (!stack.empty() && ok) {
+        const NodeS& nd = *nodes[stack.back()];
+        stack.pop_back();
+        auto visit = [&](int up) {
+          // (the cone reaches D itself: D is on a loop that the walk from the destination closed through a node it had finished
+          // already, so D was never on the stack of a back edge -- a consumer of D would be stage 1's and read a view D does not hand out)
+          if (up == id) ok = false;
+          if (seen[up] == id) return;
+          seen[up] = id;
+          const NodeS& u = *nodes[up];
+          if ((u.type == GA_NODE_DELAY && !u.delayAudible) || u.type == GA_NODE_CONVOLVER ||
+              ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty()))
+            ok = false;
+          cone.push_back(up);
+          stack.push_back(up);
+        };
+        for (const auto& p : nd.params)
+          for (const auto& m : p.modulation) visit(m.first);
+        for (const auto& in : nd.inputs)
+          for (const Conn& cn : in.connected) visit(cn.node);
+      }
+      if (!ok) continue;
+      if (r.stage1.empty()) r.stage1.assign(nodes.size(), 0);
+      r.stage1[id] = 1;
+      for (int up : cone) r.stage1[up] = 1;
+      d.delayProbe = true;
+      d.delayShadow = false;
+      d.delaySpans.clear();
+      probeDelays.push_back(id);
+    }
+    r.probeDelays = probeDelays;
+  }
+  if (!r.stage1.empty()) {
+    // A feedback loop lies entirely inside stage 1's set or entirely outside it (the set is closed upstream; a loop through a modulated
+    // source is refused above, a delay on a loop is not accepted): a loop outside is stage 2's alone, the same walk from the destination
+    // as a one-pass chunk.  A loop inside is stage 1's, and stage 1 has to enter the set where the reference's walk does
+    // (Sim::evalProbe): the nodes of the set first reached from a node outside it, in the order the walk reaches them.
     bool coneLoop = false;
-    for (int id : staleProducers) coneLoop = coneLoop || rateCone[id];
+    for (int id : staleProducers) coneLoop = coneLoop || r.stage1[id];
     if (coneLoop)
       for (const auto& e : topoRefEntry)
-        if (rateCone[e.first] && (e.second < 0 || !rateCone[e.second])) r.coneRoots.push_back(e.first);
+        if (r.stage1[e.first] && (e.second < 0 || !r.stage1[e.second])) r.coneRoots.push_back(e.first);
   }
   // ---- SpatialPannerNode: what the device path does not render is refused here, while nothing has moved ----
   if (topoHasSpatial) {
@@ -472,6 +534,10 @@ void Context::chunkSimulate(ChunkRun& r) {
   if (r.pre)   // the second stage breaks where the first stage's segments do: the rendered nodes' views change there
     for (int64_t b : r.pre->preB0)
       if (b > 0 && b < n) breaks.push_back(b);
+  if (r.pre)   // ... and where the samples of a DelayNode raised its output flag (option "delay_flag_exact")
+    for (int id : r.pre->probeDelays)
+      for (const NodeS::DelaySpan& sp : nodes[id]->delaySpans)
+        if (sp.onset > 0 && sp.onset < n) breaks.push_back(sp.onset);
   std::sort(breaks.begin(), breaks.end());
   breaks.erase(std::unique(breaks.begin(), breaks.end()), breaks.end());
   std::unordered_map<int64_t, std::vector<int>> goneAt;
@@ -492,6 +558,18 @@ void Context::chunkSimulate(ChunkRun& r) {
   sim.extraBreaks = &extraBreaks;
   sim.blockTimes = &bt;
   int minDestCh = 32;
+  if (r.stage == 1) {   // rows of the cone's output state in a snapshot (Sim::restorePre)
+    r.preRow.assign(nodes.size(), -1);
+    int row = 0;
+    for (int id : topo) {
+      r.preRow[id] = row;
+      row += (int)nodes[id]->outputs.size();
+    }
+    // (an accepted delay's cone may change its channel count inside the chunk: the counts before the chunk, for stage 2's first block)
+    if (!r.probeDelays.empty())
+      for (int id : topo)
+        for (const OutputS& o : nodes[id]->outputs) r.preCh0.push_back(o.bufCh);
+  }
   {
     int64_t b = 0;
     uint64_t prevHash = lastHash;
@@ -571,9 +649,20 @@ void Context::chunkSimulate(ChunkRun& r) {
         }
       }
       if (!replayed) {
+        if (r.pre && !r.pre->preCh0.empty()) {
+          // A consumer sizes its input from its producers' channel counts BEFORE it pulls them (AudioNodeInput.cs:140-168): the counts of
+          // the block before.  Stage 1 has left the cone with the counts of the chunk's last block: put back what block b - 1 left.
+          const ChunkRun& p = *r.pre;
+          const size_t s1 = b > 0 ? (size_t)(std::upper_bound(p.preB0.begin(), p.preB0.end(), b - 1) - p.preB0.begin()) - 1 : 0;
+          for (int id : p.topo) {
+            NodeS& cn = *nodes[id];
+            for (size_t o = 0; o < cn.outputs.size(); o++)
+              cn.outputs[o].bufCh = b > 0 ? p.preSnap[s1][(size_t)p.preRow[id] + o].bufCh : p.preCh0[(size_t)p.preRow[id] + o];
+          }
+        }
         inRender = true;
         try {
-          if (r.stage == 1) sim.evalProbe(r.rateMods, r.coneRoots);
+          if (r.stage == 1) sim.evalProbe(r.rateMods, r.coneRoots, r.probeDelays);
           else sim.evalNode(0);
         } catch (...) {
           inRender = false;
@@ -600,14 +689,6 @@ void Context::chunkSimulate(ChunkRun& r) {
       sg.b1 = std::min(nb, n);
       prevHash = sg.hash;
       if (r.stage == 1) {   // the cone's output state in this segment, for the second stage (Sim::restorePre)
-        if (r.preRow.empty()) {
-          r.preRow.assign(nodes.size(), -1);
-          int row = 0;
-          for (int id : topo) {
-            r.preRow[id] = row;
-            row += (int)nodes[id]->outputs.size();
-          }
-        }
         std::vector<ChunkRun::PreOut> snap;
         for (int id : topo)
           for (const OutputS& o : nodes[id]->outputs) snap.push_back(ChunkRun::PreOut{o.bufCh, o.silent, o.zero});
@@ -626,6 +707,9 @@ void Context::chunkSimulate(ChunkRun& r) {
       for (int id : r.streamIds) streamReplay(*nodes[id], n, bt, false);
     }
   }
+  if (r.pre && !r.pre->preCh0.empty() && !r.pre->preSnap.empty())   // (the cone leaves the chunk with the counts of its last block)
+    for (int id : r.pre->topo)
+      for (size_t o = 0; o < nodes[id]->outputs.size(); o++) nodes[id]->outputs[o].bufCh = r.pre->preSnap.back()[(size_t)r.pre->preRow[id] + o].bufCh;
   if (r.stage != 1) chunkMinDestCh = minDestCh;
   r.tmSim = nowMs();
 
@@ -882,7 +966,7 @@ void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
   latched = true;
   profileNow = profile && (profileSeq++ % std::max(profileEvery, 1)) == 0;
   chunkTopology(r);
-  if (!r.rateMods.empty()) {   // a playbackRate modulated by a signal: the modulator cone first (runTwoStageChunk)
+  if (!r.rateMods.empty() || !r.probeDelays.empty()) {   // a playbackRate modulated by a signal, a DelayNode's flag read from its samples: their cones first (runTwoStageChunk)
     runTwoStageChunk(r);
     return;
   }
@@ -954,7 +1038,7 @@ void Context::chunkRetire(ChunkRun& r) {
 }
 
 // ======================================================================================================
-// two-stage chunks: a k-rate playbackRate modulated by a signal
+// two-stage chunks: a k-rate playbackRate modulated by a signal, a DelayNode's output flag read from its samples
 // ======================================================================================================
 // The rate of every block (clamp(intrinsic(t0) + modulation[0]), AudioParam.cs:143-165) sets how many samples the block consumes and
 // where a one-shot source runs out of data: source spans, segments and the silence flags downstream depend on audio the host never
@@ -963,6 +1047,12 @@ void Context::chunkRetire(ChunkRun& r) {
 // wait, then the host reads the rates and the walk summaries back.  Stage 2 plans and runs everything else: the cone's nodes count as
 // rendered -- their per-block state comes from stage 1's simulation (Sim::restorePre), their output views from stage 1's executor.
 // Nothing of the next chunk overlaps this one's planning: the wait is on the whole of stage 1.
+// Option "delay_flag_exact": the DelayNodes chunkTopology accepted and their cones are stage 1's as well.  Stage 1 keeps each one's
+// predicted flag apart (NodeS::delayShadow) and plans the node as ever; where the prediction raises the flag inside the chunk,
+// delay_onset_kernel looks for the first block of the node's output rows that holds a sample != 0f, and its word travels to the host
+// with the rates.  Stage 2 sees the flag down before that block and up from it on (Sim::restorePre), breaks its segments there and
+// hands the node's rows to its consumers from there on.  Without a modulated rate and without a predicted rise there is nothing to
+// read back: the probe and the wait are skipped, the two stages are queued back to back.
 // A graph with feedback: every loop lies inside the cone (stage 1's) or outside it (stage 2's), and both stages run the chunk's r.n
 // blocks -- `cycleBlocks` when every loop is cut at a DelayNode, one otherwise (chunkTopology).  A stale term resolves in the stage that
 // plans its consumer, which is its producer's stage.  The kept blocks of the stale producers and leavers of BOTH stages are seeded
@@ -979,8 +1069,10 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   r1.maxLevel = r.maxLevel;
   r1.rateMods = r.rateMods;
   r1.coneRoots = std::move(r.coneRoots);
+  r1.probeDelays = r.probeDelays;
+  const std::vector<char>& stage1 = r.stage1;
   for (int id : r.topo)
-    if (rateCone[id]) r1.topo.push_back(id);
+    if (stage1[id]) r1.topo.push_back(id);
   lastSegStable = false;   // (no first-block replay on either side of the split: chunkSimulate)
   chunkSimulate(r1);
   chunkResources(r1);
@@ -1001,9 +1093,24 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   chunkDelayCommit(r1);
   chunkRateProbe(r1);
   chunkExecute(r1);
-  const double tw0 = nowMs();
-  GA_HIP(hipStreamSynchronize(stream));   // the rates and walk summaries (chunkRateProbe)
-  if (gaTiming) fprintf(stderr, "[ga]   two-stage chunk: stage 1 wait %.3f ms\n", nowMs() - tw0);
+  if (r1.waited) {   // (no modulated rate, and no accepted delay whose flag can rise in this chunk: nothing to read back)
+    const double tw0 = nowMs();
+    GA_HIP(hipStreamSynchronize(stream));   // the rates, walk summaries and onset blocks (chunkRateProbe)
+    if (gaTiming) fprintf(stderr, "[ga]   two-stage chunk: stage 1 wait %.3f ms\n", nowMs() - tw0);
+  }
+  // the accepted delays: the block in which each span's samples raised the flag; the flag the node leaves the chunk with is its last span's
+  for (int id : r1.probeDelays) {
+    NodeS& d = *nodes[id];
+    bool read = false;
+    for (NodeS::DelaySpan& sp : d.delaySpans) {
+      if (sp.word < 0) continue;
+      const int32_t v = r1.onsetWords[sp.word];
+      if (v != std::numeric_limits<int32_t>::max()) sp.onset = v;
+      read = true;
+    }
+    d.delayAudible = !d.delaySpans.empty() && d.delaySpans.back().onset != std::numeric_limits<int64_t>::max();
+    if (read) stats.delay_flags_read++;
+  }
 
   // ---- stage 2: everything else ----
   r.stage = 2;
@@ -1015,7 +1122,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
     std::vector<int> rest;
     rest.reserve(r.topo.size() - r1.topo.size());
     for (int id : r.topo)
-      if (!rateCone[id]) rest.push_back(id);
+      if (!stage1[id]) rest.push_back(id);
     r.topo.swap(rest);
   }
   chunkSimulate(r);
@@ -1036,6 +1143,18 @@ void Context::runTwoStageChunk(ChunkRun& r) {
       if (g != 1.f) ex.setScale((int)si, id, g);
       if (const float* cv = ex1.curveOf((int)s1, id)) ex.setCurve((int)si, id, cv);
     }
+    // an accepted delay: stage 1 wrote its rows for every segment (planDelay) and handed out no view; consumers see them from the
+    // onset on (stage 2 breaks its segments there: chunkSimulate)
+    for (int id : r1.probeDelays) {
+      const NodeS::DelaySpan* sp = nullptr;
+      for (const NodeS::DelaySpan& q : nodes[id]->delaySpans)
+        if (q.b0 <= r.segs[si].b0) sp = &q;
+      if (!sp) continue;
+      Views v((size_t)std::max(sp->ch, 1), nullptr);
+      if (r.segs[si].b0 >= sp->onset)
+        for (int ch = 0; ch < sp->ch; ch++) v[ch] = r1.ex->nodeOut(id, ch);
+      ex.outViews[si][id] = v;
+    }
   }
   curveListTopoSize = ~(size_t)0;
   chunkParamCurves(r);
@@ -1052,13 +1171,16 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   chunkCommit(r);
   curveListTopoSize = ~(size_t)0;
   r1.ex.reset();
+  for (int id : probeDelays) nodes[id]->delayProbe = false;
+  probeDelays.clear();
   chunkRetire(r);
   lastSegStable = false;   // (the last segment's records hold stage 2's nodes only: no first-block replay in the next chunk)
 }
 
 // stage 1: the modulation input of every modulated rate mixed (Exec::resolveInSeg: the mix every modulated parameter gets), the rate
-// of every block (krate_probe_kernel), the walk of every modulated buffer source (gsr_walk_kernel, option rate_mod_walk), and one
-// copy of the rates and walk summaries to page-locked memory
+// of every block (krate_probe_kernel), the walk of every modulated buffer source (gsr_walk_kernel, option rate_mod_walk), the onset
+// blocks of the accepted DelayNodes (delay_onset_kernel, option delay_flag_exact), and one copy of the rates, walk summaries and onset
+// words to page-locked memory
 void Context::chunkRateProbe(ChunkRun& r) {
   Exec& ex = *r.ex;
   const int64_t n = r.n;
@@ -1089,7 +1211,30 @@ void Context::chunkRateProbe(ChunkRun& r) {
     }
   // device area: rates [nm][n], walk summaries, descriptors; the first two are read back
   const size_t ratesBytes = (size_t)roundup((int64_t)nm * n * (int64_t)sizeof(float), 16);
-  const size_t readBytes = ratesBytes + walks.size() * sizeof(GsrWalkOut);
+  // the accepted delays (option "delay_flag_exact"): one job per span between two re-rents in which the prediction raises the flag --
+  // the samples cannot raise it earlier -- over the blocks from there to the span's end; its word travels with the rates
+  std::vector<DelayOnsetJob> onsets;
+  for (int id : r.probeDelays) {
+    NodeS& d = *nodes[id];
+    for (size_t k = 0; k < d.delaySpans.size(); k++) {
+      NodeS::DelaySpan& sp = d.delaySpans[k];
+      const int64_t end = std::min<int64_t>(k + 1 < d.delaySpans.size() ? d.delaySpans[k + 1].b0 : n, n);
+      sp.word = -1;
+      if (sp.rise < 0 || sp.rise >= end || sp.ch < 1) continue;
+      DelayOnsetJob oj{};
+      oj.nrows = std::min(sp.ch, kDelayOnsetRows);
+      for (int ch = 0; ch < oj.nrows; ch++) oj.rows[ch] = ex.nodeOut(id, ch);   // (planDelay wrote every block of the span)
+      oj.first = (int32_t)sp.rise;
+      oj.count = (int32_t)(end - sp.rise);
+      sp.word = (int)onsets.size();
+      onsets.push_back(oj);
+    }
+  }
+  const size_t onsetOff = (size_t)roundup((int64_t)(ratesBytes + walks.size() * sizeof(GsrWalkOut)), 16);
+  const size_t readBytes = onsets.empty() ? ratesBytes + walks.size() * sizeof(GsrWalkOut)
+                                          : (size_t)roundup((int64_t)(onsetOff + onsets.size() * sizeof(int32_t)), 16);
+  r.waited = readBytes > 0;
+  if (!r.waited) return;
   size_t descCount = 0;
   for (const GsrWalkJob& j : walks) descCount += (size_t)j.nrel + 1;
   const size_t devBytes = readBytes + descCount * sizeof(GsrBlock);
@@ -1150,6 +1295,15 @@ void Context::chunkRateProbe(ChunkRun& r) {
   }
   const size_t btOff = ex.plan.putv(r.bt);
   hipStream_t st = stream;
+  if (!onsets.empty()) {
+    int32_t* wordsDev = (int32_t*)((char*)rateModDev + onsetOff);
+    r.onsetWords = (const int32_t*)((const char*)rateModHost + onsetOff);
+    for (size_t k = 0; k < onsets.size(); k++) onsets[k].out = wordsDev + k;
+    const std::vector<int32_t> none(onsets.size(), std::numeric_limits<int32_t>::max());
+    const size_t noneOff = ex.plan.putv(none), noneBytes = none.size() * sizeof(int32_t);
+    ex.plan.add(LK_OTHER, [=](uint8_t* base) { GA_HIP(hipMemcpyAsync(wordsDev, base + noneOff, noneBytes, hipMemcpyDeviceToDevice, st)); });
+    ex.flush(onsets, LK_OTHER, &DelayOnsetJob::count, [=](const DelayOnsetJob* t, int nj, int64_t mx, uint8_t*) { launch_delay_onset(st, t, nj, mx); });
+  }
   ex.flush(pjobs, LK_OTHER, nullptr, [=](const KrateProbeJob* t, int nj, int64_t, uint8_t* base) { launch_krate_probe(st, t, nj, base, (const double*)(base + btOff), n); });
   ex.flush(walks, LK_OTHER, nullptr, [=](const GsrWalkJob* t, int nw, int64_t, uint8_t*) { launch_gsr_walk(st, t, nw); });
   void* hostDst = rateModHost;

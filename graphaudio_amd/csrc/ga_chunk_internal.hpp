@@ -122,9 +122,13 @@ struct Sim {
   // A cone with a feedback loop is entered where the reference's walk from the destination enters it (`roots`, ChunkRun::coneRoots):
   // which edge of the loop reads its producer's previous block follows from that (TermS::stale).  The cone is closed upstream, so the
   // walk between two roots only visits nodes outside it, which leave the cone's state alone.
-  void evalProbe(const std::vector<std::pair<int, int>>& mods, const std::vector<int>& roots) {
+  // The DelayNodes whose flag is read from their samples (option "delay_flag_exact", Context::chunkTopology) are evaluated after the
+  // roots: their cones are stage 1's as well, and nothing in stage 1 reads their output.
+  void evalProbe(const std::vector<std::pair<int, int>>& mods, const std::vector<int>& roots, const std::vector<int>& delays) {
     for (int id : roots)
       if (!c.nodes[id]->disposed) evalNode(id);   // (a source of the cone disposed at the chunk's first block: chunkSimulate)
+    for (int id : delays)
+      if (!c.nodes[id]->disposed) evalNode(id);
     for (const auto& pm : mods) {
       InSeg is;
       pullMod(c.nodes[pm.first]->params[pm.second], is);
@@ -375,10 +379,17 @@ struct Sim {
       case GA_NODE_DELAY: {  // DelayNode.cs:43-100
         const InSeg& in = ns.ins[0];
         const int ch = in.bufCh;
+        // A node whose flag is read from its samples in this chunk (option "delay_flag_exact", Context::chunkTopology): the prediction
+        // below runs on a flag of its own and only says from which block on the samples have to be looked at (DelaySpan::rise)
+        bool& audible = n_.delayProbe ? n_.delayShadow : n_.delayAudible;
         if (ch != n_.delayCh) {   // `_outputBuffer` re-rented: a cleared buffer is silent again (:49-55)
           n_.delayAudible = false;
+          n_.delayShadow = false;
           n_.delayCh = ch;
+          if (n_.delayProbe) n_.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
         }
+        if (n_.delayProbe && n_.delaySpans.empty()) n_.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
+        const bool wasAudible = audible;
         const int64_t B = c.currentBlock + brel;   // absolute block of this evaluation
         const int64_t OPEN = std::numeric_limits<int64_t>::max();
         const int maxD = n_.maxDelaySamples;
@@ -416,16 +427,16 @@ struct Sim {
         // second connection that ended earlier) would wake up too early.  While audio is on its way the node is evaluated again
         // block by block.
         const bool timelineOnly = !n_.params[0].events.empty() && ns.pinSilent(0) && blockTimes && brel < (int64_t)blockTimes->size();
-        if (!n_.delayAudible && timelineOnly) {
+        if (!audible && timelineOnly) {
           const ParamS& pd = n_.params[0];
           const double t0 = (*blockTimes)[brel], dts = 1.0 / c.sampleRate;
           bool pending = false;
-          for (int r = 0; r < ch && !n_.delayAudible; r++) {
+          for (int r = 0; r < ch && !audible; r++) {
             auto& m = model[r];
             for (auto& run : m.runs)
               if (run.second == OPEN || run.second + maxD >= m.pos) pending = true;
             if (m.runs.empty()) continue;
-            for (int i = 0; i < kBlock && !n_.delayAudible; i++) {
+            for (int i = 0; i < kBlock && !audible; i++) {
               const float dtv = param_value_at(pd.events.data(), (int)pd.events.size(), pd.value, pd.arate ? t0 + i * dts : t0);
               int d = (int)(dtv * (float)c.sampleRate);
               d = std::min(std::max(d, 0), maxD);
@@ -433,22 +444,22 @@ struct Sim {
               const int64_t q = m.pos + i - d;
               for (auto& run : m.runs)
                 if (q >= run.first && (run.second == OPEN || q < run.second)) {
-                  n_.delayAudible = true;
+                  audible = true;
                   break;
                 }
             }
           }
-          if (!n_.delayAudible && pending && extraBreaks) extraBreaks->push_back(brel + 1);
-        } else if (!n_.delayAudible && dmax > 0) {
+          if (!audible && pending && extraBreaks) extraBreaks->push_back(brel + 1);
+        } else if (!audible && dmax > 0) {
           dmin = std::max(dmin, 1);
           int64_t nextFlip = OPEN;
-          for (int r = 0; r < ch && !n_.delayAudible; r++) {
+          for (int r = 0; r < ch && !audible; r++) {
             auto& m = model[r];
             const int64_t lo = m.pos - dmax, hi = m.pos + (kBlock - 1) - dmin;   // ring frames this block can read
             for (auto& run : m.runs) {
               const int64_t rs = run.first, re = run.second == OPEN ? OPEN : run.second - 1;
               if (rs <= hi && re >= lo) {
-                n_.delayAudible = true;
+                audible = true;
                 break;
               }
               if (rs > hi) {   // arrives k blocks from now: pos + 128 k + 127 - dmin >= rs
@@ -457,11 +468,19 @@ struct Sim {
               }
             }
           }
-          if (!n_.delayAudible && nextFlip != OPEN && extraBreaks) extraBreaks->push_back(nextFlip - c.currentBlock);
+          if (!audible && nextFlip != OPEN && extraBreaks) extraBreaks->push_back(nextFlip - c.currentBlock);
         }
-        ns.delayAudible = n_.delayAudible;
+        if (audible && !wasAudible) {
+          if (n_.delayProbe) {
+            n_.delaySpans.back().rise = brel;
+          } else if (c.delayFlagExact && n_.delayPredChunk != c.stats.chunks) {   // (a node that was not accepted: chunkTopology says why)
+            n_.delayPredChunk = c.stats.chunks;
+            c.stats.delay_flags_predicted++;
+          }
+        }
+        ns.delayAudible = n_.delayAudible;   // (an accepted node: false -- stage 2 hands its views out, Context::runTwoStageChunk)
         n_.outputs[0].bufCh = ch;
-        n_.outputs[0].silent = !n_.delayAudible;
+        n_.outputs[0].silent = !audible;
         break;
       }
       default: fail(GA_ERR_UNSUPPORTED, "node type not supported on the device path");
@@ -982,10 +1001,15 @@ struct ChunkRun {
   int stage = 0;                                 // 0: one pass over the graph; 1: the modulator cone; 2: everything else
   std::vector<std::pair<int, int>> rateMods;     // (source, param) of the modulated rates
   std::vector<int> coneRoots;                    // stage 1 of a cone with a feedback loop: where the reference's walk enters the cone, in order
+  std::vector<int> probeDelays;                  // DelayNodes whose flag this chunk reads from their samples (option "delay_flag_exact")
+  std::vector<char> stage1;                      // node id -> rendered by stage 1: the modulator cone, the accepted delays and their cones
+  bool waited = true;                            // stage 1: the host waited for the probe's words (false: nothing to read back)
+  const int32_t* onsetWords = nullptr;           // stage 1: the words of delay_onset_kernel, read back (NodeS::DelaySpan::word indexes them)
   struct PreOut { int bufCh; bool silent, zero; };
   std::vector<int> preRow;                       // stage 1: node id -> its first output's row in a snapshot, -1 = not in the cone
   std::vector<std::vector<PreOut>> preSnap;      // stage 1: [segment][row] the cone's output state
   std::vector<int64_t> preB0;                    // stage 1: segment starts
+  std::vector<int> preCh0;                       // stage 1 with accepted delays: [row] the cone's channel counts before the chunk
   const ChunkRun* pre = nullptr;                 // stage 2: stage 1
   std::vector<int> rmOf;                         // stage 2: node id -> index into rmIn, -1 = none
   std::vector<RateModIn> rmIn;
@@ -1003,6 +1027,13 @@ inline bool Sim::restorePre(int id) {
     n_.outputs[o].bufCh = q.bufCh;
     n_.outputs[o].silent = q.silent;
     n_.outputs[o].zero = q.zero;
+  }
+  if (n_.delayProbe) {   // the flag of an accepted DelayNode: down until the block in which its samples raised it (delay_onset_kernel)
+    bool silent = true;
+    for (const NodeS::DelaySpan& sp : n_.delaySpans)
+      if (sp.b0 <= brel) silent = brel < sp.onset;
+    n_.outputs[0].silent = silent;
+    n_.outputs[0].zero = false;
   }
   n_.lastProcessedBlock = blockNumber;
   return true;

@@ -204,6 +204,20 @@ struct NodeS {
   int delayCh = 0;                 // channels of `_outputBuffer` (re-rented, i.e. silent again, when the count changes)
   int delayRings = 0;              // CircularBuffers allocated so far (2 at construction, grown on demand)
   bool delayAudible = false;       // the output buffer's non-silent flag (sticky, :96-97)
+  // option "delay_flag_exact": the flag of this chunk is read from the node's output samples (Context::chunkTopology accepts the node
+  // per chunk; delay_onset_kernel).  While accepted the simulation's PREDICTED flag lives in delayShadow, not in delayAudible.
+  bool delayProbe = false;
+  bool delayShadow = false;
+  bool delayOnLoop = false;        // (chunkTopology) among the stack nodes of a back edge (a loop closed through a finished node is found by the acceptance walk)
+  struct DelaySpan {               // the blocks between two re-rents of `_outputBuffer` inside the chunk (:50-56: the flag starts down)
+    int64_t b0;                    // first block (chunk-relative)
+    int64_t rise;                  // block in which the prediction raises the flag, -1 = not in this span
+    int64_t onset;                 // block in which the samples raise it (read back), INT64_MAX = not in this span
+    int ch;
+    int word = -1;                 // index of the span's word among the chunk's onset words, -1 = no job (the prediction did not rise)
+  };
+  std::vector<DelaySpan> delaySpans;
+  int64_t delayPredChunk = -1;     // ga_stats.delay_flags_predicted counts a (delay, chunk) pair once
   float* delayHist = nullptr;      // device [rings][maxDelaySamples]: the samples written just before the current chunk
   int delayHistRings = 0;
   float* delayLine = nullptr;      // device scratch [rings][maxDelaySamples + delayCap]: history followed by the chunk's input
@@ -709,6 +723,8 @@ struct Context {
       if (!nd.params[p].modulation.empty()) return true;
     return false;
   }
+  bool delayFlagExact = false;   // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology)
+  std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (NodeS::delayProbe)
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);

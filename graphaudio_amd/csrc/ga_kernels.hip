@@ -3306,6 +3306,34 @@ void launch_delay(hipStream_t s, const DelayJob* jobs_dev, int njobs, int64_t ma
   GA_LAUNCH_JOBS(delay_kernel, gx, 256, jobs_dev, njobs);
 }
 
+// The first 128-frame block of a DelayNode's output rows that holds a sample `!= 0f` (see DelayOnsetJob).  One wave per block and
+// turn: lane l tests frames l and l + 64 of every row (rows are 4-byte aligned in general: dword loads, coalesced), a ballot says
+// whether the block holds one, lane 0 lowers the job's word.  A wave visits its blocks in rising order and stops at its first hit.
+__global__ __launch_bounds__(256) void delay_onset_kernel(const DelayOnsetJob* __restrict jobs) {
+  const DelayOnsetJob& job = jobs[blockIdx.y];   // (read in place: the row table is indexed in a loop)
+  const int lane = threadIdx.x & 63;
+  const int nrows = min(max(job.nrows, 0), kDelayOnsetRows);
+  const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); b < job.count; b += waves) {
+    const int64_t f = ((int64_t)job.first + b) * kBlock + lane;
+    unsigned bits = 0;
+    for (int r = 0; r < nrows; r++) {
+      const GA_GLOBAL float* p = gptr(job.rows[r]) + f;
+      // -0.0f is zero, a NaN and a denormal are not: the bit pattern without its sign, whatever the wave's denormal mode
+      bits |= (__float_as_uint(p[0]) << 1) | (__float_as_uint(p[64]) << 1);
+    }
+    if (__ballot(bits != 0) != 0ull) {   // (wave-uniform: every lane leaves the loop)
+      if (lane == 0) atomicMin(job.out, (int32_t)(job.first + b));
+      break;
+    }
+  }
+}
+void launch_delay_onset(hipStream_t s, const DelayOnsetJob* jobs_dev, int njobs, int64_t max_blocks) {
+  if (njobs <= 0 || max_blocks <= 0) return;
+  int gx = (int)std::min<int64_t>((max_blocks + 3) / 4, 256);
+  GA_LAUNCH_JOBS(delay_onset_kernel, gx, 256, jobs_dev, njobs);
+}
+
 
 __device__ __forceinline__ void pan_gains(float pan, int stereo, float& gl, float& gr) {   // :94-98 / :129-133
   const float PIf = 3.14159265358979323846f;

@@ -622,6 +622,19 @@ struct DelayJob {
 };
 void launch_delay(hipStream_t s, const DelayJob* jobs_dev, int njobs, int64_t max_n);
 
+// The block in which a DelayNode's output buffer becomes non-silent (option "delay_flag_exact"): the reference raises the flag at the
+// first output sample that is `!= 0f` (DelayNode.cs:72,92,96-97) -- -0.0f is zero, a NaN and a denormal are not.  `*out` (set to
+// INT32_MAX by the plan in front of the launch) becomes the first chunk block in [first, first + count) in which any of the rows
+// holds such a sample.  Rows are chunk-frame indexed (row[b * 128 .. b * 128 + 127] = block b) and readable over the whole range.
+constexpr int kDelayOnsetRows = 32;
+struct DelayOnsetJob {
+  const float* rows[kDelayOnsetRows];
+  int32_t* out;
+  int32_t first, count;
+  int32_t nrows, pad_;
+};
+void launch_delay_onset(hipStream_t s, const DelayOnsetJob* jobs_dev, int njobs, int64_t max_blocks);
+
 // AudioParam.ComputeARate / ComputeKRate with a non-silent modulation input (AudioParam.cs:123-135,148-160):
 //   a-rate: out[f] = clamp(intrinsic[f] + mod[f], min, max) ; k-rate: the block's first sample of both, repeated over the block
 struct ParamModJob {

@@ -136,6 +136,10 @@ typedef struct ga_stats {
                                    last segment were taken over (steady renders, option "sim_replay") */
   int64_t twin_rows;            /* channel rows that were not computed a second time: a mono signal in a stereo node or input is the
                                    same numbers on every channel (AudioNodeInput.cs:182-244), evaluated once (option "twin_channels") */
+  int64_t delay_flags_read;     /* option "delay_flag_exact": (DelayNode, chunk) pairs whose output flag was taken from the node's output
+                                   samples (the first sample != 0f, DelayNode.cs:72,92,96-97) */
+  int64_t delay_flags_predicted; /* (DelayNode, chunk) pairs whose output flag rose by the host's prediction while the option was on: a
+                                    delay on a feedback loop, behind another undecided delay, a modulated playbackRate or a convolver */
 } ga_stats;
 enum {
   GA_STAGE_OTHER = 0,        /* sources, biquads, gains, parameter curves, ... */

@@ -1,0 +1,132 @@
+"""Cost of option delay_flag_exact on a chorus scene: V voices, each a burst into a low-pass biquad whose second
+connection is a DelayNode (0.02 s, modulated by a 2 Hz triangle through a 0.005 gain) fed by a one-shot that starts with digital
+silence of a different length per voice, so the delays' flags rise one after the other.
+
+Renders SECONDS of audio in chunks of CHUNK blocks with the option off and on, prints frames/s for both, the chunks that waited for
+stage 1 and the mean stage-1 wait (from the library's GA_TIMING log), and whether the two outputs differ.
+
+    python tools/delay_flag_chorus.py [--voices 256] [--seconds 4] [--chunk 64]
+"""
+import argparse
+import os
+import re
+import sys
+import tempfile
+import time
+
+os.environ["GA_TIMING"] = "1"   # (read when the library is loaded)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np
+
+from graphaudio_amd import (AudioBufferSourceNode, BiQuadFilterNode, DelayNode, FilterType, GainNode, OfflineAudioContext,
+                            OscillatorNode, OscillatorType, PlayableAudioBuffer)
+
+SR = 48000
+
+
+def build_idle(ctx, voices):
+    """Voices next to DelayNodes nothing feeds: accepted chunk after chunk, never probed -- no stage-1 wait."""
+    ctx.Destination.SetChannelCount(1)
+    hold = []
+    for v in range(voices):
+        s = AudioBufferSourceNode(ctx)
+        s.Buffer = PlayableAudioBuffer.FromMonoArray((np.random.default_rng(v).standard_normal(SR) * 0.1).astype(np.float32), SR)
+        s.Loop = True
+        d = DelayNode(ctx, 0.05)
+        s.Connect(ctx.Destination)
+        d.Connect(ctx.Destination)
+        s.Start()
+        hold += [s, d]
+    return hold
+
+
+def build(ctx, voices):
+    ctx.Destination.SetChannelCount(1)
+    hold = []
+    mix = GainNode(ctx)
+    mix.Gain.Value = 1.0 / 16.0
+    mix.Connect(ctx.Destination)
+    for v in range(voices):
+        rng = np.random.default_rng(100 + v)
+        burst = AudioBufferSourceNode(ctx)
+        burst.Buffer = PlayableAudioBuffer.FromMonoArray((rng.standard_normal(384) * 0.25).astype(np.float32), SR)
+        bq = BiQuadFilterNode(ctx)
+        bq.Type = FilterType.Lowpass
+        bq.Frequency.Value = 200.0 + 3.0 * v
+        bq.Q.Value = 8.0
+        z = 805 + 37 * v
+        x = (rng.standard_normal(z + 2560) * 0.25).astype(np.float32)
+        x[:z] = 0.0
+        late = AudioBufferSourceNode(ctx)
+        late.Buffer = PlayableAudioBuffer.FromMonoArray(x, SR)
+        d = DelayNode(ctx, 0.05)
+        d.DelayTime.Value = 0.02
+        lfo = OscillatorNode(ctx)
+        lfo.Type = OscillatorType.Triangle
+        lfo.Frequency.Value = 2.0
+        depth = GainNode(ctx)
+        depth.Gain.Value = 0.005
+        lfo.Connect(depth)
+        depth.Connect(d.DelayTime)
+        burst.Connect(bq)
+        late.Connect(d)
+        d.Connect(bq)
+        bq.Connect(mix)
+        for s in (burst, late, lfo):
+            s.Start()
+        hold += [burst, bq, late, d, lfo, depth]
+    return hold
+
+
+def run(voices, frames, chunk, on, build=build):
+    ctx = OfflineAudioContext(SR)
+    ctx.SetOption("max_chunk_blocks", chunk)
+    ctx.SetOption("delay_flag_exact", 1 if on else 0)
+    hold = build(ctx, voices)
+    out = np.zeros((1, frames), np.float32)
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+b") as log:   # the library writes its timing lines to the process's stderr
+        os.dup2(log.fileno(), 2)
+        try:
+            t0 = time.perf_counter()
+            ctx.Render(out, frames)
+            dt = time.perf_counter() - t0
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        log.seek(0)
+        text = log.read().decode("ascii", "replace")
+    waits = [float(m) for m in re.findall(r"stage 1 wait ([0-9.]+) ms", text)]
+    st = ctx.GetStats()
+    del hold
+    ctx.Dispose()
+    return out, dt, waits, st
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voices", type=int, default=256)
+    ap.add_argument("--seconds", type=float, default=4.0)
+    ap.add_argument("--chunk", type=int, default=64)
+    ap.add_argument("--idle", action="store_true", help="the idle-delay scene instead: the option must cost no stage-1 wait")
+    a = ap.parse_args()
+    scene = build_idle if a.idle else build
+    frames = int(a.seconds * SR) // 128 * 128
+    run(min(a.voices, 8), 128 * 64, a.chunk, True, scene)   # (warm-up: module load, allocations)
+    res = {}
+    for on in (0, 1):
+        out, dt, waits, st = run(a.voices, frames, a.chunk, on, scene)
+        res[on] = out
+        print(f"delay_flag_exact={on}: {frames / dt:,.0f} frames/s ({dt * 1e3:.1f} ms for {frames} frames, {st['chunks']} chunks), "
+              f"chunks that waited for stage 1: {len(waits)}, mean wait {np.mean(waits) if waits else 0.0:.3f} ms, "
+              f"flags read {st['delay_flags_read']}, predicted {st['delay_flags_predicted']}")
+    if a.idle:
+        return
+    d = res[0] - res[1]
+    print(f"outputs differ by {float(np.sqrt(np.mean(d * d))):.3e} RMS on {float(np.sqrt(np.mean(res[1] ** 2))):.3e} RMS")
+
+
+if __name__ == "__main__":
+    main()
