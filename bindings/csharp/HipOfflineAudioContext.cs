@@ -68,7 +68,7 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
     private bool _spatialParamSignals;
     /// <summary>Option "spatial_param_signals" (default off): signals connected to the AudioParams of a Hip.SpatialPannerNode are
     /// rendered -- the node's per-block descriptors are then made on the device.  Off: such a connection makes Render throw
-    /// NotSupportedException before anything moves.  A signal on Occlusion is refused either way.</summary>
+    /// NotSupportedException before anything moves.  A signal on Occlusion is refused unless SpatialOcclusion is on too.</summary>
     public bool SpatialParamSignals
     {
         get => _spatialParamSignals;
@@ -76,6 +76,21 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         {
             GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "spatial_param_signals", value ? 1 : 0));
             _spatialParamSignals = value;
+        }
+    }
+
+    private bool _spatialOcclusion;
+    /// <summary>Option "spatial_occlusion" (default off): Occlusion above 0 and TransmissionLow / Mid / High of a Hip.SpatialPannerNode
+    /// are rendered -- 0 is open air, 1 fully blocked, a transmission the share of its band that passes the obstacle; the stage is
+    /// this library's own definition (three bands split at 800 Hz and 8 kHz), not Steam Audio's.  Off: an Occlusion above 0 makes
+    /// Render throw NotSupportedException before anything moves.  A signal on Occlusion needs SpatialParamSignals as well.</summary>
+    public bool SpatialOcclusion
+    {
+        get => _spatialOcclusion;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "spatial_occlusion", value ? 1 : 0));
+            _spatialOcclusion = value;
         }
     }
 

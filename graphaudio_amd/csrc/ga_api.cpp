@@ -385,6 +385,7 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "resample_fast") c.resampleFast = value != 0;
     else if (k == "rate_mod_walk") c.rateModWalk = value != 0;
     else if (k == "spatial_param_signals") c.spatialParamSignals = value != 0;
+    else if (k == "spatial_occlusion") c.spatialOcclusion = value != 0;
     else if (k == "delay_flag_exact") c.delayFlagExact = value != 0;
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);

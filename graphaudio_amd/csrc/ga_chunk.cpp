@@ -411,7 +411,7 @@ void Context::chunkTopology(ChunkRun& r) {
         if (nd.params[p].modulation.empty()) continue;
         if (!spatialParamSignals)
           fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to parameter " + std::to_string(p) + " (signals on the node's parameters are not on the device path)");
-        if (p == 13)   // (its values exist on the device alone: the host cannot show that occlusion stays at 0)
+        if (p == 13 && !spatialOcclusion)   // (its values exist on the device alone: the host cannot show that occlusion stays at 0)
           fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to occlusion (Steam Audio's occlusion / three-band transmission filters are not known here, "
                                          "and a signal's values cannot be shown to stay at 0)");
       }
@@ -425,7 +425,7 @@ void Context::chunkTopology(ChunkRun& r) {
         double t = currentTime;   // the accumulated block clock (AudioContextBase.cs:78-79), as chunkSimulate builds it
         for (int64_t b = 0; b < r.n && !occluded; b++, t += increment) occluded = param_value_at(oc.events.data(), (int)oc.events.size(), oc.value, t) > 0.0f;
       }
-      if (occluded)
+      if (occluded && !spatialOcclusion)
         fail(GA_ERR_UNSUPPORTED, who + "occlusion > 0 (Steam Audio's occlusion / three-band transmission filters are not known here)");
     }
   }
@@ -467,7 +467,14 @@ void Context::chunkTopology(ChunkRun& r) {
         }
         nd.spPrev.g = tmp.g;
         nd.spPrev.beta = tmp.beta;
+        if (nd.spEqOnDevice && nd.spDirect) {   // ... and the previous triple with the run flags of the band filters
+          SpatialDirectState ds;
+          GA_HIP(hipMemcpy(&ds, nd.spDirect, sizeof(SpatialDirectState), hipMemcpyDeviceToHost));
+          nd.spEq = ds.prev;
+          nd.spEqOpen = (ds.open[0] ? 1 : 0) | (ds.open[1] ? 2 : 0);
+        }
       }
+      nd.spEqOnDevice = false;
       nd.spOnDevice = false;
       apiEpoch++;
     }

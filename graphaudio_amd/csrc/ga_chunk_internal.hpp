@@ -587,6 +587,7 @@ struct Exec {
   size_t spatialJobsOff = 0;               // where the job table ends up (put when the chunk's tables are complete: chunkExecute)
   double spatialFma = 0;                   // fused multiply-adds of the level's workgroups
   std::vector<SpatialDescJob> spatialDescJobs;   // signal-driven spatial nodes of the level being planned (spatial_desc_kernel)
+  std::vector<SpatialDirectJob> spatialDirectJobs;   // option "spatial_occlusion": the level's nodes with an active block in the segment (spatial_direct_kernel)
   std::vector<ParamModJob> pmodJobs;
   std::vector<ResampleBlock> traj;  // per-chunk trajectory table (all rates + custom tail blocks)
   bool mixAligned = true;
@@ -911,6 +912,12 @@ struct Exec {
     std::memcpy(ls.v, c.listener, sizeof(ls.v));
     flush(spatialDescJobs, LK_OTHER, &SpatialDescJob::nb, [=](const SpatialDescJob* t, int nj, int64_t mx, uint8_t* base) {
       launch_spatial_desc(st, t, nj, (int)mx, base, ls);
+    });
+    // occlusion / transmission of the level's panners that have an active block: behind the descriptors (the triples of the
+    // signal-driven nodes), in front of the panners (which read x' through their input views)
+    const SpatialBands bands = c.spBands;
+    flush(spatialDirectJobs, LK_OTHER, &SpatialDirectJob::nb, [=](const SpatialDirectJob* t, int nj, int64_t mx, uint8_t* base) {
+      launch_spatial_direct(st, t, nj, (int)mx, base, bands);
     });
     // all spatial panners of the level: one launch (the job table is put when the chunk's tables are complete: chunkExecute)
     if (!spatialWorks.empty()) c.noteKernel(LK_OTHER, "spatial_panner_kernel");

@@ -243,6 +243,7 @@ Context::~Context() {
     if (np && np->spHist[1]) (void)hipFree(np->spHist[1]);
     if (np && np->spCarry[0]) (void)hipFree(np->spCarry[0]);
     if (np && np->spCarry[1]) (void)hipFree(np->spCarry[1]);
+    if (np && np->spDirect) (void)hipFree(np->spDirect);
   }
   for (auto& kv : tw16) (void)hipFree(kv.second);
   if (rateModDev) (void)hipFree(rateModDev);
@@ -579,7 +580,12 @@ void Context::doDispose(int id) {
         h = nullptr;
       }
     }
-    n.spOnDevice = false;
+    if (n.spDirect) {
+      if (stream) (void)hipStreamSynchronize(stream);
+      dfree(n.spDirect, sizeof(SpatialDirectState));
+      n.spDirect = nullptr;
+    }
+    n.spOnDevice = n.spEqOnDevice = false;
     n.irBuf = -1;
     n.hrirRequested = -1;
   }

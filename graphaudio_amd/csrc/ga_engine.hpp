@@ -343,6 +343,16 @@ struct NodeS {
   int spCarryCur = 0;
   bool spOnDevice = false;
   bool spSignals = false;                  // per chunk (Context::chunkTopology): this chunk's descriptors are made on the device
+  // Occlusion and transmission (option "spatial_occlusion"): the EQ triple of the previous processed block (valid as spPrev.valid) and,
+  // per input channel (bit ch), whether that block was active -- its run of the band filters continues.  The filters' states live in
+  // spDirect on the device; while spEqOnDevice is set (a signal-driven node) the triple and the run flags live there as well and
+  // come back with spCarry.
+  SpatialEq spEq{1.0f, 0.0f, 0.0f};
+  int spEqOpen = 0;
+  SpatialDirectState* spDirect = nullptr;
+  bool spEqOnDevice = false;
+  size_t spEqOff = 0;                      // per chunk: the node's SpatialEqEntry table (spEqSeq == Context::chunkSeq)
+  uint64_t spEqSeq = ~0ull;
   uint64_t spCurveOff[kSpatialParams] = {};   // per chunk: the per-block values of the parameters on timelines (kSpatialNoCurve: none)
   // per chunk (valid while spSeq == Context::chunkSeq and spExec is the chunk's executor): where the node's tables and job live
   uint64_t spSeq = ~0ull;
@@ -723,6 +733,9 @@ struct Context {
       if (!nd.params[p].modulation.empty()) return true;
     return false;
   }
+  bool spatialOcclusion = false;      // option "spatial_occlusion": occlusion > 0 and the three-band transmission are rendered (spatial_direct_kernel); 0 = refused
+  SpatialBands spBands{};             // the band filters of that stage: fixed per context (made when the first job is planned)
+  bool spBandsMade = false;
   bool delayFlagExact = false;   // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology)
   std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (NodeS::delayProbe)
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
@@ -818,6 +831,8 @@ struct Context {
   void planDelay(NodePlanCtx& k);
   void planStereoPanner(NodePlanCtx& k);
   void planSpatialPanner(NodePlanCtx& k);
+  void planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, NodeS& nd, const SpatialEq& prev, int open, bool prevValid);
+  void spatialEqTable(Exec& ex, NodeS& nd, int64_t n);
   // SpatialPannerNode: geometry of one block (SpatialPannerNode.cs:133-204,263-284 in float32) -> HRIR indices, weights, g, beta
   void spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& out) const;
   float spatialParamAt(const NodeS& nd, int p, double t) const;   // the k-rate value of a block: sample 0 of the timeline (event values are clamped when they are scheduled)

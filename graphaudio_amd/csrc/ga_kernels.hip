@@ -3213,7 +3213,7 @@ void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nwor
 //  block's inputs (blocks b0 + 1 ..), or read from the carried descriptor an earlier launch or the host left (block b0).
 //  The job is read through the uniform pointer (scalar loads), the parameter loops are unrolled: no scratch.
 // ======================================================================================================
-__device__ __forceinline__ void spatial_desc_geometry(const SpatialDescJob& job, const uint8_t* tables, const SpatialListener& L, int b, SpatialGeom& o) {
+__device__ __forceinline__ void spatial_desc_geometry(const SpatialDescJob& job, const uint8_t* tables, const SpatialListener& L, int b, SpatialGeom& o, SpatialEq& eq) {
   float pv[kSpatialParams];
 #pragma unroll
   for (int p = 0; p < kSpatialParams; p++) {
@@ -3223,6 +3223,11 @@ __device__ __forceinline__ void spatial_desc_geometry(const SpatialDescJob& job,
     pv[p] = v;
   }
   spatial_geometry<SpatialMathDouble>(pv, L.v, job.model, job.azimuths, job.dirs, o);
+  if (job.eq_off != kSpatialNoCurve) {   // option "spatial_occlusion": the largest band factor joins g, the rest is the block's EQ triple
+    float s;
+    spatial_occlusion(pv[13], pv[14], pv[15], pv[16], s, eq);
+    o.g = o.g * s;
+  }
 }
 __global__ __launch_bounds__(64) void spatial_desc_kernel(const SpatialDescJob* __restrict jobs, uint8_t* __restrict tables, SpatialListener L) {
   const SpatialDescJob& job = jobs[blockIdx.y];
@@ -3232,10 +3237,11 @@ __global__ __launch_bounds__(64) void spatial_desc_kernel(const SpatialDescJob* 
   GA_GLOBAL SpatialDesc* desc = gptr((SpatialDesc*)(tables + job.desc_off));
   const int dmax = max(job.dirs, 1) - 1;
   SpatialGeom cur, pr;
-  spatial_desc_geometry(job, tables, L, b, cur);
+  SpatialEq eq{1.0f, 0.0f, 0.0f}, eqPr;
+  spatial_desc_geometry(job, tables, L, b, cur, eq);
   bool have = false;
   if (i > 0) {
-    spatial_desc_geometry(job, tables, L, b - 1, pr);
+    spatial_desc_geometry(job, tables, L, b - 1, pr, eqPr);
     have = true;
   } else if (job.prev_valid) {
     SpatialCarry c = job.prev_host;
@@ -3273,6 +3279,12 @@ __global__ __launch_bounds__(64) void spatial_desc_kernel(const SpatialDescJob* 
   d->gb = cur.g * cur.beta;
   d->dry = cur.g * (1.0f - cur.beta);
   d->flags = (d->flags & ~1) | (fade ? 1 : 0);
+  if (job.eq_off != kSpatialNoCurve) {
+    GA_GLOBAL SpatialEqEntry* e = gptr((SpatialEqEntry*)(tables + job.eq_off)) + b + 1;
+    e->c.cM = eq.cM;
+    e->c.cL = eq.cL;
+    e->c.cH = eq.cH;
+  }
   if (i == job.nb - 1) {
     GA_GLOBAL SpatialCarry* po = gptr(job.prev_out);
     for (int q = 0; q < 4; q++) {
@@ -3287,6 +3299,113 @@ void launch_spatial_desc(hipStream_t s, const SpatialDescJob* jobs_dev, int njob
   if (njobs <= 0 || max_nb <= 0) return;
   const int gx = (max_nb + 63) / 64;
   GA_LAUNCH_JOBS(spatial_desc_kernel, gx, 64, jobs_dev, njobs, tables_dev, listener);
+}
+
+// ======================================================================================================
+//  SpatialPannerNode occlusion / three-band transmission (ga_kernels.hpp, SpatialDirectJob; DESIGN.md "SpatialPannerNode",
+//  "Occlusion and transmission"): x' of every input channel in front of spatial_panner_kernel.  One lane per (node, channel)
+//  walks the chunk's blocks in time order with both one-pole recurrences in registers -- serial in time on purpose: every sample
+//  is the same chain however the render is cut into chunks; nodes and channels are the parallel axis.  One wavefront per
+//  workgroup serves kSpatialDirectRows rows (8 nodes): few rows per wave, because the walk is latency bound and a level of a
+//  thousand nodes should reach every CU.  Per block the wave stages its rows' 128 frames through a [16][129] LDS tile in both
+//  directions (row r is read and written by all 64 lanes at consecutive addresses; lane l < 16 then walks tile[l][.], bank
+//  (l + n) mod 64: no conflict), so no lane walks its own global row.  A block that is not active passes through the tile unchanged.
+// ======================================================================================================
+constexpr int kSpatialDirectRows = 16;   // (node, channel) rows per wavefront
+__global__ __launch_bounds__(64) void spatial_direct_kernel(const SpatialDirectJob* __restrict jobs, int njobs, int max_nb,
+                                                            const uint8_t* __restrict tables, SpatialBands K) {
+  __shared__ float tile[kSpatialDirectRows][kBlock + 1];
+  __shared__ const float* src[kSpatialDirectRows];
+  __shared__ float* dst[kSpatialDirectRows];
+  const int lane = threadIdx.x, ch = lane & 1;
+  const int ji = (int)blockIdx.x * (kSpatialDirectRows / 2) + (lane >> 1);
+  const bool mine = lane < kSpatialDirectRows && ji < njobs;
+  const SpatialDirectJob& job = jobs[mine ? ji : 0];
+  const float* const inp = job.in[ch];
+  float* const outp = job.out[ch];
+  const bool walks = mine && inp != nullptr;   // (lane 1 of a mono segment has nothing to do: its run is not open afterwards)
+  const int nb = walks ? job.nb : 0;
+  const int64_t fA = (int64_t)job.b0 * kBlock;
+  const GA_GLOBAL SpatialEqEntry* eqs = gptr((const SpatialEqEntry*)(tables + job.eq_off)) + job.b0 + 1;
+  GA_GLOBAL SpatialDirectState* st = gptr(job.state);
+  float zl = 0.f, zh = 0.f;
+  SpatialEq pr{1.0f, 0.0f, 0.0f};
+  bool have = false, open = false;
+  if (walks) {
+    have = job.prev_valid != 0;
+    if (job.from_state) {
+      pr.cM = st->prev.cM;
+      pr.cL = st->prev.cL;
+      pr.cH = st->prev.cH;
+      open = st->open[ch] != 0;
+    } else {
+      pr = job.prev;
+      open = ((job.open >> ch) & 1) != 0;
+    }
+    open = open && have;
+    if (open) {
+      zl = st->zl[ch];
+      zh = st->zh[ch];
+    }
+  }
+  for (int b = 0; b < max_nb; b++) {
+    const bool on = b < nb;
+    if (lane < kSpatialDirectRows) {
+      src[lane] = on ? inp + fA + (int64_t)b * kBlock : nullptr;
+      dst[lane] = on ? outp + fA + (int64_t)b * kBlock : nullptr;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int r = 0; r < kSpatialDirectRows; r++) {
+      const float* p = src[r];
+      if (p) {
+        tile[r][lane] = gptr(p)[lane];
+        tile[r][64 + lane] = gptr(p)[64 + lane];
+      }
+    }
+    __syncthreads();
+    if (on) {
+      SpatialEq cur;
+      cur.cM = eqs[b].c.cM;
+      cur.cL = eqs[b].c.cL;
+      cur.cH = eqs[b].c.cH;
+      if (!have) pr = cur;   // the first processed block after creation or silence: its own triple alone
+      const bool active = !spatial_eq_identity(cur) || !spatial_eq_identity(pr);
+      if (active) {
+        if (!open) zl = zh = 0.f;   // the first block of a run of active blocks
+#pragma unroll 8
+        for (int n = 0; n < kBlock; n++) tile[lane][n] = spatial_direct_step(K, spatial_eq_at(pr, cur, n), tile[lane][n], zl, zh);
+      }
+      open = active;
+      have = true;
+      pr = cur;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int r = 0; r < kSpatialDirectRows; r++) {
+      float* p = dst[r];
+      if (p) {
+        gptr(p)[lane] = tile[r][lane];
+        gptr(p)[64 + lane] = tile[r][64 + lane];
+      }
+    }
+    __syncthreads();
+  }
+  if (mine) {
+    st->zl[ch] = zl;
+    st->zh[ch] = zh;
+    st->open[ch] = (walks && open) ? 1 : 0;
+    if (ch == 0) {
+      st->prev.cM = pr.cM;
+      st->prev.cL = pr.cL;
+      st->prev.cH = pr.cH;
+    }
+  }
+}
+void launch_spatial_direct(hipStream_t s, const SpatialDirectJob* jobs_dev, int njobs, int max_nb, const uint8_t* tables_dev, const SpatialBands& bands) {
+  if (njobs <= 0 || max_nb <= 0) return;
+  const int per = kSpatialDirectRows / 2;
+  hipLaunchKernelGGL(spatial_direct_kernel, dim3((njobs + per - 1) / per), dim3(64), 0, s, jobs_dev, njobs, max_nb, tables_dev, bands);
 }
 
 

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "ga_spatial_geom.hpp"
+#include "ga_spatial_direct.hpp"
 
 namespace ga {
 
@@ -710,9 +711,39 @@ struct SpatialDescJob {   // one signal-driven node over one segment of a chunk 
   uint64_t curve_off[kSpatialParams];   // or its per-block values float[nblocks] in the chunk's tables (kSpatialNoCurve: none)
   const float* mod[kSpatialParams];     // channel 0 of the mixed modulation input, chunk-frame indexed (null: silent in this segment)
   float vmin[kSpatialParams], vmax[kSpatialParams];
+  uint64_t eq_off;        // option "spatial_occlusion": the node's SpatialEqEntry[nblocks + 1] (kSpatialNoCurve: occlusion is not rendered)
 };
 struct SpatialListener { float v[12]; };   // origin, right, up, ahead
 void launch_spatial_desc(hipStream_t s, const SpatialDescJob* jobs_dev, int njobs, int max_nb, uint8_t* tables_dev, const SpatialListener& listener);
+
+// Occlusion and three-band transmission (option "spatial_occlusion"; DESIGN.md "SpatialPannerNode", "Occlusion and transmission"):
+// spatial_direct_kernel makes x' = cM x + cL lo(x) + cH hi(x) per input channel in front of spatial_panner_kernel, which then reads
+// x' through the node's SpatialSeg views.  One lane per (node, input channel) walks the chunk's blocks in time order; the triple
+// ramps from the previous processed block's to the block's own.  A block is active when either triple is not the identity; the
+// band filters run in active blocks only, from zero state at the first block of a run of active blocks.  Blocks that are not
+// active are copied (a segment without a job keeps its input views).  The job decides all of that from the triples it reads, whoever made them (host or spatial_desc_kernel).
+struct SpatialEqEntry {   // one per block, entry b + 1 = block b (as SpatialDesc); entry 0 is not used (the carried triple is in the job / the state)
+  SpatialEq c;
+  int pad_;
+};
+struct SpatialDirectState {   // per node, on the device: what a chunk leaves for the next one
+  float zl[2], zh[2];     // the filters' states per input channel (of a run that is open)
+  SpatialEq prev;         // the triple of the last processed block (valid as SpatialPrev::valid says)
+  int open[2];            // per channel: the last block was active and held the channel -- its run continues
+  int pad_;
+};
+struct SpatialDirectJob {   // one node over one segment of a chunk (every block of it is processed); lanes 2 j and 2 j + 1 are its input channels
+  const float* in[2];     // the node's input views of the segment, chunk-frame indexed (in[1] null: mono)
+  float* out[2];          // x' of both channels, chunk-frame indexed: what the node's SpatialSeg entry of the segment points at
+  uint64_t eq_off;        // the node's SpatialEqEntry[nblocks + 1]
+  SpatialDirectState* state;
+  SpatialEq prev;         // the carried triple and run flags (bit ch) where the host holds them ...
+  int open;
+  int from_state;         // ... != 0: they are read from `state` (a signal-driven node: an earlier launch left them)
+  int prev_valid;         // block b0 has a previous processed block
+  int b0, nb;             // blocks [b0, b0 + nb) of the chunk
+};
+void launch_spatial_direct(hipStream_t s, const SpatialDirectJob* jobs_dev, int njobs, int max_nb, const uint8_t* tables_dev, const SpatialBands& bands);
 
 // ProcessBlockInterleaved (AudioContextBase.cs:125-155): dst[(f0 + i) * channels + ch] = ch < used ? src[ch][f0 + i] : 0
 struct InterleaveSrc {

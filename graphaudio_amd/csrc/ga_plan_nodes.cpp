@@ -266,6 +266,44 @@ void Context::spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::Sp
   o.valid = true;
 }
 
+// Occlusion and transmission (option "spatial_occlusion"): one job of spatial_direct_kernel for the node over this segment.  x' goes to
+// two chunk planes of the node's own, and the panner's input views of the segment (sgs[si]) are redirected to them.  `prev`, `open`
+// and `prevValid` are the carried state at the segment's first block.
+void Context::planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, NodeS& nd, const SpatialEq& prev, int open, bool prevValid) {
+  if (!spBandsMade) {
+    spBands = spatial_bands(sampleRate);
+    spBandsMade = true;
+  }
+  if (!nd.spDirect) {
+    nd.spDirect = (SpatialDirectState*)dalloc(sizeof(SpatialDirectState));
+    GA_HIP(hipMemsetAsync(nd.spDirect, 0, sizeof(SpatialDirectState), stream));
+  }
+  SpatialSeg* sgs = (SpatialSeg*)&ex.plan.host[nd.spSegOff];
+  SpatialDirectJob j{};
+  j.in[0] = sgs[si].in_l;
+  j.in[1] = sgs[si].in_r;
+  j.out[0] = ex.inMixed(ns.id, 250, 0);
+  j.out[1] = j.in[1] ? ex.inMixed(ns.id, 250, 1) : nullptr;
+  j.eq_off = nd.spEqOff;
+  j.state = nd.spDirect;
+  j.prev = prev;
+  j.open = open;
+  j.from_state = nd.spEqOnDevice ? 1 : 0;
+  j.prev_valid = prevValid ? 1 : 0;
+  j.b0 = (int)sg.b0;
+  j.nb = (int)(sg.b1 - sg.b0);
+  sgs[si].in_l = j.out[0];
+  sgs[si].in_r = j.out[1];
+  ex.spatialDirectJobs.push_back(j);
+}
+// the node's per-block triples of this chunk: every entry the identity until a segment fills its blocks in
+void Context::spatialEqTable(Exec& ex, NodeS& nd, int64_t n) {
+  if (nd.spEqSeq == chunkSeq && nd.spExec == &ex) return;
+  std::vector<SpatialEqEntry> eqs((size_t)n + 1, SpatialEqEntry{SpatialEq{1.0f, 0.0f, 0.0f}, 0});
+  nd.spEqOff = ex.plan.putv(eqs);
+  nd.spEqSeq = chunkSeq;
+}
+
 // One descriptor per block, made here (not in the simulation, so that a moving source does not cut the chunk into one-block
 // segments for every other node), the segment's workgroups, and -- in the chunk's last segment -- the history of the next chunk.
 void Context::planSpatialPanner(NodePlanCtx& k) {
@@ -301,6 +339,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
         nd.spCurveOff[p] = ex.plan.putv(curve);
       }
     }
+    nd.spEqSeq = ~0ull;   // (the triples' table is made by the first segment that has a job for spatial_direct_kernel)
     std::vector<SpatialDesc> descs((size_t)n + 1);
     std::memset(descs.data(), 0, descs.size() * sizeof(SpatialDesc));
     for (auto& d : descs) d.seg = -1;
@@ -333,6 +372,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
   bool tailDone = false;
   if (ns.ins[0].silent) {   // SteamAudioNodeBase.cs:61-66: cleared output, nothing else runs; the history receives zeros
     nd.spPrev.valid = false;
+    nd.spEqOpen = 0;          // (a silent input block ends a run of the band filters and drops the previous triple)
   } else {
     auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
     const bool stereo = ns.panMode == 2;
@@ -342,9 +382,14 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
     SpatialDesc* descs = (SpatialDesc*)&ex.plan.host[nd.spDescOff];
     if (nd.spSignals) {
       // One job of spatial_desc_kernel for this segment.  The modulation inputs are mixed by this level's mix jobs; the kernel reads
-      // sample 0 of every block (no per-frame curve is made for these k-rate parameters).  Signals on occlusion (refused) and on
-      // transmissionLow / Mid / High (no effect while occlusion is 0) are not resolved: the geometry reads parameters 0 .. 12.
+      // sample 0 of every block (no per-frame curve is made for these k-rate parameters).  Without option "spatial_occlusion", signals
+      // on occlusion (refused) and on transmissionLow / Mid / High (no effect while occlusion is 0) are not resolved: the geometry
+      // reads parameters 0 .. 12.  With it the kernel reads all 17, folds the largest band factor into g and writes the block's triple;
+      // the node always gets a job of spatial_direct_kernel, which decides from the triples what it has to do.
+      const int lastParam = spatialOcclusion ? GA_SPATIAL_PARAM_COUNT - 1 : 12;
+      if (spatialOcclusion) spatialEqTable(ex, nd, n);
       SpatialDescJob dj{};
+      dj.eq_off = spatialOcclusion ? nd.spEqOff : kSpatialNoCurve;
       dj.desc_off = nd.spDescOff;
       dj.b0 = (int)sg.b0;
       dj.nb = (int)(sg.b1 - sg.b0);
@@ -367,7 +412,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
         dj.vmin[p] = ps.minv;
         dj.vmax[p] = ps.maxv;
         dj.mod[p] = nullptr;
-        if (p <= 12 && !ns.pinSilent(p)) {
+        if (p <= lastParam && !ns.pinSilent(p)) {
           auto mv = ex.resolveInSeg((int)si, ns.id, -1 - p, ns.pins[p], false, nullptr);
           dj.mod[p] = (!mv.empty() && mv[0]) ? mv[0] : nullptr;
         }
@@ -383,17 +428,42 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
       nd.spCarryCur ^= 1;
       if (!nd.spOnDevice) deviceStateNodes.push_back(ns.id);
       nd.spOnDevice = true;
+      if (spatialOcclusion) {
+        planSpatialDirect(ex, si, sg, ns, nd, nd.spEq, nd.spEqOpen, nd.spPrev.valid);
+        nd.spEqOnDevice = true;   // (from here on the previous triple and the run flags are what the kernel left in spDirect)
+      }
       nd.spPrev.valid = true;
     }
     bool moving = false;
     for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) moving = moving || !nd.params[p].events.empty();
     NodeS::SpatialPrev cur;
     const int T = (int)hb->length;
+    // option "spatial_occlusion": the block's EQ triple beside its descriptor; the segment gets a job of spatial_direct_kernel when one
+    // of its blocks is active (its own triple or the previous processed block's is not the identity)
+    const bool occl = spatialOcclusion && !nd.spSignals;
+    const SpatialEq eqStart = nd.spEq;
+    const int openStart = nd.spEqOpen;
+    const bool validStart = nd.spPrev.valid;
+    SpatialEq eqCur{1.0f, 0.0f, 0.0f};
+    std::vector<SpatialEq> eqv;
+    bool anyActive = false;
     for (int64_t b = sg.b0; b < sg.b1 && !nd.spSignals; b++) {
       if (moving || b == sg.b0) {
         float pv[GA_SPATIAL_PARAM_COUNT];
         for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) pv[p] = spatialParamAt(nd, p, k.r.bt[b]);
         spatialGeometry(nd, pv, D, cur);
+        if (occl) {
+          float s;
+          spatial_occlusion(pv[13], pv[14], pv[15], pv[16], s, eqCur);
+          cur.g = cur.g * s;
+        }
+      }
+      if (occl) {
+        const bool active = !spatial_eq_identity(eqCur) || (nd.spPrev.valid && !spatial_eq_identity(nd.spEq));
+        anyActive = anyActive || active;
+        nd.spEq = eqCur;
+        nd.spEqOpen = active ? (stereo ? 3 : 1) : 0;
+        eqv.push_back(eqCur);
       }
       const NodeS::SpatialPrev& pr = nd.spPrev;
       bool fade = false;
@@ -412,6 +482,12 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
       d.flags = (fade ? 1 : 0) | (stereo ? 2 : 0);
       nd.spPrev = cur;
       ex.spatialFma += (double)kBlock * T * (fade ? 4.0 : 2.0) + 8.0 * T;
+    }
+    if (anyActive) {
+      spatialEqTable(ex, nd, n);
+      SpatialEqEntry* eqs = (SpatialEqEntry*)&ex.plan.host[nd.spEqOff];
+      for (int64_t b = sg.b0; b < sg.b1; b++) eqs[b + 1].c = eqv[(size_t)(b - sg.b0)];
+      planSpatialDirect(ex, si, sg, ns, nd, eqStart, openStart, validStart);
     }
     for (int64_t b0 = sg.b0; b0 < sg.b1; b0 += kSpatialRun) {
       const int nb = (int)std::min<int64_t>(kSpatialRun, sg.b1 - b0);

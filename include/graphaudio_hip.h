@@ -79,7 +79,12 @@ enum { /* node types creatable through ga_node_create; the destination is always
      ga_param_set_value / ga_param_get_value only (scheduling calls and ga_node_connect_param return GA_ERR_INVALID_ARGUMENT):
      17 = distanceModel (GA_DISTANCE_*), 18 = hrirAzimuths (integer A >= 1, default 1).  The HRIR set is assigned with
      ga_convolver_set_buffer.  The binaural stage is defined in DESIGN.md ("SpatialPannerNode"); the listener transform is the
-     twelve ga_set_option keys listener_{origin,right,up,ahead}_{x,y,z} (identity of SteamAudioContext.cs:45-54 by default). */
+     twelve ga_set_option keys listener_{origin,right,up,ahead}_{x,y,z} (identity of SteamAudioContext.cs:45-54 by default).
+     ga_set_option(ctx, "spatial_occlusion", 1) (default 0) renders occlusion > 0 and transmissionLow/Mid/High: occlusion is the
+     blocked share (0 = open air, 1 = fully blocked), a transmission the share of its band that passes the obstacle; the largest
+     band factor becomes a plain gain, the rest a three-band EQ of the input in front of the binaural stage (one-pole bands at 800 Hz
+     and 8 kHz; DESIGN.md "SpatialPannerNode", "Occlusion and transmission").  With 0, ga_render answers GA_ERR_UNSUPPORTED where
+     occlusion is above 0 in a block of the chunk.  A signal on occlusion needs "spatial_param_signals" = 1 as well. */
   GA_NODE_SPATIAL_PANNER = 12
 };
 enum { GA_DISTANCE_LINEAR = 0, GA_DISTANCE_INVERSE = 1, GA_DISTANCE_EXPONENTIAL = 2 };   /* SpatialPannerNode.DistanceModelType, SpatialPannerNode.cs:42-47 */

@@ -60,14 +60,16 @@ elif which == "osc":   # oscillators + panners (8(f) rank 1 nodes at scale)
         o.Connect(p).Connect(g).Connect(ctx.Destination)
         o.Start()
     ch = 2
-elif which == "spatial":   # SpatialPannerNode at scale: every voice through its own node, moving, so that every block crossfades
-    import math
+elif which in ("spatial", "spatial_occlusion"):   # SpatialPannerNode at scale: every voice through its own node, moving, so that every block crossfades
+    import math                                    # spatial_occlusion: every node behind a wall as well (option spatial_occlusion: spatial_direct_kernel)
     from graphaudio_amd import AudioBufferSourceNode, HrirSet, PlayableAudioBuffer, SpatialPannerNode
     n_voices = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
     T, A, E = 256, 24, 7
     k = np.arange(T)
     hrir = (np.random.default_rng(5).standard_normal((A * E, 2, T)) * np.exp(-6.9 * k / T) * 0.1).astype(np.float32)
     ctx.SetHrir(HrirSet.FromArray(hrir, SR), A)
+    if which == "spatial_occlusion":
+        ctx.SetOption("spatial_occlusion", 1)
     corners, period = 32, 5.0   # a circle as a 32-gon of linear ramps, one revolution per 5 s
     for v in range(n_voices):
         s = AudioBufferSourceNode(ctx)
@@ -75,6 +77,9 @@ elif which == "spatial":   # SpatialPannerNode at scale: every voice through its
         p = SpatialPannerNode(ctx)
         radius, phase = 1.5 + 2.0 * (v % 17) / 17.0, 2.0 * math.pi * v / n_voices
         p.PositionY.Value = -1.0 + 2.0 * (v % 5) / 4.0
+        if which == "spatial_occlusion":
+            p.Occlusion.Value = 1.0
+            p.TransmissionLow.Value, p.TransmissionMid.Value, p.TransmissionHigh.Value = 0.9, 0.5, 0.1
         for c in range(int(math.ceil(seconds / period * corners)) + 1):
             a, t = phase + 2.0 * math.pi * c / corners, c * period / corners
             first = c == 0
@@ -125,7 +130,7 @@ for rep in range(4):   # the first pieces carry one-time costs (formulation assi
 st = ctx.GetStats()
 print(json.dumps({k: st[k] for k in ("chunks", "segments", "kernel_launches", "device_ms_total", "mac_ms_total", "fft_ms_total", "other_ms_total", "device_bytes_in_use")}))
 print("rms", G.rms(out))
-if which in ("spatial", "spatial_signals"):   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
+if which in ("spatial", "spatial_signals", "spatial_occlusion"):   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
     ms, flops = st["stage_ms"][0], st["stage_flops"][0]
     print(f"stage other ({st['stage_kernel'][0]}): {ms:.2f} ms over {st['profiled_chunks']} chunks, {flops / 2 / 1e9:.1f} G fma, "
           f"{flops / 2 / max(ms, 1e-9) / 1e9:.2f} T fma/s = {flops / 2 / max(ms, 1e-9) / 1e9 / 78.65 * 100:.1f} % of the fp32 vector peak (all 'other' kernels in the time)")
