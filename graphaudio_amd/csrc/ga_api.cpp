@@ -58,11 +58,6 @@ int guard(ga_context* h, F&& f) {   // everything else: the next chunk simulates
   if (h) h->c.apiEpoch++;
   return guardRO(h, std::forward<F>(f));
 }
-NodeS* typed(Context& c, int id, int type) {
-  NodeS* n = c.node(id);
-  if (n->type != type) fail(GA_ERR_INVALID_ARGUMENT, "node has the wrong type for this call");
-  return n;
-}
 float clampf(float v, float mn, float mx) {  // Math.Clamp(float, float, float)
   if (v < mn) return mn;
   if (v > mx) return mx;
@@ -75,15 +70,6 @@ void addEvent(ParamS& p, const ParamEvent& e) {  // AudioParam.AddEvent, AudioPa
     if (e.time < p.events[mid].time) hi = mid; else lo = mid + 1;
   }
   p.events.insert(p.events.begin() + lo, e);
-}
-ParamS makeParam(float def, float mn, float mx, bool arate) {
-  ParamS p;
-  p.def = def;
-  p.minv = mn;
-  p.maxv = mx;
-  p.arate = arate;
-  p.value = def;
-  return p;
 }
 }  // namespace
 
@@ -102,19 +88,22 @@ int64_t Context::chunkLimit(int64_t) {
         perBlock += (double)convRowsMax * kBins * 4.0 * 4.0;
         int tailMax = kCoarseMaxP;   // the longest carried tail stretches every Y row of its stage (Context::chunkConvScratch): counted for all slots
         for (auto& np : nodes)
-          if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath == 4) tailMax = std::max(tailMax, np->ir->coarseP);
-        for (auto& np : nodes)   // private-IR convolvers (formulations B / C): y rows + x rows in both plane pairs
-          if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath == 4)
+          if (np->type == GA_NODE_CONVOLVER)
+            if (const ConvolverS& cv = rec<ConvolverS>(*np); cv.ir && cv.convPath == 4) tailMax = std::max(tailMax, cv.ir->coarseP);
+        for (auto& np : nodes) {   // private-IR convolvers (formulations B / C): y rows + x rows in both plane pairs
+          if (np->type != GA_NODE_CONVOLVER) continue;
+          const ConvolverS& cv = rec<ConvolverS>(*np);
+          if (cv.ir && cv.convPath == 4) {
             // formulation D: X frames of the input channels + (at worst, nothing fused) Y frames of the slots: 64 KB per 8192 samples
-          {
-            perBlock += (double)((np->isTrueStereo ? 2 : np->ir->nch) + (np->isTrueStereo ? 4 : np->ir->nch)) * 1024.0;
+            perBlock += (double)((cv.isTrueStereo ? 2 : cv.ir->nch) + (cv.isTrueStereo ? 4 : cv.ir->nch)) * 1024.0;
             // ... and per input row the P' history windows in front of the chunk + the window behind it, per slot the P' blocks of a
             // carried tail: 64 KB each, whatever the chunk's length (1 GB at 1024 voices x 8 partitions)
-            const double inCh = np->isTrueStereo ? 2 : np->ir->nch, slots = np->isTrueStereo ? 4 : np->ir->nch;
-            fixedBytes += (inCh * (np->ir->coarseP + 1) + slots * (double)tailMax) * 65536.0;
+            const double inCh = cv.isTrueStereo ? 2 : cv.ir->nch, slots = cv.isTrueStereo ? 4 : cv.ir->nch;
+            fixedBytes += (inCh * (cv.ir->coarseP + 1) + slots * (double)tailMax) * 65536.0;
+          } else if (cv.ir && cv.convPath != 1) {
+            perBlock += (double)(cv.ir->nch + 2 * (cv.isTrueStereo ? 2 : cv.ir->nch)) * kBins * 8.0;
           }
-          else if (np->type == GA_NODE_CONVOLVER && np->ir && np->convPath != 1)
-            perBlock += (double)(np->ir->nch + 2 * (np->isTrueStereo ? 2 : np->ir->nch)) * kBins * 8.0;
+        }
         perBlock += ((double)nodes.size() * 2.0 + 64.0) * kBlock * 4.0;
         double budget = ((double)freeB + (double)slabBlocks.size() * (double)((size_t)1 << 30) * 0.0) * memBudgetFraction;
         // memory already held by slabs / planes is reused, so add it back to the budget
@@ -338,12 +327,7 @@ int ga_context_create(int sample_rate, int device_ordinal, ga_context** out) {
   try {
     h = new ga_context(sample_rate);
     h->c.init_device(device_ordinal);
-    auto d = std::make_unique<NodeS>();  // AudioDestinationNode: 1 input with channelCount 2, no outputs (:17-21)
-    d->id = 0;
-    d->type = GA_NODE_DESTINATION;
-    d->inputs.resize(1);
-    d->inputs[0].channelCount = 2;
-    h->c.nodes.push_back(std::move(d));
+    h->c.nodes.push_back(makeNode(GA_NODE_DESTINATION, 0, 0.0, sample_rate));
     *out = h;
     return GA_OK;
   } catch (const Err& e) {
@@ -489,92 +473,12 @@ int ga_node_create(ga_context* ctx, int node_type, int* out_id) {  // constructo
 int ga_node_create_ex(ga_context* ctx, int node_type, double arg, int* out_id) {
   return guard(ctx, [&](Context& c) {
     if (!out_id) fail(GA_ERR_INVALID_ARGUMENT, "null pointer");
-    auto n = std::make_unique<NodeS>();
-    n->id = (int)c.nodes.size();
-    n->type = node_type;
-    const float FMAX = std::numeric_limits<float>::max();
-    switch (node_type) {
-      case GA_NODE_BUFFER_SOURCE:
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(1.f, 0.001f, 1000.f, false));  // AudioBufferSourceNode.cs:76
-        break;
-      case GA_NODE_GAIN:
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(1.f, -FMAX, FMAX, true));  // GainNode.cs:21-26
-        break;
-      case GA_NODE_BIQUAD:
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(1000.f, 1.f, c.sampleRate / 2.f, true));  // BiQuadFilterNode.cs:63-82
-        n->params.push_back(makeParam(1.f, 0.001f, 1000.f, true));
-        n->params.push_back(makeParam(0.f, -60.f, 60.f, false));
-        c.updateBiquadCoefficients(*n, 1000.f, 1.0f, 0.f);  // constructor call (:84)
-        n->coefDirty = true;
-        break;
-      case GA_NODE_CONVOLVER:
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        break;
-      case GA_NODE_CHANNEL_SPLITTER:   // ChannelSplitterNode.cs:14-22
-      case GA_NODE_CHANNEL_MERGER: {   // ChannelMergerNode.cs:14-21
-        int cnt = (int)arg;
-        if (cnt < 1 || cnt > 32) fail(GA_ERR_OUT_OF_RANGE, node_type == GA_NODE_CHANNEL_SPLITTER ? "numberOfOutputs" : "numberOfInputs");
-        n->inputs.resize(node_type == GA_NODE_CHANNEL_SPLITTER ? 1 : cnt);
-        n->outputs.resize(node_type == GA_NODE_CHANNEL_SPLITTER ? cnt : 1);
-        break;
-      }
-      case GA_NODE_CONSTANT_SOURCE:    // ConstantSourceNode.cs:29-38
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(1.f, -FMAX, FMAX, true));
-        break;
-      case GA_NODE_STEREO_PANNER:      // StereoPannerNode.cs:21-34
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        n->inputs[0].channelCount = 2;
-        n->inputs[0].mode = GA_COUNT_MODE_CLAMPED_MAX;
-        n->inputs[0].interp = GA_INTERP_SPEAKERS;
-        n->params.push_back(makeParam(0.f, -1.f, 1.f, true));
-        break;
-      case GA_NODE_OSCILLATOR:         // OscillatorNode.cs:43-52
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(440.f, 0.f, c.sampleRate / 2.f, true));
-        break;
-      case GA_NODE_DELAY: {            // DelayNode.cs:22-41
-        if (!(arg > 0) || arg > 10) fail(GA_ERR_OUT_OF_RANGE, "maxDelayTime");
-        n->maxDelaySamples = (int)(arg * c.sampleRate);
-        if (n->maxDelaySamples < 1) fail(GA_ERR_OUT_OF_RANGE, "maxDelayTime");
-        n->delayRings = 2;
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(0.f, 0.f, (float)arg, true));
-        break;
-      }
-      case GA_NODE_STREAM_SOURCE:      // AudioStreamSourceNodeBase.cs:59-67
-        n->outputs.resize(1);
-        n->params.push_back(makeParam(1.f, 0.001f, 1000.f, false));
-        break;
-      case GA_NODE_SPATIAL_PANNER: {   // SpatialPannerNode.cs:94-114 (float.MinValue is -float.MaxValue)
-        n->inputs.resize(1);
-        n->outputs.resize(1);
-        n->inputs[0].channelCount = 2;
-        n->inputs[0].mode = GA_COUNT_MODE_CLAMPED_MAX;
-        n->inputs[0].interp = GA_INTERP_SPEAKERS;
-        for (int i = 0; i < 3; i++) n->params.push_back(makeParam(0.f, -FMAX, FMAX, false));   // positionX/Y/Z
-        n->params.push_back(makeParam(1.f, -1.f, 1.f, false));                                 // orientationX
-        n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationY
-        n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationZ
-        n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // refDistance
-        n->params.push_back(makeParam(10000.f, 0.f, FMAX, false));                             // maxDistance
-        n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // rolloffFactor
-        n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneInnerAngle
-        n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneOuterAngle
-        n->params.push_back(makeParam(0.f, 0.f, 1.f, false));                                  // coneOuterGain
-        n->params.push_back(makeParam(1.f, 0.f, 1.f, false));                                  // spatialBlend
-        for (int i = 0; i < 4; i++) n->params.push_back(makeParam(0.f, 0.f, 1.f, false));      // occlusion, transmissionLow/Mid/High
-        break;
-      }
-      default: fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");
+    if (node_type == GA_NODE_DESTINATION) fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");   // (the context's own node 0: not for callers)
+    auto n = makeNode(node_type, (int)c.nodes.size(), arg, c.sampleRate);
+    if (node_type == GA_NODE_BIQUAD) {
+      BiquadS& bq = rec<BiquadS>(*n);
+      c.updateBiquadCoefficients(bq, 1000.f, 1.0f, 0.f);  // constructor call (BiQuadFilterNode.cs:84)
+      bq.coefDirty = true;
     }
     *out_id = n->id;
     c.nodes.push_back(std::move(n));
@@ -642,7 +546,7 @@ int ga_node_has_ended(ga_context* ctx, int node) {
   int r = 0;
   int rc = guardRO(ctx, [&](Context& c) {
     NodeS* n = c.node(node);
-    r = n->endedRaised ? 1 : 0;
+    r = isScheduledSource(n->type) && schedOf(*n).endedRaised ? 1 : 0;
   });
   return rc < 0 ? rc : r;
 }
@@ -700,7 +604,8 @@ int ga_destination_output_channels(ga_context* ctx) {
 
 int ga_param_set_value(ga_context* ctx, int node, int param, float value) {
   return guard(ctx, [&](Context& c) {  // Value setter: clamp + cancel all events (AudioParam.cs:37-48)
-    if (NodeS* sn = c.node(node); sn->type == GA_NODE_SPATIAL_PANNER && param >= GA_SPATIAL_PARAM_COUNT) {
+    if (c.node(node)->type == GA_NODE_SPATIAL_PANNER && param >= GA_SPATIAL_PARAM_COUNT) {
+      SpatialPannerS* sn = &rec<SpatialPannerS>(*c.node(node));
       const int iv = (int)value;
       if (param == GA_SPATIAL_DISTANCE_MODEL) {   // SpatialPannerNode.DistanceModel (:36-40): a plain property
         if ((float)iv != value || iv < GA_DISTANCE_LINEAR || iv > GA_DISTANCE_EXPONENTIAL) fail(GA_ERR_INVALID_ARGUMENT, "distanceModel");
@@ -724,7 +629,8 @@ int ga_param_set_value(ga_context* ctx, int node, int param, float value) {
 int ga_param_get_value(ga_context* ctx, int node, int param, float* out) {
   return guardRO(ctx, [&](Context& c) {
     if (!out) fail(GA_ERR_INVALID_ARGUMENT, "null pointer");
-    if (NodeS* sn = c.node(node); sn->type == GA_NODE_SPATIAL_PANNER && (param == GA_SPATIAL_DISTANCE_MODEL || param == GA_SPATIAL_HRIR_AZIMUTHS)) {
+    if (c.node(node)->type == GA_NODE_SPATIAL_PANNER && (param == GA_SPATIAL_DISTANCE_MODEL || param == GA_SPATIAL_HRIR_AZIMUTHS)) {
+      const SpatialPannerS* sn = &rec<SpatialPannerS>(*c.node(node));
       *out = (float)(param == GA_SPATIAL_DISTANCE_MODEL ? sn->distanceModel : sn->hrirAzimuths);
       return;
     }
@@ -787,14 +693,14 @@ int ga_param_cancel_scheduled_values(ga_context* ctx, int node, int param, doubl
 
 int ga_source_set_buffer(ga_context* ctx, int node, int buffer_id) {
   return guard(ctx, [&](Context& c) {
-    NodeS* n = typed(c, node, GA_NODE_BUFFER_SOURCE);
+    BufferSourceS* n = &rec<BufferSourceS>(*c.node(node));
     if (buffer_id >= 0 && c.buffer(buffer_id)->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
     n->bufId = buffer_id < 0 ? -1 : buffer_id;
   });
 }
 int ga_source_set_loop(ga_context* ctx, int node, int loop, double loop_start, double loop_end) {
   return guard(ctx, [&](Context& c) {
-    NodeS* n = typed(c, node, GA_NODE_BUFFER_SOURCE);
+    BufferSourceS* n = &rec<BufferSourceS>(*c.node(node));
     n->loop = loop != 0;
     n->loopStart = std::max(0.0, loop_start);
     n->loopEnd = std::max(0.0, loop_end);
@@ -806,13 +712,13 @@ int ga_source_start(ga_context* ctx, int node, double when, double offset, doubl
     const int ty = c.node(node)->type;
     if (ty == GA_NODE_CONSTANT_SOURCE || ty == GA_NODE_OSCILLATOR) {
       c.executeOrPost([cp, node, when, duration, ty]() {  // ConstantSourceNode.cs:44-63, OscillatorNode.cs:54-73
-        NodeS& s = *cp->nodes[node];
+        SchedState& s = schedOf(*cp->nodes[node]);
         if (s.hasStarted) {
           if (ty == GA_NODE_OSCILLATOR) fail(GA_ERR_INVALID_OPERATION, "OscillatorNode can only be started once.");
           return;   // a second ConstantSourceNode.Start is ignored
         }
         s.hasStarted = true;
-        s.oscPhaseReset = true;
+        if (ty == GA_NODE_OSCILLATOR) rec<OscillatorS>(*cp->nodes[node]).oscPhaseReset = true;
         s.startTime = std::max(0.0, when);
         if (!std::isnan(duration) && duration >= 0) {
           s.stopTime = s.startTime + duration;
@@ -821,9 +727,9 @@ int ga_source_start(ga_context* ctx, int node, double when, double offset, doubl
       });
       return;
     }
-    typed(c, node, GA_NODE_BUFFER_SOURCE);
+    rec<BufferSourceS>(*c.node(node));
     c.executeOrPost([cp, node, when, offset, duration]() {  // AudioBufferSourceNode.cs:81-111
-      NodeS& s = *cp->nodes[node];
+      BufferSourceS& s = rec<BufferSourceS>(*cp->nodes[node]);
       if (s.hasStarted) fail(GA_ERR_INVALID_OPERATION, "AudioBufferSourceNode can only be started once.");
       if (s.bufId < 0) fail(GA_ERR_INVALID_OPERATION, "Cannot start without a buffer set");
       s.hasStarted = true;
@@ -841,11 +747,10 @@ int ga_source_start(ga_context* ctx, int node, double when, double offset, doubl
 }
 int ga_source_stop(ga_context* ctx, int node, double when) {
   return guard(ctx, [&](Context& c) {
-    const int ty = c.node(node)->type;
-    if (ty != GA_NODE_CONSTANT_SOURCE && ty != GA_NODE_OSCILLATOR) typed(c, node, GA_NODE_BUFFER_SOURCE);
+    schedOf(*c.node(node));   // (a buffer, constant or oscillator source)
     Context* cp = &c;
     c.executeOrPost([cp, node, when]() {  // AudioBufferSourceNode.cs:118-126
-      NodeS& s = *cp->nodes[node];
+      SchedState& s = schedOf(*cp->nodes[node]);
       if (s.hasStopped) return;
       double at = std::max(0.0, when);
       s.stopTime = std::isnan(s.stopTime) ? at : std::min(s.stopTime, at);
@@ -855,19 +760,19 @@ int ga_source_stop(ga_context* ctx, int node, double when) {
 }
 int ga_oscillator_set_type(ga_context* ctx, int node, int oscillator_type) {
   return guard(ctx, [&](Context& c) {  // OscillatorNode.cs:33-42
-    typed(c, node, GA_NODE_OSCILLATOR);
+    rec<OscillatorS>(*c.node(node));
     if (oscillator_type < 0 || oscillator_type > 3) fail(GA_ERR_INVALID_ARGUMENT, "oscillator type");
     Context* cp = &c;
-    c.executeOrPost([cp, node, oscillator_type]() { cp->nodes[node]->oscType = oscillator_type; });
+    c.executeOrPost([cp, node, oscillator_type]() { rec<OscillatorS>(*cp->nodes[node]).oscType = oscillator_type; });
   });
 }
 int ga_biquad_set_type(ga_context* ctx, int node, int filter_type) {
   return guard(ctx, [&](Context& c) {
-    typed(c, node, GA_NODE_BIQUAD);
+    rec<BiquadS>(*c.node(node));
     if (filter_type < 0 || filter_type > GA_FILTER_HIGHSHELF) fail(GA_ERR_INVALID_ARGUMENT, "filter type");
     Context* cp = &c;
     c.executeOrPost([cp, node, filter_type]() {  // BiQuadFilterNode.cs:24-36
-      NodeS& b = *cp->nodes[node];
+      BiquadS& b = rec<BiquadS>(*cp->nodes[node]);
       if (b.filterType != filter_type) {
         b.filterType = filter_type;
         b.coefDirty = true;
@@ -876,21 +781,22 @@ int ga_biquad_set_type(ga_context* ctx, int node, int filter_type) {
   });
 }
 int ga_convolver_set_normalize(ga_context* ctx, int node, int normalize) {
-  return guard(ctx, [&](Context& c) { typed(c, node, GA_NODE_CONVOLVER)->normalize = normalize != 0; });
+  return guard(ctx, [&](Context& c) { rec<ConvolverS>(*c.node(node)).normalize = normalize != 0; });
 }
 int ga_convolver_set_enable_true_stereo(ga_context* ctx, int node, int enable) {
-  return guard(ctx, [&](Context& c) { typed(c, node, GA_NODE_CONVOLVER)->enableTrueStereo = enable != 0; });
+  return guard(ctx, [&](Context& c) { rec<ConvolverS>(*c.node(node)).enableTrueStereo = enable != 0; });
 }
 int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
   return guard(ctx, [&](Context& c) {  // ConvolverNode.Buffer setter, ConvolverNode.cs:25-79
     Context* cp = &c;
     if (c.node(node)->type == GA_NODE_SPATIAL_PANNER) {   // the node's HRIR set (graphaudio_hip.h): checked now, applied with the queued commands
-      NodeS* sn = c.node(node);
+      SpatialPannerS* sn = &rec<SpatialPannerS>(*c.node(node));
       if (buffer_id < 0) {
         sn->hrirRequested = -1;
         c.post([cp, node]() {
-          cp->nodes[node]->irBuf = -1;
-          cp->nodes[node]->spPrev.valid = false;   // (indices into the set that is gone: the next processed block does not fade)
+          SpatialPannerS& nd = rec<SpatialPannerS>(*cp->nodes[node]);
+          nd.irBuf = -1;
+          nd.spPrev.valid = false;   // (indices into the set that is gone: the next processed block does not fade)
           cp->graphVersion++;
         });
         return;
@@ -909,7 +815,7 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
       const float bound = (float)sumMax;
       sn->hrirRequested = buffer_id;
       c.post([cp, node, buffer_id, bound]() {
-        NodeS& nd = *cp->nodes[node];
+        SpatialPannerS& nd = rec<SpatialPannerS>(*cp->nodes[node]);
         nd.irBuf = buffer_id;
         nd.spGainBound = bound;
         nd.spPrev.valid = false;   // the previous block's indices belong to the previous set: the next processed block uses its own filters alone
@@ -917,7 +823,7 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
       });
       return;
     }
-    NodeS* n = typed(c, node, GA_NODE_CONVOLVER);
+    ConvolverS* n = &rec<ConvolverS>(*c.node(node));
     // `if (_buffer == value) return;` (:30) compares with the buffer of the last EXECUTED swap: a swap that is still
     // queued does not count, so A -> B -> A between two blocks ends on B
     if (n->irBuf == (buffer_id < 0 ? -1 : buffer_id)) {
@@ -926,7 +832,7 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
     }
     if (buffer_id < 0) {
       c.post([cp, node]() {
-        NodeS& nd = *cp->nodes[node];
+        ConvolverS& nd = rec<ConvolverS>(*cp->nodes[node]);
         cp->releaseConvState(nd);
         nd.irBuf = -1;
         nd.ir.reset();
@@ -943,7 +849,7 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
     // spectra are built eagerly with the CURRENT Normalize flag (:51-56); the swap is posted (:58-77)
     std::shared_ptr<IrSpectra> sp = c.irSpectra(buffer_id, n->normalize);
     c.post([cp, node, buffer_id, sp]() {
-      NodeS& nd = *cp->nodes[node];
+      ConvolverS& nd = rec<ConvolverS>(*cp->nodes[node]);
       // new PartitionedConvolver instances: fresh (zero) delay line and overlap; the formulation (shared-IR rows or
       // private state) is chosen at the next render, when it is known how many nodes share this impulse response
       cp->releaseConvState(nd);
@@ -980,7 +886,7 @@ int ga_render_device(ga_context* ctx, float* const* out_planar_dev, int out_chan
 // ---- AudioStreamNodeBase (GraphAudio.IO/AudioStreamSourceNodeBase.cs) ----
 int ga_stream_queue_buffer(ga_context* ctx, int node, int buffer_id) {
   return guard(ctx, [&](Context& c) {
-    NodeS* n = typed(c, node, GA_NODE_STREAM_SOURCE);
+    StreamSourceS* n = &rec<StreamSourceS>(*c.node(node));
     PlayBuf* b = c.buffer(buffer_id);
     if (b->channels < 1 || b->length < 1) fail(GA_ERR_INVALID_ARGUMENT, "Buffer must be initialized");
     if (b->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
@@ -990,7 +896,7 @@ int ga_stream_queue_buffer(ga_context* ctx, int node, int buffer_id) {
 }
 int ga_stream_set_state(ga_context* ctx, int node, int state) {
   return guard(ctx, [&](Context& c) {
-    NodeS* n = typed(c, node, GA_NODE_STREAM_SOURCE);
+    StreamSourceS* n = &rec<StreamSourceS>(*c.node(node));
     if (state < GA_STREAM_PLAYING || state > GA_STREAM_STOPPED) fail(GA_ERR_OUT_OF_RANGE, "stream state");
     const int old = n->stState;   // State setter (:37-49): immediate (Interlocked in the reference), not a posted command
     n->stState = state;
@@ -1000,7 +906,7 @@ int ga_stream_set_state(ga_context* ctx, int node, int state) {
 int ga_stream_dequeue_processed(ga_context* ctx, int node, int* buffer_id_out) {
   int got = 0;
   int rc = guard(ctx, [&](Context& c) {
-    NodeS* n = typed(c, node, GA_NODE_STREAM_SOURCE);
+    StreamSourceS* n = &rec<StreamSourceS>(*c.node(node));
     if (n->stProcessed.empty()) return;
     if (buffer_id_out) *buffer_id_out = n->stProcessed.front();
     n->stProcessed.pop_front();
@@ -1010,12 +916,12 @@ int ga_stream_dequeue_processed(ga_context* ctx, int node, int* buffer_id_out) {
 }
 int ga_stream_queued_count(ga_context* ctx, int node) {
   int v = 0;
-  int rc = guardRO(ctx, [&](Context& c) { v = (int)typed(c, node, GA_NODE_STREAM_SOURCE)->stQueued.size(); });
+  int rc = guardRO(ctx, [&](Context& c) { v = (int)rec<StreamSourceS>(*c.node(node)).stQueued.size(); });
   return rc < 0 ? rc : v;
 }
 int ga_stream_processed_count(ga_context* ctx, int node) {
   int v = 0;
-  int rc = guardRO(ctx, [&](Context& c) { v = (int)typed(c, node, GA_NODE_STREAM_SOURCE)->stProcessed.size(); });
+  int rc = guardRO(ctx, [&](Context& c) { v = (int)rec<StreamSourceS>(*c.node(node)).stProcessed.size(); });
   return rc < 0 ? rc : v;
 }
 

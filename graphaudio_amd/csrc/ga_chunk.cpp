@@ -85,7 +85,7 @@ void Context::runChunk(int64_t n, float* const* bus) {
 void Context::chunkTopology(ChunkRun& r) {
   std::vector<int>& topo = r.topo;
   for (int id : probeDelays)   // (the previous chunk's choice, if a failure kept it from being cleared: runTwoStageChunk)
-    if (id < (int)nodes.size() && nodes[id]) nodes[id]->delayProbe = false;
+    if (id < (int)nodes.size() && nodes[id]) rec<DelayS>(*nodes[id]).delayProbe = false;
   probeDelays.clear();
   // ---- reachability, level, convolver depth on the graph as it stands after the queued commands ----
   // (cached while no connection, disposal or impulse response changed since the last chunk)
@@ -101,8 +101,11 @@ void Context::chunkTopology(ChunkRun& r) {
     np->isProcessing = false;
     np->level = 0;
     np->depth = 0;
-    np->delaySplit = false;
-    np->delayOnLoop = false;
+    if (np->type == GA_NODE_DELAY) {
+      DelayS& dl = rec<DelayS>(*np);
+      dl.delaySplit = false;
+      dl.delayOnLoop = false;
+    }
   }
   cycleBlocks = 1;
   loopGainBound = 0.0;
@@ -122,7 +125,7 @@ void Context::chunkTopology(ChunkRun& r) {
     auto splittable = [&](const NodeS& d) {
       if (d.type != GA_NODE_DELAY || !d.params[0].events.empty() || !d.params[0].modulation.empty()) return 0;
       int dl = (int)(d.params[0].value * (float)sampleRate);   // DelayNode.cs:66 (float * int -> float, truncated)
-      dl = std::min(std::max(dl, 0), d.maxDelaySamples);
+      dl = std::min(std::max(dl, 0), rec<DelayS>(d).maxDelaySamples);
       return dl / kBlock;   // whole blocks of delay
     };
     std::function<bool(int)> dfs = [&](int id) {   // false: `id` is being processed (the edge that led here is a feedback edge)
@@ -137,7 +140,7 @@ void Context::chunkTopology(ChunkRun& r) {
         for (size_t q = stack.size(); q-- > 0;) {
           const int m = stack[q];
           NodeS& mn = *nodes[m];
-          mn.delayOnLoop = true;   // (read for DelayNodes only: option "delay_flag_exact", below)
+          if (mn.type == GA_NODE_DELAY) rec<DelayS>(mn).delayOnLoop = true;   // (option "delay_flag_exact", below)
           if (splittable(mn) >= 2) {
             candidate[m] = 1;
             any = true;
@@ -146,15 +149,17 @@ void Context::chunkTopology(ChunkRun& r) {
           for (auto& p : mn.params) moving = moving || !p.events.empty() || !p.modulation.empty();
           switch (mn.type) {
             case GA_NODE_GAIN: bound *= moving ? 1e9 : std::fabs((double)mn.params[0].value); break;
-            case GA_NODE_BIQUAD:
+            case GA_NODE_BIQUAD: {
+              const int ft = rec<BiquadS>(mn).filterType;
               if (moving) bound *= 1e9;
-              else if (mn.filterType == GA_FILTER_PEAKING || mn.filterType == GA_FILTER_LOWSHELF || mn.filterType == GA_FILTER_HIGHSHELF)
+              else if (ft == GA_FILTER_PEAKING || ft == GA_FILTER_LOWSHELF || ft == GA_FILTER_HIGHSHELF)
                 bound *= std::max(1.0, std::pow(10.0, (double)mn.params[2].value / 20.0));
               else bound *= std::max(1.0, (double)mn.params[1].value);   // (the resonance peak of a low / high / band pass is ~Q)
               break;
-            case GA_NODE_CONVOLVER: bound *= mn.normalize ? 2.0 : 1e9; break;   // (normalised responses: broadband gain well below 1, peaks unknown)
+            }
+            case GA_NODE_CONVOLVER: bound *= rec<ConvolverS>(mn).normalize ? 2.0 : 1e9; break;   // (normalised responses: broadband gain well below 1, peaks unknown)
             case GA_NODE_STEREO_PANNER: bound *= 2.0; break;                    // (oL = inL + inR * gainL)
-            case GA_NODE_SPATIAL_PANNER: bound *= (double)mn.spGainBound; break;   // (sum |F| + |D| <= max(1, sum |h|): g <= 1, the weights sum to 1)
+            case GA_NODE_SPATIAL_PANNER: bound *= (double)rec<SpatialPannerS>(mn).spGainBound; break;   // (sum |F| + |D| <= max(1, sum |h|): g <= 1, the weights sum to 1)
             default: break;
           }
           if (m == id) break;
@@ -175,7 +180,7 @@ void Context::chunkTopology(ChunkRun& r) {
             if (!dfs(m.first)) continue;
             NodeS& up = *nodes[m.first];
             lvl = std::max(lvl, up.level + 1);
-            dep = std::max(dep, up.depth + ((up.type == GA_NODE_CONVOLVER && up.ir) ? 1 : 0));
+            dep = std::max(dep, up.depth + (hasImpulseResponse(up) ? 1 : 0));
           }
         }
       for (auto& in : nd.inputs)
@@ -183,7 +188,7 @@ void Context::chunkTopology(ChunkRun& r) {
           if (!dfs(cn.node)) continue;
           NodeS& up = *nodes[cn.node];
           lvl = std::max(lvl, up.level + 1);
-          dep = std::max(dep, up.depth + ((up.type == GA_NODE_CONVOLVER && up.ir) ? 1 : 0));
+          dep = std::max(dep, up.depth + (hasImpulseResponse(up) ? 1 : 0));
         }
       nd.level = lvl;
       nd.depth = dep;
@@ -226,7 +231,7 @@ void Context::chunkTopology(ChunkRun& r) {
           }
           dfs2(up);
           lvl = std::max(lvl, lvl2[up] + 1);
-          dep = std::max(dep, dep2[up] + ((nodes[up]->type == GA_NODE_CONVOLVER && nodes[up]->ir) ? 1 : 0));
+          dep = std::max(dep, dep2[up] + (hasImpulseResponse(*nodes[up]) ? 1 : 0));
         };
         for (auto& p : nd.params)
           for (auto& m : p.modulation) edge(m.first);
@@ -244,7 +249,7 @@ void Context::chunkTopology(ChunkRun& r) {
         for (int id : topo) {
           nodes[id]->level = lvl2[id];
           nodes[id]->depth = dep2[id];
-          nodes[id]->delaySplit = candidate[id] != 0;
+          if (nodes[id]->type == GA_NODE_DELAY) rec<DelayS>(*nodes[id]).delaySplit = candidate[id] != 0;
         }
         cycleBlocks = K;
       }
@@ -323,8 +328,9 @@ void Context::chunkTopology(ChunkRun& r) {
       if (rateCone[id] && nodes[id]->type == GA_NODE_CONVOLVER)
         fail(GA_ERR_UNSUPPORTED, "a ConvolverNode in front of a modulated playbackRate is not on the device path");
     for (const auto& pm : topoRateMods) {
-      NodeS& nd = *nodes[pm.first];
-      if (nd.type != GA_NODE_BUFFER_SOURCE || !nd.loop || nd.bufId < 0 || !buffers[nd.bufId]) continue;
+      if (nodes[pm.first]->type != GA_NODE_BUFFER_SOURCE) continue;
+      BufferSourceS& nd = rec<BufferSourceS>(*nodes[pm.first]);
+      if (!nd.loop || nd.bufId < 0 || !buffers[nd.bufId]) continue;
       const SrcGeom g = sourceGeom(*this, nd, *buffers[nd.bufId]);
       if (g.loopEndFrame <= g.loopStartFrame)   // (the replay's guard would fire inside the device walk: refused while nothing has moved)
         fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
@@ -337,7 +343,7 @@ void Context::chunkTopology(ChunkRun& r) {
   // from the flags of the blocks that went into the ring (Sim::process), never late, sometimes early.  A delay whose cone can be
   // rendered ahead of the rest is rendered in stage 1 instead, and the block in which its samples raise the flag is read back
   // (delay_onset_kernel).  Accepted, per chunk, while nothing has moved: a reachable DelayNode whose flag is down, that is on no
-  // feedback loop (not among the nodes of a back edge's loop, NodeS::delayOnLoop, and not reached by its own cone: deciding it would
+  // feedback loop (not among the nodes of a back edge's loop, DelayS::delayOnLoop, and not reached by its own cone: deciding it would
   // split the reference's walk inside a block), with no other DelayNode whose flag is down in front
   // of it (the control state of the nodes in between would be undecided: more than two stages), no source with a modulated
   // playbackRate in front of it and not in front of one (stage 1 plans both from the state before the chunk), and no ConvolverNode
@@ -346,8 +352,9 @@ void Context::chunkTopology(ChunkRun& r) {
   if (delayFlagExact && topoHasTimeNodes) {
     std::vector<int> seen, stack, cone;
     for (int id : topo) {
-      NodeS& d = *nodes[id];
-      if (d.type != GA_NODE_DELAY || d.delayAudible || d.delayOnLoop || d.delaySplit) continue;
+      if (nodes[id]->type != GA_NODE_DELAY) continue;
+      DelayS& d = rec<DelayS>(*nodes[id]);
+      if (d.delayAudible || d.delayOnLoop || d.delaySplit) continue;
       if (!topoRateMods.empty() && rateCone[id]) continue;
       if (seen.empty()) seen.assign(nodes.size(), -1);
       bool ok = true;
@@ -364,7 +371,7 @@ void Context::chunkTopology(ChunkRun& r) {
           if (seen[up] == id) return;
           seen[up] = id;
           const NodeS& u = *nodes[up];
-          if ((u.type == GA_NODE_DELAY && !u.delayAudible) || u.type == GA_NODE_CONVOLVER ||
+          if ((u.type == GA_NODE_DELAY && !rec<DelayS>(u).delayAudible) || u.type == GA_NODE_CONVOLVER ||
               ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty()))
             ok = false;
           cone.push_back(up);
@@ -401,8 +408,8 @@ void Context::chunkTopology(ChunkRun& r) {
   if (topoHasSpatial) {
     const double increment = (double)kBlock / sampleRate;
     for (int id : topo) {
-      NodeS& nd = *nodes[id];
-      if (nd.type != GA_NODE_SPATIAL_PANNER) continue;
+      if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
+      SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
       // (decided here, on the graph as the chunk finds it: a modulator that ends inside the chunk is disconnected by the simulation,
       // and the blocks before that still read it)
       nd.spSignals = spatialSignalDriven(nd);
@@ -430,21 +437,26 @@ void Context::chunkTopology(ChunkRun& r) {
     }
   }
   // automated runs that ended hand their state back to the host: only nodes whose state went to the device are looked at
-  // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, NodeS::bqDynSeq / panDynSeq, not a flag to reset)
+  // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, DynStamp::dynSeq, not a flag to reset)
   for (size_t i = 0; i < deviceStateNodes.size();) {
     const int id = deviceStateNodes[i];
     NodeS* np = id < (int)nodes.size() ? nodes[id].get() : nullptr;
-    if (!np || np->disposed || (!np->panOnDevice && !np->coefOnDevice && !np->spOnDevice)) {
+    const bool onDevice = np && !np->disposed &&
+                          ((np->type == GA_NODE_STEREO_PANNER && rec<StereoPannerS>(*np).panOnDevice) ||
+                           (np->type == GA_NODE_BIQUAD && rec<BiquadS>(*np).coefOnDevice) ||
+                           (np->type == GA_NODE_SPATIAL_PANNER && rec<SpatialPannerS>(*np).spOnDevice));
+    if (!onDevice) {
       deviceStateNodes[i] = deviceStateNodes.back();
       deviceStateNodes.pop_back();
       continue;
     }
     i++;
-    NodeS& nd = *np;
-    if (!nd.reachable) continue;
+    if (!np->reachable) continue;
     // (while a signal is connected to the parameter the node stays on its per-sample kernel, which serves a silent modulation input
     // as a constant too -- Sim::process -- so the state stays where it is: no stall of the pipeline per modulated node and chunk)
-    if (nd.type == GA_NODE_STEREO_PANNER && nd.panOnDevice && nd.params[0].events.empty() && nd.params[0].modulation.empty()) {
+    if (np->type == GA_NODE_STEREO_PANNER) {
+      StereoPannerS& nd = rec<StereoPannerS>(*np);
+      if (!nd.params[0].events.empty() || !nd.params[0].modulation.empty()) continue;
       PanState tmp;   // back to a constant pan: the gains the automated run left on the device are the node's state
       GA_HIP(hipStreamSynchronize(stream));   // the state the previous chunk left
       GA_HIP(hipMemcpy(&tmp, nd.panDev, sizeof(PanState), hipMemcpyDeviceToHost));
@@ -453,8 +465,9 @@ void Context::chunkTopology(ChunkRun& r) {
       nd.panGR = tmp.gain_r;
       nd.panOnDevice = false;
       apiEpoch++;   // (host-tracked state changed: the next first block is traversed)
-    }
-    if (nd.type == GA_NODE_SPATIAL_PANNER && nd.spOnDevice && !spatialSignalDriven(nd)) {
+    } else if (np->type == GA_NODE_SPATIAL_PANNER) {
+      SpatialPannerS& nd = rec<SpatialPannerS>(*np);
+      if (spatialSignalDriven(nd)) continue;
       // the last signal is gone: the descriptor of the previous processed block comes back once, the host path continues (and its
       // first block fades from the descriptor the device made).  `valid` never left the host.
       if (nd.spPrev.valid && nd.spCarry[nd.spCarryCur]) {
@@ -477,8 +490,9 @@ void Context::chunkTopology(ChunkRun& r) {
       nd.spEqOnDevice = false;
       nd.spOnDevice = false;
       apiEpoch++;
-    }
-    if (nd.type == GA_NODE_BIQUAD && nd.coefOnDevice && nd.bqDyn) {
+    } else {
+      BiquadS& nd = rec<BiquadS>(*np);
+      if (!nd.bqDyn) continue;
       bool automated = false;
       for (auto& p : nd.params) automated = automated || !p.events.empty() || !p.modulation.empty();
       if (!automated) {  // back to constant parameters: fetch the coefficients the automated run left on the device
@@ -519,8 +533,8 @@ void Context::chunkSimulate(ChunkRun& r) {
     r.srcIndex[id] = (int)srcIds.size();
     srcIds.push_back(id);
     const RateModIn* rm = (id < (int)r.rmOf.size() && r.rmOf[id] >= 0) ? &r.rmIn[r.rmOf[id]] : nullptr;
-    srcPlans.push_back(scheduled ? planScheduled(*this, nd, n, bt) : planSource(*this, nd, n, bt, rm));
-    for (const SrcSpan& sp : nd.spans)
+    srcPlans.push_back(scheduled ? planScheduled(*this, nd, n, bt) : planSource(*this, rec<BufferSourceS>(nd), n, bt, rm));
+    for (const SrcSpan& sp : schedOf(nd).spans)
       if (sp.b0 > 0 && sp.b0 < n) breaks.push_back(sp.b0);
     if (srcPlans.back().partialBlock >= 0) {
       breaks.push_back(srcPlans.back().partialBlock);
@@ -528,8 +542,8 @@ void Context::chunkSimulate(ChunkRun& r) {
     }
   }
   for (int id : topo) {   // AudioStreamNodeBase: replay on indices; a change of channel count / silence is a segment break
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_STREAM_SOURCE) continue;
+    if (nodes[id]->type != GA_NODE_STREAM_SOURCE) continue;
+    StreamSourceS& nd = rec<StreamSourceS>(*nodes[id]);
     // (a modulated rate: the values the first stage read back)
     nd.stRateMod = (id < (int)r.rmOf.size() && r.rmOf[id] >= 0) ? r.rmIn[r.rmOf[id]].rates : nullptr;
     if (!nd.stRateMod && !nd.params.empty() && !nd.params[0].modulation.empty()) fail(GA_ERR_DEVICE, "internal: modulated stream rate without its values");
@@ -543,7 +557,7 @@ void Context::chunkSimulate(ChunkRun& r) {
       if (b > 0 && b < n) breaks.push_back(b);
   if (r.pre)   // ... and where the samples of a DelayNode raised its output flag (option "delay_flag_exact")
     for (int id : r.pre->probeDelays)
-      for (const NodeS::DelaySpan& sp : nodes[id]->delaySpans)
+      for (const DelayS::DelaySpan& sp : rec<DelayS>(*nodes[id]).delaySpans)
         if (sp.onset > 0 && sp.onset < n) breaks.push_back(sp.onset);
   std::sort(breaks.begin(), breaks.end());
   breaks.erase(std::unique(breaks.begin(), breaks.end()), breaks.end());
@@ -610,7 +624,7 @@ void Context::chunkSimulate(ChunkRun& r) {
           if (ns.type == GA_NODE_DELAY) {
             // a DelayNode's control state is its output flag, which is sticky once raised (DelayNode.cs:96-97): a node that is audible
             // with a constant delay time behaves like any other node; until then its ring model has to be walked block by block
-            const NodeS& dn = *nodes[ns.id];
+            const DelayS& dn = rec<DelayS>(*nodes[ns.id]);
             if (!ns.delayAudible || !dn.delayAudible || !dn.params[0].events.empty() || !dn.params[0].modulation.empty()) {
               same = false;
               break;
@@ -618,9 +632,9 @@ void Context::chunkSimulate(ChunkRun& r) {
             continue;
           }
           if (ns.type != GA_NODE_BUFFER_SOURCE && ns.type != GA_NODE_CONSTANT_SOURCE && ns.type != GA_NODE_OSCILLATOR) continue;
-          const NodeS& sn = *nodes[ns.id];
-          const SrcSpan& sp = spanAt(sn, 0);
-          if (sp.phase != ns.srcPhase || (ns.type == GA_NODE_BUFFER_SOURCE && ns.srcBuf != sn.bufId)) {
+          NodeS& sn = *nodes[ns.id];
+          const SrcSpan& sp = spanAt(schedOf(sn), 0);
+          if (sp.phase != ns.srcPhase || (ns.type == GA_NODE_BUFFER_SOURCE && ns.srcBuf != rec<BufferSourceS>(sn).bufId)) {
             same = false;
             break;
           }
@@ -633,16 +647,16 @@ void Context::chunkSimulate(ChunkRun& r) {
             switch (ns.type) {
               case GA_NODE_BUFFER_SOURCE:
                 if (ns.srcPhase == SRC_PLAY) {
-                  const SrcSpan& sp = spanAt(*nodes[ns.id], 0);
+                  const SrcSpan& sp = spanAt(rec<BufferSourceS>(*nodes[ns.id]), 0);
                   ns.srcPos = sp.pos + (0 - sp.b0) * kBlock;
                   ns.srcBlk = sp.blkIdx + (0 - sp.b0);
                 }
                 break;
               case GA_NODE_BIQUAD:   // (per-chunk flags the traversal would have set again: Sim::process)
-                if (ns.bqDynamic && !ns.ins[0].silent) nodes[ns.id]->bqDynSeq = chunkSeq;
+                if (ns.bqDynamic && !ns.ins[0].silent) rec<BiquadS>(*nodes[ns.id]).dynSeq = chunkSeq;
                 break;
               case GA_NODE_STEREO_PANNER:
-                if (ns.panDyn) nodes[ns.id]->panDynSeq = chunkSeq;
+                if (ns.panDyn) rec<StereoPannerS>(*nodes[ns.id]).dynSeq = chunkSeq;
                 break;
               case GA_NODE_DESTINATION:
                 destOutCh = ns.outCh;
@@ -711,7 +725,7 @@ void Context::chunkSimulate(ChunkRun& r) {
     if (n < (int64_t)bt.size() - 1) {
       bt.resize(n + 1);
       // the chunk was cut short: the stream tables (window at the END of the chunk, pieces) are rebuilt for the blocks that run
-      for (int id : r.streamIds) streamReplay(*nodes[id], n, bt, false);
+      for (int id : r.streamIds) streamReplay(rec<StreamSourceS>(*nodes[id]), n, bt, false);
     }
   }
   if (r.pre && !r.pre->preCh0.empty() && !r.pre->preSnap.empty())   // (the cone leaves the chunk with the counts of its last block)
@@ -727,8 +741,8 @@ void Context::chunkResources(ChunkRun& r) {
   const int64_t frames = r.n * kBlock;
   // ---- DelayNode state: history [rings][maxDelay] (persistent) and the chunk's line [rings][maxDelay + frames] ----
   for (int id : r.topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_DELAY) continue;
+    if (nodes[id]->type != GA_NODE_DELAY) continue;
+    DelayS& nd = rec<DelayS>(*nodes[id]);
     nd.delayLoaded = false;
     int rings = std::max(nd.delayRings, 2);
     for (const Segment& sg : r.segs)
@@ -890,9 +904,9 @@ void Context::chunkCommit(ChunkRun& r) {
   std::vector<int>& srcIds = r.srcIds;
   // ---- commit the control state to the end of the chunk ----
   for (size_t i = 0; i < srcIds.size(); i++) {
-    NodeS& s = *nodes[srcIds[i]];
     SrcPlanOut& po = r.srcPlans[i];
-    if (s.type != GA_NODE_BUFFER_SOURCE) {  // ConstantSourceNode / OscillatorNode: only the Ended + Dispose bookkeeping
+    if (nodes[srcIds[i]]->type != GA_NODE_BUFFER_SOURCE) {  // ConstantSourceNode / OscillatorNode: only the Ended + Dispose bookkeeping
+      SchedState& s = schedOf(*nodes[srcIds[i]]);
       if (po.gone && po.goneAt <= n) {
         if (!s.endedRaised) endedQueue.push_back(srcIds[i]);
         s.endedRaised = true;
@@ -900,6 +914,7 @@ void Context::chunkCommit(ChunkRun& r) {
       }
       continue;
     }
+    BufferSourceS& s = rec<BufferSourceS>(*nodes[srcIds[i]]);
     // recompute progress against the (possibly shortened) chunk
     if (s.spans.empty()) continue;
     int64_t firstPlay = -1;
@@ -950,7 +965,7 @@ void Context::chunkCommit(ChunkRun& r) {
       if (po.goneAt == n) pending.push_back([this, id = srcIds[i]]() { doDispose(id); });  // runs in the next block's drain
     }
   }
-  for (int id : r.streamIds) streamReplay(*nodes[id], n, bt, true);   // queue / resampler state at the end of the executed blocks
+  for (int id : r.streamIds) streamReplay(rec<StreamSourceS>(*nodes[id]), n, bt, true);   // queue / resampler state at the end of the executed blocks
   if (r.stage == 1) return;   // (the second stage of the chunk advances the clock)
   currentBlock += n;
   currentTime = bt[n];
@@ -1055,7 +1070,7 @@ void Context::chunkRetire(ChunkRun& r) {
 // rendered -- their per-block state comes from stage 1's simulation (Sim::restorePre), their output views from stage 1's executor.
 // Nothing of the next chunk overlaps this one's planning: the wait is on the whole of stage 1.
 // Option "delay_flag_exact": the DelayNodes chunkTopology accepted and their cones are stage 1's as well.  Stage 1 keeps each one's
-// predicted flag apart (NodeS::delayShadow) and plans the node as ever; where the prediction raises the flag inside the chunk,
+// predicted flag apart (DelayS::delayShadow) and plans the node as ever; where the prediction raises the flag inside the chunk,
 // delay_onset_kernel looks for the first block of the node's output rows that holds a sample != 0f, and its word travels to the host
 // with the rates.  Stage 2 sees the flag down before that block and up from it on (Sim::restorePre), breaks its segments there and
 // hands the node's rows to its consumers from there on.  Without a modulated rate and without a predicted rise there is nothing to
@@ -1107,9 +1122,9 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   }
   // the accepted delays: the block in which each span's samples raised the flag; the flag the node leaves the chunk with is its last span's
   for (int id : r1.probeDelays) {
-    NodeS& d = *nodes[id];
+    DelayS& d = rec<DelayS>(*nodes[id]);
     bool read = false;
-    for (NodeS::DelaySpan& sp : d.delaySpans) {
+    for (DelayS::DelaySpan& sp : d.delaySpans) {
       if (sp.word < 0) continue;
       const int32_t v = r1.onsetWords[sp.word];
       if (v != std::numeric_limits<int32_t>::max()) sp.onset = v;
@@ -1153,8 +1168,8 @@ void Context::runTwoStageChunk(ChunkRun& r) {
     // an accepted delay: stage 1 wrote its rows for every segment (planDelay) and handed out no view; consumers see them from the
     // onset on (stage 2 breaks its segments there: chunkSimulate)
     for (int id : r1.probeDelays) {
-      const NodeS::DelaySpan* sp = nullptr;
-      for (const NodeS::DelaySpan& q : nodes[id]->delaySpans)
+      const DelayS::DelaySpan* sp = nullptr;
+      for (const DelayS::DelaySpan& q : rec<DelayS>(*nodes[id]).delaySpans)
         if (q.b0 <= r.segs[si].b0) sp = &q;
       if (!sp) continue;
       Views v((size_t)std::max(sp->ch, 1), nullptr);
@@ -1178,7 +1193,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   chunkCommit(r);
   curveListTopoSize = ~(size_t)0;
   r1.ex.reset();
-  for (int id : probeDelays) nodes[id]->delayProbe = false;
+  for (int id : probeDelays) rec<DelayS>(*nodes[id]).delayProbe = false;
   probeDelays.clear();
   chunkRetire(r);
   lastSegStable = false;   // (the last segment's records hold stage 2's nodes only: no first-block replay in the next chunk)
@@ -1211,7 +1226,7 @@ void Context::chunkRateProbe(ChunkRun& r) {
     for (int k = 0; k < nm; k++) {
       NodeS& s = *nodes[r.rateMods[k].first];
       GsrWalkJob j{};
-      if (s.type != GA_NODE_BUFFER_SOURCE || !rateModWalkJob(*this, s, n, r.bt, j)) continue;
+      if (s.type != GA_NODE_BUFFER_SOURCE || !rateModWalkJob(*this, rec<BufferSourceS>(s), n, r.bt, j)) continue;
       walkOf[k] = (int)walks.size();
       walkMod.push_back(k);
       walks.push_back(j);
@@ -1222,9 +1237,9 @@ void Context::chunkRateProbe(ChunkRun& r) {
   // the samples cannot raise it earlier -- over the blocks from there to the span's end; its word travels with the rates
   std::vector<DelayOnsetJob> onsets;
   for (int id : r.probeDelays) {
-    NodeS& d = *nodes[id];
+    DelayS& d = rec<DelayS>(*nodes[id]);
     for (size_t k = 0; k < d.delaySpans.size(); k++) {
-      NodeS::DelaySpan& sp = d.delaySpans[k];
+      DelayS::DelaySpan& sp = d.delaySpans[k];
       const int64_t end = std::min<int64_t>(k + 1 < d.delaySpans.size() ? d.delaySpans[k + 1].b0 : n, n);
       sp.word = -1;
       if (sp.rise < 0 || sp.rise >= end || sp.ch < 1) continue;

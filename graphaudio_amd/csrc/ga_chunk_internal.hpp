@@ -67,7 +67,7 @@ struct SrcGeom {
   double effectiveRate;
 };
 
-SrcGeom sourceGeom(Context& c, NodeS& s, PlayBuf& b);
+SrcGeom sourceGeom(Context& c, BufferSourceS& s, PlayBuf& b);
 Resampler& resamplerFor(Context& c, double rate);
 
 struct SrcPlanOut {
@@ -88,12 +88,12 @@ struct RateModIn {
   int64_t nrel = 0;                  // blocks walked
 };
 
-SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm = nullptr);
+SrcPlanOut planSource(Context& c, BufferSourceS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm = nullptr);
 // the walk of a modulated buffer source (gsr_walk_kernel) from the source's state; false = the source does not play in these blocks
-bool rateModWalkJob(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j);
-SrcPlanOut planScheduled(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt);
+bool rateModWalkJob(Context& c, BufferSourceS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j);
+SrcPlanOut planScheduled(Context& c, NodeS& nd, int64_t n, const std::vector<double>& bt);
 
-static const SrcSpan& spanAt(const NodeS& s, int64_t b) {
+static const SrcSpan& spanAt(const SchedState& s, int64_t b) {
   size_t i = s.spans.size() - 1;
   while (i > 0 && s.spans[i].b0 > b) i--;
   return s.spans[i];
@@ -247,63 +247,67 @@ struct Sim {
         n_.outputs[0].zero = ns.ins[0].zero;   // (0 * g = 0 for every finite gain; a NaN gain is not worth a special case here)
         break;
       case GA_NODE_BIQUAD: {  // BiQuadFilterNode.cs:87-147
-        n_.outputs[0].bufCh = ns.ins[0].bufCh;
-        n_.outputs[0].silent = ns.ins[0].silent;
-        if (!ns.ins[0].silent && !ns.ins[0].zero) n_.everFed = true;
-        n_.outputs[0].zero = ns.ins[0].zero && !n_.everFed;   // zero input AND zero state
-        ns.bqDynamic = !n_.params[0].events.empty() || !n_.params[1].events.empty() || !n_.params[2].events.empty() ||
+        BiquadS& bq = rec<BiquadS>(n_);
+        bq.outputs[0].bufCh = ns.ins[0].bufCh;
+        bq.outputs[0].silent = ns.ins[0].silent;
+        if (!ns.ins[0].silent && !ns.ins[0].zero) bq.everFed = true;
+        bq.outputs[0].zero = ns.ins[0].zero && !bq.everFed;   // zero input AND zero state
+        ns.bqDynamic = !bq.params[0].events.empty() || !bq.params[1].events.empty() || !bq.params[2].events.empty() ||
                        !ns.pinSilent(0) || !ns.pinSilent(1) || !ns.pinSilent(2) ||   // a modulated parameter moves per sample
-                       n_.bqDynSeq == c.chunkSeq ||   // (went dynamic earlier in this chunk: the coefficient state lives on the device until the chunk ends)
+                       bq.dynSeq == c.chunkSeq ||   // (went dynamic earlier in this chunk: the coefficient state lives on the device until the chunk ends)
                        // the coefficient state is on the device and a signal is still connected to a parameter (silent right now):
                        // the per-sample kernel serves constants too, and the state is not fetched back per chunk (Context::chunkTopology)
-                       (n_.coefOnDevice && (!n_.params[0].modulation.empty() || !n_.params[1].modulation.empty() || !n_.params[2].modulation.empty()));
-        if (ns.bqDynamic && !ns.ins[0].silent) n_.bqDynSeq = c.chunkSeq;
+                       (bq.coefOnDevice && (!bq.params[0].modulation.empty() || !bq.params[1].modulation.empty() || !bq.params[2].modulation.empty()));
+        if (ns.bqDynamic && !ns.ins[0].silent) bq.dynSeq = c.chunkSeq;
         if (!ns.ins[0].silent && ns.bqDynamic) {
           ns.bqActive = true;   // coefficients are refreshed per sample on the device
         } else if (!ns.ins[0].silent) {
           float nyq = c.sampleRate / 2.f;
-          float f = n_.params[0].value;
+          float f = bq.params[0].value;
           f = f < 1.f ? 1.f : (f > nyq ? nyq : f);
-          float q = max_ref(0.001f, n_.params[1].value);   // Math.Max (:124): a NaN Q stays NaN
-          float gainDb = n_.params[2].value;
+          float q = max_ref(0.001f, bq.params[1].value);   // Math.Max (:124): a NaN Q stays NaN
+          float gainDb = bq.params[2].value;
           // usedFreq/usedQ start every block at 1000 / 1.0 (_lastFrequency/_lastQ are never updated, :13-14,111-112)
-          if (n_.coefDirty || std::fabs(f - 1000.f) > 0.001f || std::fabs(q - 1.0f) > 0.0001f) {
-            c.updateBiquadCoefficients(n_, f, q, gainDb);
-            n_.coefDirty = false;
+          if (bq.coefDirty || std::fabs(f - 1000.f) > 0.001f || std::fabs(q - 1.0f) > 0.0001f) {
+            c.updateBiquadCoefficients(bq, f, q, gainDb);
+            bq.coefDirty = false;
           }
           ns.bqActive = true;
-          ns.b0 = n_.b0; ns.b1 = n_.b1; ns.b2 = n_.b2; ns.a1 = n_.a1; ns.a2 = n_.a2;
+          ns.b0 = bq.b0; ns.b1 = bq.b1; ns.b2 = bq.b2; ns.a1 = bq.a1; ns.a2 = bq.a2;
         }
         break;
       }
-      case GA_NODE_CONVOLVER:  // ConvolverNode.cs:102-155
-        if (!n_.ir) {
-          n_.outputs[0].bufCh = ns.ins[0].bufCh;
-          n_.outputs[0].silent = true;
-          n_.outputs[0].zero = false;
+      case GA_NODE_CONVOLVER: {  // ConvolverNode.cs:102-155
+        ConvolverS& cv = rec<ConvolverS>(n_);
+        if (!cv.ir) {
+          cv.outputs[0].bufCh = ns.ins[0].bufCh;
+          cv.outputs[0].silent = true;
+          cv.outputs[0].zero = false;
         } else {
-          n_.outputs[0].bufCh = n_.effectiveOutCh;
-          n_.outputs[0].silent = false;  // MarkAsNonSilent even for silent input (:153)
-          if (!ns.ins[0].silent && !ns.ins[0].zero) n_.everFed = true;
-          n_.outputs[0].zero = !n_.everFed;   // nothing has reached the input yet: the flagged-non-silent output is exact zeros
+          cv.outputs[0].bufCh = cv.effectiveOutCh;
+          cv.outputs[0].silent = false;  // MarkAsNonSilent even for silent input (:153)
+          if (!ns.ins[0].silent && !ns.ins[0].zero) cv.everFed = true;
+          cv.outputs[0].zero = !cv.everFed;   // nothing has reached the input yet: the flagged-non-silent output is exact zeros
         }
         break;
+      }
       case GA_NODE_BUFFER_SOURCE: {
-        const SrcSpan& sp = spanAt(n_, brel);
-        PlayBuf* b = n_.bufId >= 0 ? c.buffers[n_.bufId].get() : nullptr;
+        BufferSourceS& bs = rec<BufferSourceS>(n_);
+        const SrcSpan& sp = spanAt(bs, brel);
+        PlayBuf* b = bs.bufId >= 0 ? c.buffers[bs.bufId].get() : nullptr;
         ns.srcPhase = sp.phase;
-        ns.srcBuf = n_.bufId;
+        ns.srcBuf = bs.bufId;
         if (sp.phase == SRC_PLAY && b) {
-          n_.outputs[0].bufCh = b->channels;
-          n_.outputs[0].silent = false;
+          bs.outputs[0].bufCh = b->channels;
+          bs.outputs[0].silent = false;
           ns.srcPos = sp.pos + (brel - sp.b0) * kBlock;
           ns.srcBlk = sp.blkIdx + (brel - sp.b0);
         } else if (sp.phase == SRC_END && b) {  // whole block cleared (:360-368)
-          n_.outputs[0].bufCh = b->channels;
-          n_.outputs[0].silent = true;
+          bs.outputs[0].bufCh = b->channels;
+          bs.outputs[0].silent = true;
         } else {  // ProduceSilence: 1-channel silent buffer (:391-402)
-          n_.outputs[0].bufCh = 1;
-          n_.outputs[0].silent = true;
+          bs.outputs[0].bufCh = 1;
+          bs.outputs[0].silent = true;
         }
         break;
       }
@@ -329,76 +333,80 @@ struct Sim {
         break;
       }
       case GA_NODE_STREAM_SOURCE: {  // AudioStreamSourceNodeBase.cs:132-301: channel count / silence per block from the host replay
-        const NodeS::StreamBlockInfo bi = brel < (int64_t)n_.stInfo.size() ? n_.stInfo[brel] : NodeS::StreamBlockInfo{1, true};
-        n_.outputs[0].bufCh = bi.outCh;
-        n_.outputs[0].silent = bi.silent;
+        StreamSourceS& st = rec<StreamSourceS>(n_);
+        const StreamSourceS::StreamBlockInfo bi = brel < (int64_t)st.stInfo.size() ? st.stInfo[brel] : StreamSourceS::StreamBlockInfo{1, true};
+        st.outputs[0].bufCh = bi.outCh;
+        st.outputs[0].silent = bi.silent;
         break;
       }
       case GA_NODE_CONSTANT_SOURCE:
       case GA_NODE_OSCILLATOR: {  // always a 1-channel buffer; non-silent in every block that plays (:136, :151)
-        const SrcSpan& sp = spanAt(n_, brel);
+        const SrcSpan& sp = spanAt(schedOf(n_), brel);
         ns.srcPhase = sp.phase;
         n_.outputs[0].bufCh = 1;
         n_.outputs[0].silent = sp.phase != SRC_PLAY;
         break;
       }
       case GA_NODE_STEREO_PANNER: {  // StereoPannerNode.cs:36-74
-        n_.outputs[0].bufCh = 2;
-        n_.outputs[0].silent = ns.ins[0].silent;
-        n_.outputs[0].zero = ns.ins[0].zero;
+        StereoPannerS& pn = rec<StereoPannerS>(n_);
+        pn.outputs[0].bufCh = 2;
+        pn.outputs[0].silent = ns.ins[0].silent;
+        pn.outputs[0].zero = ns.ins[0].zero;
         ns.panMode = ns.ins[0].bufCh == 1 ? 1 : 2;
-        if (!ns.ins[0].silent && (!n_.params[0].events.empty() || !ns.pinSilent(0) || n_.panDynSeq == c.chunkSeq ||
-                                  (n_.panOnDevice && !n_.params[0].modulation.empty()))) {   // (state on the device, a signal still connected: Context::chunkTopology)
-          n_.panDynSeq = c.chunkSeq;
+        if (!ns.ins[0].silent && (!pn.params[0].events.empty() || !ns.pinSilent(0) || pn.dynSeq == c.chunkSeq ||
+                                  (pn.panOnDevice && !pn.params[0].modulation.empty()))) {   // (state on the device, a signal still connected: Context::chunkTopology)
+          pn.dynSeq = c.chunkSeq;
           ns.panDyn = true;   // gains follow the a-rate curve on the device (stereo_panner_dynamic_kernel)
         } else if (!ns.ins[0].silent) {
-          float pan = std::min(std::max(n_.params[0].value, -1.0f), 1.0f);
-          if (pan != n_.panLast) {  // the gains follow the law of the path that sees the change (:92-99, :127-134)
+          float pan = std::min(std::max(pn.params[0].value, -1.0f), 1.0f);
+          if (pan != pn.panLast) {  // the gains follow the law of the path that sees the change (:92-99, :127-134)
             const float PIf = 3.14159265358979323846f;
             float x = ns.panMode == 1 ? (pan + 1.0f) * 0.5f : (pan <= 0.0f ? pan + 1.0f : pan);
-            n_.panGL = std::cos(x * PIf / 2.0f);
-            n_.panGR = std::sin(x * PIf / 2.0f);
-            n_.panLast = pan;
+            pn.panGL = std::cos(x * PIf / 2.0f);
+            pn.panGR = std::sin(x * PIf / 2.0f);
+            pn.panLast = pan;
           }
           ns.pan = pan;
-          ns.panGL = n_.panGL;
-          ns.panGR = n_.panGR;
+          ns.panGL = pn.panGL;
+          ns.panGR = pn.panGR;
         }
         break;
       }
       case GA_NODE_SPATIAL_PANNER: {  // SpatialPannerNode.cs:117-261 over SteamAudioNodeBase.cs:61-70
-        n_.outputs[0].bufCh = 2;
-        n_.outputs[0].silent = ns.ins[0].silent;
-        if (!ns.ins[0].silent && !ns.ins[0].zero) n_.everFed = true;
-        n_.outputs[0].zero = ns.ins[0].zero && !n_.everFed;   // zero input AND zero history
+        SpatialPannerS& sp = rec<SpatialPannerS>(n_);
+        sp.outputs[0].bufCh = 2;
+        sp.outputs[0].silent = ns.ins[0].silent;
+        if (!ns.ins[0].silent && !ns.ins[0].zero) sp.everFed = true;
+        sp.outputs[0].zero = ns.ins[0].zero && !sp.everFed;   // zero input AND zero history
         ns.panMode = ns.ins[0].bufCh == 1 ? 1 : 2;   // mono / stereo input (a change is a new segment: hashSeg)
         // the per-block descriptors (geometry, HRIR selection, fade flag) do not cut segments: they are made per block where the
         // node is planned (Context::planSpatialPanner), from the parameters' timelines and the descriptor of the previous block
         break;
       }
       case GA_NODE_DELAY: {  // DelayNode.cs:43-100
+        DelayS& dl = rec<DelayS>(n_);
         const InSeg& in = ns.ins[0];
         const int ch = in.bufCh;
         // A node whose flag is read from its samples in this chunk (option "delay_flag_exact", Context::chunkTopology): the prediction
         // below runs on a flag of its own and only says from which block on the samples have to be looked at (DelaySpan::rise)
-        bool& audible = n_.delayProbe ? n_.delayShadow : n_.delayAudible;
-        if (ch != n_.delayCh) {   // `_outputBuffer` re-rented: a cleared buffer is silent again (:49-55)
-          n_.delayAudible = false;
-          n_.delayShadow = false;
-          n_.delayCh = ch;
-          if (n_.delayProbe) n_.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
+        bool& audible = dl.delayProbe ? dl.delayShadow : dl.delayAudible;
+        if (ch != dl.delayCh) {   // `_outputBuffer` re-rented: a cleared buffer is silent again (:49-55)
+          dl.delayAudible = false;
+          dl.delayShadow = false;
+          dl.delayCh = ch;
+          if (dl.delayProbe) dl.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
         }
-        if (n_.delayProbe && n_.delaySpans.empty()) n_.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
+        if (dl.delayProbe && dl.delaySpans.empty()) dl.delaySpans.push_back({brel, -1, std::numeric_limits<int64_t>::max(), ch});
         const bool wasAudible = audible;
         const int64_t B = c.currentBlock + brel;   // absolute block of this evaluation
         const int64_t OPEN = std::numeric_limits<int64_t>::max();
-        const int maxD = n_.maxDelaySamples;
-        auto& model = n_.delayModel;
+        const int maxD = dl.maxDelaySamples;
+        auto& model = dl.delayModel;
         // rings that were written since the previous evaluation advanced by the blocks in between
-        if (n_.delayPrevEval >= 0)
-          for (int r = 0; r < std::min((int)model.size(), n_.delayPrevCh); r++) model[r].pos += (B - n_.delayPrevEval) * kBlock;
-        n_.delayPrevEval = B;
-        n_.delayPrevCh = ch;
+        if (dl.delayPrevEval >= 0)
+          for (int r = 0; r < std::min((int)model.size(), dl.delayPrevCh); r++) model[r].pos += (B - dl.delayPrevEval) * kBlock;
+        dl.delayPrevEval = B;
+        dl.delayPrevCh = ch;
         if ((int)model.size() < std::max(ch, 2)) model.resize(std::max(ch, 2));   // EnsureChannelCount (:102-113)
         for (int r = 0; r < (int)model.size(); r++) {
           auto& m = model[r];
@@ -415,8 +423,8 @@ struct Sim {
         // The output buffer's non-silent flag is set by the first non-zero output SAMPLE and never cleared (:72,:92,:96-97).
         // Data is not visible to the control plane: samples that came from a non-silent input block are taken to be non-zero.
         int dmin = 1, dmax = maxD;
-        if (n_.params[0].events.empty() && ns.pinSilent(0)) {
-          int d = (int)(n_.params[0].value * (float)c.sampleRate);
+        if (dl.params[0].events.empty() && ns.pinSilent(0)) {
+          int d = (int)(dl.params[0].value * (float)c.sampleRate);
           d = std::min(std::max(d, 0), maxD);
           dmin = dmax = d;
         }
@@ -426,9 +434,9 @@ struct Sim {
         // audible -- blocks before the delayed audio arrives -- and a consumer whose state was frozen by silence (a biquad with a
         // second connection that ended earlier) would wake up too early.  While audio is on its way the node is evaluated again
         // block by block.
-        const bool timelineOnly = !n_.params[0].events.empty() && ns.pinSilent(0) && blockTimes && brel < (int64_t)blockTimes->size();
+        const bool timelineOnly = !dl.params[0].events.empty() && ns.pinSilent(0) && blockTimes && brel < (int64_t)blockTimes->size();
         if (!audible && timelineOnly) {
-          const ParamS& pd = n_.params[0];
+          const ParamS& pd = dl.params[0];
           const double t0 = (*blockTimes)[brel], dts = 1.0 / c.sampleRate;
           bool pending = false;
           for (int r = 0; r < ch && !audible; r++) {
@@ -471,16 +479,16 @@ struct Sim {
           if (!audible && nextFlip != OPEN && extraBreaks) extraBreaks->push_back(nextFlip - c.currentBlock);
         }
         if (audible && !wasAudible) {
-          if (n_.delayProbe) {
-            n_.delaySpans.back().rise = brel;
-          } else if (c.delayFlagExact && n_.delayPredChunk != c.stats.chunks) {   // (a node that was not accepted: chunkTopology says why)
-            n_.delayPredChunk = c.stats.chunks;
+          if (dl.delayProbe) {
+            dl.delaySpans.back().rise = brel;
+          } else if (c.delayFlagExact && dl.delayPredChunk != c.stats.chunks) {   // (a node that was not accepted: chunkTopology says why)
+            dl.delayPredChunk = c.stats.chunks;
             c.stats.delay_flags_predicted++;
           }
         }
-        ns.delayAudible = n_.delayAudible;   // (an accepted node: false -- stage 2 hands its views out, Context::runTwoStageChunk)
-        n_.outputs[0].bufCh = ch;
-        n_.outputs[0].silent = !audible;
+        ns.delayAudible = dl.delayAudible;   // (an accepted node: false -- stage 2 hands its views out, Context::runTwoStageChunk)
+        dl.outputs[0].bufCh = ch;
+        dl.outputs[0].silent = !audible;
         break;
       }
       default: fail(GA_ERR_UNSUPPORTED, "node type not supported on the device path");
@@ -1011,7 +1019,7 @@ struct ChunkRun {
   std::vector<int> probeDelays;                  // DelayNodes whose flag this chunk reads from their samples (option "delay_flag_exact")
   std::vector<char> stage1;                      // node id -> rendered by stage 1: the modulator cone, the accepted delays and their cones
   bool waited = true;                            // stage 1: the host waited for the probe's words (false: nothing to read back)
-  const int32_t* onsetWords = nullptr;           // stage 1: the words of delay_onset_kernel, read back (NodeS::DelaySpan::word indexes them)
+  const int32_t* onsetWords = nullptr;           // stage 1: the words of delay_onset_kernel, read back (DelayS::DelaySpan::word indexes them)
   struct PreOut { int bufCh; bool silent, zero; };
   std::vector<int> preRow;                       // stage 1: node id -> its first output's row in a snapshot, -1 = not in the cone
   std::vector<std::vector<PreOut>> preSnap;      // stage 1: [segment][row] the cone's output state
@@ -1035,9 +1043,9 @@ inline bool Sim::restorePre(int id) {
     n_.outputs[o].silent = q.silent;
     n_.outputs[o].zero = q.zero;
   }
-  if (n_.delayProbe) {   // the flag of an accepted DelayNode: down until the block in which its samples raised it (delay_onset_kernel)
+  if (n_.type == GA_NODE_DELAY && rec<DelayS>(n_).delayProbe) {   // the flag of an accepted DelayNode: down until the block in which its samples raised it (delay_onset_kernel)
     bool silent = true;
-    for (const NodeS::DelaySpan& sp : n_.delaySpans)
+    for (const DelayS::DelaySpan& sp : rec<DelayS>(n_).delaySpans)
       if (sp.b0 <= brel) silent = brel < sp.onset;
     n_.outputs[0].silent = silent;
     n_.outputs[0].zero = false;

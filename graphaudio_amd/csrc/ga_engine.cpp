@@ -225,25 +225,37 @@ Context::~Context() {
     if (a.p) (void)hipFree(a.p);
   for (auto& a : planesBalt)
     if (a.p) (void)hipFree(a.p);
-  for (auto& np : nodes) {
-    if (np && np->bHistR) (void)hipFree(np->bHistR);
-    if (np && np->bHistI) (void)hipFree(np->bHistI);
-    if (np && np->bOverlap) (void)hipFree(np->bOverlap);
-    if (np && np->dHistBase[0]) (void)hipFree(np->dHistBase[0]);
-    if (np && np->dHistBase[1]) (void)hipFree(np->dHistBase[1]);
-    if (np && np->dTail[0]) (void)hipFree(np->dTail[0]);
-    if (np && np->dTail[1]) (void)hipFree(np->dTail[1]);
-    if (np && np->stWin[0]) (void)hipFree(np->stWin[0]);
-    if (np && np->stWin[1]) (void)hipFree(np->stWin[1]);
-    if (np && np->delayHist) (void)hipFree(np->delayHist);
-    if (np && np->delayLine) (void)hipFree(np->delayLine);
-    if (np && np->oscPhase) (void)hipFree(np->oscPhase);
-    if (np && np->panDev) (void)hipFree(np->panDev);
-    if (np && np->spHist[0]) (void)hipFree(np->spHist[0]);
-    if (np && np->spHist[1]) (void)hipFree(np->spHist[1]);
-    if (np && np->spCarry[0]) (void)hipFree(np->spCarry[0]);
-    if (np && np->spCarry[1]) (void)hipFree(np->spCarry[1]);
-    if (np && np->spDirect) (void)hipFree(np->spDirect);
+  for (auto& np : nodes) {   // the device state of every node, by the type of its record
+    if (!np) continue;
+    auto drop = [](std::initializer_list<void*> ps) {
+      for (void* p : ps)
+        if (p) (void)hipFree(p);
+    };
+    switch (np->type) {
+      case GA_NODE_CONVOLVER: {
+        ConvolverS& cv = rec<ConvolverS>(*np);
+        drop({cv.bHistR, cv.bHistI, cv.bOverlap, cv.dHistBase[0], cv.dHistBase[1], cv.dTail[0], cv.dTail[1]});
+        break;
+      }
+      case GA_NODE_STREAM_SOURCE: {
+        StreamSourceS& st = rec<StreamSourceS>(*np);
+        drop({st.stWin[0], st.stWin[1]});
+        break;
+      }
+      case GA_NODE_DELAY: {
+        DelayS& dl = rec<DelayS>(*np);
+        drop({dl.delayHist, dl.delayLine});
+        break;
+      }
+      case GA_NODE_OSCILLATOR: drop({rec<OscillatorS>(*np).oscPhase}); break;
+      case GA_NODE_STEREO_PANNER: drop({rec<StereoPannerS>(*np).panDev}); break;
+      case GA_NODE_SPATIAL_PANNER: {
+        SpatialPannerS& sp = rec<SpatialPannerS>(*np);
+        drop({sp.spHist[0], sp.spHist[1], sp.spCarry[0], sp.spCarry[1], sp.spDirect});
+        break;
+      }
+      default: break;
+    }
   }
   for (auto& kv : tw16) (void)hipFree(kv.second);
   if (rateModDev) (void)hipFree(rateModDev);
@@ -347,14 +359,27 @@ void Context::collectGarbage() {
     std::vector<char> used(buffers.size(), 0);
     for (auto& np : nodes) {
       if (!np || np->disposed) continue;
-      if (np->bufId >= 0 && np->bufId < (int)used.size()) used[np->bufId] = 1;
-      if (np->irBuf >= 0 && np->irBuf < (int)used.size()) used[np->irBuf] = 1;
-      for (auto& e : np->dHistExt)   // a convolver's input history that is a span of the buffer (NodeS::dHistExt)
-        if (e.first && e.second >= 0 && e.second < (int)used.size()) used[e.second] = 1;
-      if (np->type == GA_NODE_STREAM_SOURCE) {   // queued, current and processed (not yet handed back) buffers of a stream
-        if (np->stCurrent >= 0 && np->stCurrent < (int)used.size()) used[np->stCurrent] = 1;
-        for (int id : np->stQueued) if (id >= 0 && id < (int)used.size()) used[id] = 1;
-        for (int id : np->stProcessed) if (id >= 0 && id < (int)used.size()) used[id] = 1;
+      auto use = [&](int id) {
+        if (id >= 0 && id < (int)used.size()) used[id] = 1;
+      };
+      switch (np->type) {
+        case GA_NODE_BUFFER_SOURCE: use(rec<BufferSourceS>(*np).bufId); break;
+        case GA_NODE_SPATIAL_PANNER: use(rec<SpatialPannerS>(*np).irBuf); break;
+        case GA_NODE_CONVOLVER: {
+          const ConvolverS& cv = rec<ConvolverS>(*np);
+          use(cv.irBuf);
+          for (auto& e : cv.dHistExt)   // an input history that is a span of the buffer (ConvolverS::dHistExt)
+            if (e.first) use(e.second);
+          break;
+        }
+        case GA_NODE_STREAM_SOURCE: {   // queued, current and processed (not yet handed back) buffers of a stream
+          const StreamSourceS& st = rec<StreamSourceS>(*np);
+          use(st.stCurrent);
+          for (int id : st.stQueued) use(id);
+          for (int id : st.stProcessed) use(id);
+          break;
+        }
+        default: break;
       }
     }
     std::vector<int> keep;
@@ -551,12 +576,13 @@ void Context::doDispose(int id) {
   for (int p = 0; p < (int)n.params.size(); p++) inputDisconnectAll(InRef{id, -1 - p});
   // OnDispose
   if (n.type == GA_NODE_DELAY) {   // the delay lines go with the node
+    DelayS& d = rec<DelayS>(n);
     if (stream) (void)hipStreamSynchronize(stream);
-    if (n.delayHist) dfree(n.delayHist, (size_t)n.maxDelaySamples * n.delayHistRings * sizeof(float));
-    if (n.delayLine) dfree(n.delayLine, ((size_t)n.maxDelaySamples + (size_t)n.delayCap) * n.delayLineRings * sizeof(float));
-    n.delayHist = n.delayLine = nullptr;
-    n.delayHistRings = n.delayLineRings = 0;
-    n.delayCap = 0;
+    if (d.delayHist) dfree(d.delayHist, (size_t)d.maxDelaySamples * d.delayHistRings * sizeof(float));
+    if (d.delayLine) dfree(d.delayLine, ((size_t)d.maxDelaySamples + (size_t)d.delayCap) * d.delayLineRings * sizeof(float));
+    d.delayHist = d.delayLine = nullptr;
+    d.delayHistRings = d.delayLineRings = 0;
+    d.delayCap = 0;
   }
   if (n.staleBuf) {   // (feedback cycles: the kept output block goes with the node)
     if (stream) (void)hipStreamSynchronize(stream);
@@ -566,43 +592,48 @@ void Context::doDispose(int id) {
     n.staleRows = 0;
   }
   if (n.type == GA_NODE_SPATIAL_PANNER) {   // the carried input history goes with the node, the HRIR set is let go
-    if (n.spHist[0]) {
+    SpatialPannerS& sp = rec<SpatialPannerS>(n);
+    if (sp.spHist[0]) {
       if (stream) (void)hipStreamSynchronize(stream);
-      for (float*& h : n.spHist) {
+      for (float*& h : sp.spHist) {
         dfree(h, kSpatialMaxTaps * sizeof(float));
         h = nullptr;
       }
     }
-    if (n.spCarry[0]) {
+    if (sp.spCarry[0]) {
       if (stream) (void)hipStreamSynchronize(stream);
-      for (SpatialCarry*& h : n.spCarry) {
+      for (SpatialCarry*& h : sp.spCarry) {
         dfree(h, sizeof(SpatialCarry));
         h = nullptr;
       }
     }
-    if (n.spDirect) {
+    if (sp.spDirect) {
       if (stream) (void)hipStreamSynchronize(stream);
-      dfree(n.spDirect, sizeof(SpatialDirectState));
-      n.spDirect = nullptr;
+      dfree(sp.spDirect, sizeof(SpatialDirectState));
+      sp.spDirect = nullptr;
     }
-    n.spOnDevice = n.spEqOnDevice = false;
-    n.irBuf = -1;
-    n.hrirRequested = -1;
+    sp.spOnDevice = sp.spEqOnDevice = false;
+    sp.irBuf = -1;
+    sp.hrirRequested = -1;
   }
-  if (n.type == GA_NODE_BUFFER_SOURCE) n.bufId = -1;  // AudioBufferSourceNode.cs:412
-  if (n.type == GA_NODE_STREAM_SOURCE && n.stState != GA_STREAM_STOPPED) {   // AudioStreamSourceNodeBase.cs:315-327
-    n.stState = GA_STREAM_STOPPED;
-    streamFlushToProcessed(n);
+  if (n.type == GA_NODE_BUFFER_SOURCE) rec<BufferSourceS>(n).bufId = -1;  // AudioBufferSourceNode.cs:412
+  if (n.type == GA_NODE_STREAM_SOURCE) {   // AudioStreamSourceNodeBase.cs:315-327
+    StreamSourceS& st = rec<StreamSourceS>(n);
+    if (st.stState != GA_STREAM_STOPPED) {
+      st.stState = GA_STREAM_STOPPED;
+      streamFlushToProcessed(st);
+    }
   }
   if (n.type == GA_NODE_CONVOLVER) {                   // ConvolverNode.cs:166-175
-    releaseConvState(n);   // while n.ir still tells the size of the private history (device byte accounting)
-    n.ir.reset();
-    n.irBuf = -1;
+    ConvolverS& cv = rec<ConvolverS>(n);
+    releaseConvState(cv);   // while cv.ir still tells the size of the private history (device byte accounting)
+    cv.ir.reset();
+    cv.irBuf = -1;
   }
 }
 
 // a node loses its PartitionedConvolver instances (Buffer reassigned / disposed): rows and private state are released
-void Context::releaseConvState(NodeS& n) {
+void Context::releaseConvState(ConvolverS& n) {
   graphVersion++;   // the node's impulse response (hence its convolver depth contribution) changes
   for (auto& r : n.convRows)
     if (r.group) r.group->rows[r.idx] = {-1, 0};
@@ -658,8 +689,8 @@ void Context::flushPlaneHistories(int pair) {
   std::vector<HistJobB> jobs;
   int maxh = 1;
   for (int id : bResidents[pair]) {
-    NodeS* n = node(id);
-    if (!n || n->bHistPlane != pair || !n->ir || !n->bHistR) continue;
+    ConvolverS* n = &rec<ConvolverS>(*node(id));
+    if (n->bHistPlane != pair || !n->ir || !n->bHistR) continue;
     const int h = n->ir->P - 1;
     const size_t hstride = (size_t)kBins * std::max(h, 1);
     for (int c = 0; c < n->bHistNx && h > 0; c++) {
@@ -728,11 +759,11 @@ ConvRowRef Context::addGroupRow(const std::shared_ptr<IrSpectra>& ir, int ch, in
 // the device).  One reverse sweep over the processing order, per chunk.
 void Context::refOrderSensitivity(const std::vector<int>& topo) {
   bool anyConv = false;
-  for (int id : topo) anyConv = anyConv || (nodes[id]->type == GA_NODE_CONVOLVER && nodes[id]->ir);
+  for (int id : topo) anyConv = anyConv || (nodes[id]->type == GA_NODE_CONVOLVER && rec<ConvolverS>(*nodes[id]).ir);
   if (!anyConv) return;
   if (convRefOrder != 1) {
     for (int id : topo)
-      if (nodes[id]->type == GA_NODE_CONVOLVER) nodes[id]->refSens = convRefOrder == 2;
+      if (nodes[id]->type == GA_NODE_CONVOLVER) rec<ConvolverS>(*nodes[id]).refSens = convRefOrder == 2;
     return;
   }
   // (a graph with feedback: the sweep follows the reference's processing order of the WHOLE graph -- the planning order may have cut
@@ -760,7 +791,7 @@ void Context::refOrderSensitivity(const std::vector<int>& topo) {
         f = f < 1.f ? 1.f : (f > nyq ? nyq : f);
         const float q = max_ref(0.001f, nd.params[1].value);
         float o[5];
-        biquadCoefficients(nd.filterType, (float)sampleRate, f, q, nd.params[2].value, o);
+        biquadCoefficients(rec<BiquadS>(nd).filterType, (float)sampleRate, f, q, nd.params[2].value, o);
         s = biquadDeviation(o, 1) > convRefMinDeviation;
       }
     }
@@ -770,7 +801,7 @@ void Context::refOrderSensitivity(const std::vector<int>& topo) {
         if (r.input < 0 || sens[r.node]) s = true;
       }
     sens[*it] = s ? 1 : 0;
-    if (nd.type == GA_NODE_CONVOLVER) nd.refSens = s;
+    if (nd.type == GA_NODE_CONVOLVER) rec<ConvolverS>(nd).refSens = s;
   }
 }
 
@@ -781,7 +812,7 @@ void Context::assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks)
   // depth moves its rows (FDL column + overlap tail) to the group of that depth.  A node that is no longer reachable from the
   // destination is not processed at all (pull model): its rows wait in a group of their own (depth -1, never executed), so
   // that the delay line keeps its content, and come back the same way when the node is connected again.
-  auto moveRows = [&](NodeS& nd, int id, int depth) {
+  auto moveRows = [&](ConvolverS& nd, int id, int depth) {
       for (size_t slot = 0; slot < nd.convRows.size(); slot++) {
         ConvRowRef old = nd.convRows[slot];
         if (old.group->depth == depth) continue;
@@ -805,13 +836,14 @@ void Context::assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks)
       }
   };
   for (auto& np : nodes) {
-    if (!np) continue;
-    NodeS& nd = *np;
-    if (nd.type == GA_NODE_CONVOLVER && nd.ir && nd.convPath == 1 && !nd.reachable && !nd.disposed) moveRows(nd, nd.id, -1);
+    if (!np || np->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*np);
+    if (nd.ir && nd.convPath == 1 && !nd.reachable && !nd.disposed) moveRows(nd, nd.id, -1);
   }
   for (int id : topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_CONVOLVER || !nd.ir) continue;
+    if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+    if (!nd.ir) continue;
     users[nd.ir.get()]++;
     if (nd.convPath == 1) {
       hasA[nd.ir.get()] = true;
@@ -819,8 +851,9 @@ void Context::assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks)
     }
   }
   for (int id : topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.convPath != 0) continue;
+    if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+    if (!nd.ir || nd.convPath != 0) continue;
     IrSpectra* ir = nd.ir.get();
     const int channels = ir->nch;
     const bool pathC = useTimeFft && ir->P > 64 && ir->P <= 1024;   // FFT along the block axis (N2 <= 4096)
@@ -945,7 +978,7 @@ void biquadCoefficients(int filterType, float sampleRate, float frequency, float
   o[3] = A1 / a0;
   o[4] = A2 / a0;
 }
-void Context::updateBiquadCoefficients(NodeS& n, float frequency, float q, float gain) {
+void Context::updateBiquadCoefficients(BiquadS& n, float frequency, float q, float gain) {
   // The reference recomputes the coefficients at sample 0 of every block (BiQuadFilterNode.cs:111-126: its "last" values are
   // never updated) -- with unchanged parameters that is the same arithmetic on the same inputs: remember the result.
   if (n.coefMemoValid && n.coefMemoType == n.filterType && n.coefMemoIn[0] == frequency && n.coefMemoIn[1] == q && n.coefMemoIn[2] == gain) {
@@ -1063,7 +1096,7 @@ const float2* Context::twiddles16(int N2) {
 }
 
 // AudioStreamNodeBase.FlushToProcessed (AudioStreamSourceNodeBase.cs:95-116)
-void Context::streamFlushToProcessed(NodeS& s) {
+void Context::streamFlushToProcessed(StreamSourceS& s) {
   if (s.stCurrent >= 0) s.stProcessed.push_back(s.stCurrent);
   s.stCurrent = -1;
   while (!s.stQueued.empty()) {

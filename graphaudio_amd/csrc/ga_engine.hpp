@@ -150,29 +150,67 @@ struct SrcSpan {
   int64_t blkIdx;  // index of b0 in the resampler trajectory (resampled playback)
 };
 
+// ---- node records ----
+// A node's type is fixed when it is created, so its record is chosen there (makeNode): NodeS is what EVERY node has, and each type
+// with state of its own derives a record from it (one allocation, the common part first).  State that several types have is a small
+// sub-record those records include.  rec<R>(node) is the one way from a NodeS to its typed record; it checks `type` on every call.
 struct NodeS {
   int id = 0, type = 0;
   bool disposed = false;
-  std::vector<InputS> inputs;
-  std::vector<OutputS> outputs;
-  std::vector<ParamS> params;
-  int64_t lastProcessedBlock = -1;
   bool isProcessing = false;
   bool reachable = false;
   bool prevReachable = false;   // reachable in the topology the PREVIOUS chunk ran on (= it was evaluated there; chunkTopology)
   int level = 0, depth = 0;
+  int64_t lastProcessedBlock = -1;
+  std::vector<InputS> inputs;
+  std::vector<OutputS> outputs;
+  std::vector<ParamS> params;
+  // feedback cycles: a node that some consumer pulls while it is being processed keeps a copy of the block it put out last
+  // (shape of its output views: one row of 128 frames per channel, per output for a ChannelSplitterNode)
+  bool staleProducer = false;
+  float* staleBuf = nullptr;   // the copy consumers read in this chunk: [staleRows][128]
+  float* staleNext = nullptr;  // ... and the one this chunk's output is written to (the two swap when the chunk is planned)
+  int staleRows = 0;
+  uint64_t staleSeq = 0;       // Context::chunkSeq of the chunk that last wrote staleBuf (chunkStaleCommit): a node that stops being pulled
+                               // from inside its own evaluation and later is again must not find the block it kept back then
+  NodeS() = default;
+  NodeS(const NodeS&) = delete;
+  NodeS& operator=(const NodeS&) = delete;
+  virtual ~NodeS() = default;   // (Context::nodes owns every record through this type)
+};
+// ChannelSplitterNode, ChannelMergerNode, GainNode and the destination have no state beyond NodeS.
 
-  // AudioBufferSourceNode (AudioBufferSourceNode.cs:15-30)
-  int bufId = -1;
+// scheduled sources (AudioBufferSourceNode.cs:15-30; ConstantSourceNode and OscillatorNode keep the same fields)
+struct SchedState {
   bool hasStarted = false, hasStopped = false, endedRaised = false;
   double startTime = std::nan(""), stopTime = std::nan("");
-  double offset = 0, duration = std::numeric_limits<double>::infinity();
+  int64_t schedLo = 0, schedHi = 0;  // per chunk: frames [lo, hi) of the chunk in which the scheduled source plays
+  std::vector<SrcSpan> spans;        // per chunk: the phase timeline (planSource, planScheduled)
+};
+// nodes whose output depends on earlier input (biquad, convolver, spatial panner)
+struct FedState {
+  bool everFed = false;   // (control plane) a non-silent, not-known-zero block has reached this node's input: its state / tail may be non-zero
+};
+// nodes that read an impulse-response buffer (the convolver's IR, the spatial panner's HRIR set); Context::collectGarbage keeps it alive
+struct IrRef {
+  int irBuf = -1;
+};
+// nodes whose parameters can be automated per sample (biquad, stereo panner)
+struct DynStamp {
+  uint64_t dynSeq = ~0ull;   // chunk in which the node ran its per-sample kernel (Context::chunkSeq)
+};
+
+struct ScheduledS : NodeS, SchedState {};   // (what schedOf hands out: the three records below derive from it)
+
+struct BufferSourceS : ScheduledS {
+  static constexpr int kType = GA_NODE_BUFFER_SOURCE;
+  int bufId = -1;
   int64_t playbackPosition = 0;
+  double offset = 0, duration = std::numeric_limits<double>::infinity();
   bool loop = false;
   double loopStart = 0, loopEnd = 0;
   int64_t rsBlocks = 0;          // resampler: blocks played so far (index into the trajectory)
   int64_t rsStartPos = 0;        // resampler: buffer index where consumption started
-  std::vector<SrcSpan> spans;    // per-chunk plan
   // general replay mode (GsrBlock): entered -- for good -- when the source loops while resampling or its rate moves
   bool gsr = false;
   double rsRate = 0.0;           // trajectory mode: the effective rate the trajectory belongs to
@@ -189,17 +227,29 @@ struct NodeS {
   const GsrBlock* gsrDesc = nullptr;
   int64_t gsrWalked = -1;
   GsrBlock gsrTail{};
-  // ConstantSourceNode / OscillatorNode share hasStarted/hasStopped/startTime/stopTime/endedRaised with the buffer source
+};
+
+struct ConstantSourceS : ScheduledS {
+  static constexpr int kType = GA_NODE_CONSTANT_SOURCE;
+};
+
+struct OscillatorS : ScheduledS {
+  static constexpr int kType = GA_NODE_OSCILLATOR;
   int oscType = 0;                 // OscillatorNode._type
   double* oscPhase = nullptr;      // device: OscillatorNode._phase (one double)
   bool oscPhaseReset = false;      // Start() sets _phase = 0 (OscillatorNode.cs:62)
-  int64_t schedLo = 0, schedHi = 0;  // per chunk: frames [lo, hi) of the chunk in which the scheduled source plays
-  // StereoPannerNode (StereoPannerNode.cs:12-14)
+};
+
+struct StereoPannerS : NodeS, DynStamp {   // StereoPannerNode.cs:12-14
+  static constexpr int kType = GA_NODE_STEREO_PANNER;
   float panLast = std::nanf(""), panGL = 0.5f, panGR = 0.5f;
   PanState* panDev = nullptr;      // device copy of the three, authoritative while pan is automated (panOnDevice)
   bool panOnDevice = false;
-  uint64_t bqDynSeq = ~0ull, panDynSeq = ~0ull;   // (chunk in which the node ran its per-sample kernel: Context::chunkSeq)
-  // DelayNode (DelayNode.cs:13-15)
+};
+
+struct DelayS : NodeS {   // DelayNode.cs:13-15
+  static constexpr int kType = GA_NODE_DELAY;
+  bool delaySplit = false;     // (per chunk) a DelayNode at which a feedback loop is cut: reader in front of everything, writer at its level
   int maxDelaySamples = 0;
   int delayCh = 0;                 // channels of `_outputBuffer` (re-rented, i.e. silent again, when the count changes)
   int delayRings = 0;              // CircularBuffers allocated so far (2 at construction, grown on demand)
@@ -236,7 +286,10 @@ struct NodeS {
   std::vector<DelayRingModel> delayModel;
   int64_t delayPrevEval = -1;                             // absolute block of the previous evaluation
   int delayPrevCh = 0;
-  // BiQuadFilterNode (BiQuadFilterNode.cs:12-19)
+};
+
+struct BiquadS : NodeS, FedState, DynStamp {   // BiQuadFilterNode.cs:12-19
+  static constexpr int kType = GA_NODE_BIQUAD;
   int filterType = GA_FILTER_LOWPASS;
   float b0 = 0, b1 = 0, b2 = 0, a1 = 0, a2 = 0;
   bool coefDirty = true;
@@ -248,8 +301,10 @@ struct NodeS {
   int bqTwinN = 32;                 // channels 0 .. bqTwinN-1 hold the SAME filter state (all zero at first; kept equal while the channels are
                                     // fed the same signal -- mono material in a stereo node -- and evaluated once: planBiquad, BiquadJob::twins)
   bool coefOnDevice = false;        // the device copy of the coefficients is newer than b0..a2 above (automated run)
-  // ConvolverNode (ConvolverNode.cs:12-16,87,95)
-  int irBuf = -1;
+};
+
+struct ConvolverS : NodeS, FedState, IrRef {   // ConvolverNode.cs:12-16,87,95
+  static constexpr int kType = GA_NODE_CONVOLVER;
   std::shared_ptr<IrSpectra> ir;
   int effectiveOutCh = 0;
   bool isTrueStereo = false, normalize = true, enableTrueStereo = true;
@@ -279,7 +334,6 @@ struct NodeS {
   int64_t dHistLen = 0;
   int dHistCur = 0;
   bool dHistZero = true;
-  bool everFed = false;   // (control plane) a non-silent, not-known-zero block has reached this node's input: its state / tail may be non-zero
   // ... and the LEADER of a fused group (or a convolver on its own) carries, per output channel, what the input so far adds to
   // the samples behind the last chunk's end (ga_plan_conv.cpp, planCoarseStage): valid for the next chunk only, and only while the
   // group's signature is the same; the input histories above stay the authoritative state
@@ -287,8 +341,20 @@ struct NodeS {
   int64_t dTailLen = 0;
   int dTailCh = 0, dTailCur = 0;
   uint64_t dTailSig = 0, dTailSeq = ~0ull - 1;
-  // AudioStreamNodeBase (GraphAudio.IO/AudioStreamSourceNodeBase.cs:21-28): queue state lives on the host (indices only), the
-  // resampler window of every channel lives on the device between chunks (stWin, double buffered), Pos / Ready on the host
+  // per chunk: convolver outputs that one summing input consumes are summed as spectra (Context::planCoarseFusion);
+  // the leader's output slabs carry the sum, the other members contribute no time-domain signal of their own
+  int dLeader = -1;
+  int dGroupSize = 0;   // (on a leader) members of its fused group in this chunk, itself included
+  // formulation R (the reference's own order and arithmetic, launch_refmac): refSens = the output reaches arithmetic that amplifies
+  // or quantises last-bit differences (Context::refOrderSensitivity, per chunk); refOrder = this chunk evaluates the node that way
+  // (nodes on the B / C state layout: spectra history + overlap, which R shares)
+  bool refSens = false, refOrder = false;
+};
+
+// AudioStreamNodeBase (GraphAudio.IO/AudioStreamSourceNodeBase.cs:21-28): queue state lives on the host (indices only), the
+// resampler window of every channel lives on the device between chunks (stWin, double buffered), Pos / Ready on the host
+struct StreamSourceS : NodeS {
+  static constexpr int kType = GA_NODE_STREAM_SOURCE;
   std::deque<int> stQueued, stProcessed;   // buffer ids
   int stCurrent = -1;
   int64_t stPos = 0;
@@ -311,18 +377,14 @@ struct NodeS {
   bool stFed = false;                       // the chunk's pieces moved a resampler window
   uint64_t stBlocksOff = 0, stPiecesOff = 0, stSegsOff = 0;
   bool stUploaded = false;
-  // per chunk: convolver outputs that one summing input consumes are summed as spectra (Context::planCoarseFusion);
-  // the leader's output slabs carry the sum, the other members contribute no time-domain signal of their own
-  int dLeader = -1;
-  int dGroupSize = 0;   // (on a leader) members of its fused group in this chunk, itself included
-  // formulation R (the reference's own order and arithmetic, launch_refmac): refSens = the output reaches arithmetic that amplifies
-  // or quantises last-bit differences (Context::refOrderSensitivity, per chunk); refOrder = this chunk evaluates the node that way
-  // (nodes on the B / C state layout: spectra history + overlap, which R shares)
-  bool refSens = false, refOrder = false;
-  // SpatialPannerNode (SpatialPannerNode.cs; DESIGN.md "SpatialPannerNode").  The HRIR set is buffer `irBuf`.  Control plane: the
-  // descriptor of the previous PROCESSED block (spPrev, valid unless the node is new or its last input block was silent) -- it
-  // carries across chunks and render calls.  Device: the last kSpatialMaxTaps samples of the mono mix, double buffered (a chunk
-  // reads one copy and writes the other).
+};
+
+// SpatialPannerNode (SpatialPannerNode.cs; DESIGN.md "SpatialPannerNode").  The HRIR set is buffer `irBuf`.  Control plane: the
+// descriptor of the previous PROCESSED block (spPrev, valid unless the node is new or its last input block was silent) -- it
+// carries across chunks and render calls.  Device: the last kSpatialMaxTaps samples of the mono mix, double buffered (a chunk
+// reads one copy and writes the other).
+struct SpatialPannerS : NodeS, FedState, IrRef {
+  static constexpr int kType = GA_NODE_SPATIAL_PANNER;
   int distanceModel = GA_DISTANCE_INVERSE;
   int hrirAzimuths = 1;
   int hrirRequested = -1;            // the set the host assigned last (the assignment itself is a queued command): what hrirAzimuths is checked against
@@ -359,16 +421,146 @@ struct NodeS {
   const void* spExec = nullptr;
   size_t spDescOff = 0, spSegOff = 0;
   int spJob = -1;
-  // feedback cycles: a node that some consumer pulls while it is being processed keeps a copy of the block it put out last
-  // (shape of its output views: one row of 128 frames per channel, per output for a ChannelSplitterNode)
-  bool staleProducer = false;
-  bool delaySplit = false;     // (per chunk) a DelayNode at which a feedback loop is cut: reader in front of everything, writer at its level
-  float* staleBuf = nullptr;   // the copy consumers read in this chunk: [staleRows][128]
-  float* staleNext = nullptr;  // ... and the one this chunk's output is written to (the two swap when the chunk is planned)
-  int staleRows = 0;
-  uint64_t staleSeq = 0;       // Context::chunkSeq of the chunk that last wrote staleBuf (chunkStaleCommit): a node that stops being pulled
-                               // from inside its own evaluation and later is again must not find the block it kept back then
 };
+
+// The typed record of a node.  The check is always on: `type` sits in the record's first cache line, and a planner or an API call
+// that reaches for another type's state fails here instead of reading a neighbour's bytes.
+// (the failure is one out-of-line call, so that a check costs its caller a compare and a branch and no string code)
+[[noreturn]] __attribute__((cold, noinline)) inline void failWrongNodeType() { fail(GA_ERR_INVALID_ARGUMENT, "node has the wrong type for this call"); }
+template <class R>
+inline R& rec(NodeS& n) {
+  if (__builtin_expect(n.type != R::kType, 0)) failWrongNodeType();
+  return static_cast<R&>(n);
+}
+template <class R>
+inline const R& rec(const NodeS& n) { return rec<R>(const_cast<NodeS&>(n)); }
+// ... and the schedule of a scheduled source of any of the three types, for code that serves all of them: the same check against
+// the one list of those types (a new scheduled source derives from ScheduledS and is named here)
+inline bool isScheduledSource(int type) { return type == GA_NODE_BUFFER_SOURCE || type == GA_NODE_CONSTANT_SOURCE || type == GA_NODE_OSCILLATOR; }
+inline SchedState& schedOf(NodeS& n) {
+  if (__builtin_expect(!isScheduledSource(n.type), 0)) failWrongNodeType();
+  return static_cast<ScheduledS&>(n);
+}
+inline bool hasImpulseResponse(const NodeS& n) {   // a ConvolverNode that convolves: one more convolver depth behind it
+  return n.type == GA_NODE_CONVOLVER && rec<ConvolverS>(n).ir != nullptr;
+}
+
+inline ParamS makeParam(float def, float mn, float mx, bool arate) {
+  ParamS p;
+  p.def = def;
+  p.minv = mn;
+  p.maxv = mx;
+  p.arate = arate;
+  p.value = def;
+  return p;
+}
+
+// The record of a new node of `type`: inputs, outputs and parameters as the reference's constructors make them (`arg`: the number of
+// outputs / inputs of a splitter / merger, a DelayNode's maxDelayTime).  ga_node_create_ex and the destination of ga_context_create.
+inline std::unique_ptr<NodeS> makeNode(int type, int id, double arg, int sampleRate) {   // (GA_NODE_DESTINATION included: ga_node_create_ex refuses it)
+  const float FMAX = std::numeric_limits<float>::max();
+  std::unique_ptr<NodeS> n;
+  auto shape = [&](int ins, int outs, int params) {   // (each vector is sized once: one allocation apiece)
+    n->inputs.resize(ins);
+    n->outputs.resize(outs);
+    n->params.reserve(params);
+  };
+  auto clampedStereoInput = [&]() {
+    n->inputs[0].channelCount = 2;
+    n->inputs[0].mode = GA_COUNT_MODE_CLAMPED_MAX;
+    n->inputs[0].interp = GA_INTERP_SPEAKERS;
+  };
+  switch (type) {
+    case GA_NODE_DESTINATION:   // AudioDestinationNode: 1 input with channelCount 2, no outputs (:17-21)
+      n = std::make_unique<NodeS>();
+      shape(1, 0, 0);
+      n->inputs[0].channelCount = 2;
+      break;
+    case GA_NODE_BUFFER_SOURCE:
+      n = std::make_unique<BufferSourceS>();
+      shape(0, 1, 1);
+      n->params.push_back(makeParam(1.f, 0.001f, 1000.f, false));  // AudioBufferSourceNode.cs:76
+      break;
+    case GA_NODE_GAIN:
+      n = std::make_unique<NodeS>();
+      shape(1, 1, 1);
+      n->params.push_back(makeParam(1.f, -FMAX, FMAX, true));  // GainNode.cs:21-26
+      break;
+    case GA_NODE_BIQUAD:   // (the constructor's coefficient update, BiQuadFilterNode.cs:84, is the caller's: Context::updateBiquadCoefficients)
+      n = std::make_unique<BiquadS>();
+      shape(1, 1, 3);
+      n->params.push_back(makeParam(1000.f, 1.f, sampleRate / 2.f, true));  // BiQuadFilterNode.cs:63-82
+      n->params.push_back(makeParam(1.f, 0.001f, 1000.f, true));
+      n->params.push_back(makeParam(0.f, -60.f, 60.f, false));
+      break;
+    case GA_NODE_CONVOLVER:
+      n = std::make_unique<ConvolverS>();
+      shape(1, 1, 0);
+      break;
+    case GA_NODE_CHANNEL_SPLITTER:   // ChannelSplitterNode.cs:14-22
+    case GA_NODE_CHANNEL_MERGER: {   // ChannelMergerNode.cs:14-21
+      int cnt = (int)arg;
+      if (cnt < 1 || cnt > 32) fail(GA_ERR_OUT_OF_RANGE, type == GA_NODE_CHANNEL_SPLITTER ? "numberOfOutputs" : "numberOfInputs");
+      n = std::make_unique<NodeS>();
+      shape(type == GA_NODE_CHANNEL_SPLITTER ? 1 : cnt, type == GA_NODE_CHANNEL_SPLITTER ? cnt : 1, 0);
+      break;
+    }
+    case GA_NODE_CONSTANT_SOURCE:    // ConstantSourceNode.cs:29-38
+      n = std::make_unique<ConstantSourceS>();
+      shape(0, 1, 1);
+      n->params.push_back(makeParam(1.f, -FMAX, FMAX, true));
+      break;
+    case GA_NODE_STEREO_PANNER:      // StereoPannerNode.cs:21-34
+      n = std::make_unique<StereoPannerS>();
+      shape(1, 1, 1);
+      clampedStereoInput();
+      n->params.push_back(makeParam(0.f, -1.f, 1.f, true));
+      break;
+    case GA_NODE_OSCILLATOR:         // OscillatorNode.cs:43-52
+      n = std::make_unique<OscillatorS>();
+      shape(0, 1, 1);
+      n->params.push_back(makeParam(440.f, 0.f, sampleRate / 2.f, true));
+      break;
+    case GA_NODE_DELAY: {            // DelayNode.cs:22-41
+      if (!(arg > 0) || arg > 10) fail(GA_ERR_OUT_OF_RANGE, "maxDelayTime");
+      auto d = std::make_unique<DelayS>();
+      d->maxDelaySamples = (int)(arg * sampleRate);
+      if (d->maxDelaySamples < 1) fail(GA_ERR_OUT_OF_RANGE, "maxDelayTime");
+      d->delayRings = 2;
+      n = std::move(d);
+      shape(1, 1, 1);
+      n->params.push_back(makeParam(0.f, 0.f, (float)arg, true));
+      break;
+    }
+    case GA_NODE_STREAM_SOURCE:      // AudioStreamSourceNodeBase.cs:59-67
+      n = std::make_unique<StreamSourceS>();
+      shape(0, 1, 1);
+      n->params.push_back(makeParam(1.f, 0.001f, 1000.f, false));
+      break;
+    case GA_NODE_SPATIAL_PANNER: {   // SpatialPannerNode.cs:94-114 (float.MinValue is -float.MaxValue)
+      n = std::make_unique<SpatialPannerS>();
+      shape(1, 1, GA_SPATIAL_PARAM_COUNT);
+      clampedStereoInput();
+      for (int i = 0; i < 3; i++) n->params.push_back(makeParam(0.f, -FMAX, FMAX, false));   // positionX/Y/Z
+      n->params.push_back(makeParam(1.f, -1.f, 1.f, false));                                 // orientationX
+      n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationY
+      n->params.push_back(makeParam(0.f, -1.f, 1.f, false));                                 // orientationZ
+      n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // refDistance
+      n->params.push_back(makeParam(10000.f, 0.f, FMAX, false));                             // maxDistance
+      n->params.push_back(makeParam(1.f, 0.f, FMAX, false));                                 // rolloffFactor
+      n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneInnerAngle
+      n->params.push_back(makeParam(360.f, 0.f, 360.f, false));                              // coneOuterAngle
+      n->params.push_back(makeParam(0.f, 0.f, 1.f, false));                                  // coneOuterGain
+      n->params.push_back(makeParam(1.f, 0.f, 1.f, false));                                  // spatialBlend
+      for (int i = 0; i < 4; i++) n->params.push_back(makeParam(0.f, 0.f, 1.f, false));      // occlusion, transmissionLow/Mid/High
+      break;
+    }
+    default: fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");
+  }
+  n->id = id;
+  n->type = type;
+  return n;
+}
 
 // A vector with inline room for N elements (heap only beyond): the per-node, per-segment records of the control-plane
 // simulation and of the planner are almost always one input with one term and a channel or two, and with tens of thousands of
@@ -497,7 +689,7 @@ struct NodeSeg {
   int id = 0;
   int type = 0;   // (the node's type, so that a replayed record is dispatched without touching the node: Context::chunkSimulate)
   // ... and what the planner's sorting / cascade-fusion sweeps ask of every node, so that only the planning pass itself touches the
-  // 1.2 KB node records (config 4: 28,672 of them, three sweeps of cache misses per chunk): set when the record is made, valid
+  // node records (config 4: 28,672 of them, three sweeps of cache misses per chunk): set when the record is made, valid
   // while the graph stands (a replayed record belongs to the same graph version)
   int16_t level = 0, depth = 0;
   bool fan1 = false;   // output 0 feeds exactly one input
@@ -723,7 +915,7 @@ struct Context {
   void doDispose(int id);
 
   std::shared_ptr<IrSpectra> irSpectra(int bufId, bool normalize);
-  void releaseConvState(NodeS& n);
+  void releaseConvState(ConvolverS& n);
   void refOrderSensitivity(const std::vector<int>& topo);
   bool ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto);
   bool spatialParamSignals = false;   // option "spatial_param_signals": SpatialPannerNode parameters accept signals (spatial_desc_kernel); 0 = refused
@@ -737,7 +929,7 @@ struct Context {
   SpatialBands spBands{};             // the band filters of that stage: fixed per context (made when the first job is planned)
   bool spBandsMade = false;
   bool delayFlagExact = false;   // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology)
-  std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (NodeS::delayProbe)
+  std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (DelayS::delayProbe)
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);
@@ -814,7 +1006,7 @@ struct Context {
   std::vector<TconvLaunch> tconvPlan(int nblocks, int P) const;   // FFT lengths of the segments that cover a chunk
   bool fft64 = false;            // option "fft64": double-precision 256-point transforms in the B-layout kernels (reference-like)
   bool useTimeFft = true;        // option "time_fft": formulation C for 64 < P <= 1024
-  void updateBiquadCoefficients(NodeS& n, float frequency, float q, float gain);
+  void updateBiquadCoefficients(BiquadS& n, float frequency, float q, float gain);
 
   void render(float* const* out, int channels, int64_t frames, int64_t start, bool deviceOut);
   void runChunk(int64_t nblocks, float* const* bus);
@@ -831,10 +1023,10 @@ struct Context {
   void planDelay(NodePlanCtx& k);
   void planStereoPanner(NodePlanCtx& k);
   void planSpatialPanner(NodePlanCtx& k);
-  void planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, NodeS& nd, const SpatialEq& prev, int open, bool prevValid);
-  void spatialEqTable(Exec& ex, NodeS& nd, int64_t n);
+  void planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, SpatialPannerS& nd, const SpatialEq& prev, int open, bool prevValid);
+  void spatialEqTable(Exec& ex, SpatialPannerS& nd, int64_t n);
   // SpatialPannerNode: geometry of one block (SpatialPannerNode.cs:133-204,263-284 in float32) -> HRIR indices, weights, g, beta
-  void spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& out) const;
+  void spatialGeometry(const SpatialPannerS& nd, const float* pv, int D, SpatialPannerS::SpatialPrev& out) const;
   float spatialParamAt(const NodeS& nd, int p, double t) const;   // the k-rate value of a block: sample 0 of the timeline (event values are clamped when they are scheduled)
   // the listener transform (SteamAudioContext.cs:45-54, options listener_*): origin, right, up, ahead
   float listener[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1};
@@ -865,11 +1057,11 @@ struct Context {
   size_t rateModDevBytes = 0;
   void* rateModHost = nullptr;
   size_t rateModHostBytes = 0;
-  void ensureBiquadState(NodeS& bn);
+  void ensureBiquadState(BiquadS& bn);
   // AudioStreamNodeBase.Process replayed on indices for `nblocks` blocks from the node's current state: fills the node's per-chunk
   // tables (commit = false) or moves the node's state to the end of the replayed blocks (commit = true)
-  void streamReplay(NodeS& s, int64_t nblocks, const std::vector<double>& bt, bool commit);
-  void streamFlushToProcessed(NodeS& s);
+  void streamReplay(StreamSourceS& s, int64_t nblocks, const std::vector<double>& bt, bool commit);
+  void streamFlushToProcessed(StreamSourceS& s);
   bool faulted = false;      // a render failed after control state had moved: the context refuses further renders
   std::string faultMsg;
   int chunkPhase = 0;        // 0 = checks only (a failure leaves the context usable), 1 = state is moving

@@ -61,8 +61,9 @@ void Context::planCoarseFusion(const std::vector<int>& topo, const std::vector<S
     uint64_t key = hmix(graphVersion, (uint64_t)segs.size());
     for (const Segment& sg : segs) key = hmix(key, sg.hash);
     for (int id : topo) {
-      const NodeS& nd = *nodes[id];
-      if (nd.type == GA_NODE_CONVOLVER) key = hmix(hmix(key, ((uint64_t)id << 8) | (uint64_t)nd.convPath), (uint64_t)(uintptr_t)nd.ir.get());
+      if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+      const ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+      key = hmix(hmix(key, ((uint64_t)id << 8) | (uint64_t)nd.convPath), (uint64_t)(uintptr_t)nd.ir.get());
     }
     if (fusionKeyValid && key == fusionKey) return;
     fusionKey = key;
@@ -70,8 +71,8 @@ void Context::planCoarseFusion(const std::vector<int>& topo, const std::vector<S
   }
   std::vector<int> cand;
   for (int id : topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_CONVOLVER) continue;
+    if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
     nd.dLeader = -1;
     if (!nd.ir || nd.convPath != 4) continue;
     nd.dLeader = id;
@@ -100,7 +101,7 @@ void Context::planCoarseFusion(const std::vector<int>& topo, const std::vector<S
     }
   std::map<std::tuple<int, int, int, int, int>, int> leaderOf;   // (consumer, input, depth, output channels, partitions) -> leader
   for (int id : cand) {   // topo order: the leader is the first member the traversal reaches
-    NodeS& nd = *nodes[id];
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
     if (seen[id] != (int)segs.size()) continue;
     const InRef& r = nd.outputs[0].connectedInputs[0];
     auto key = std::make_tuple(r.node, r.input, nd.depth, nd.effectiveOutCh, nd.ir->coarseP);
@@ -139,14 +140,14 @@ static const float* convChunkInput(Context& c, Exec& ex, const Exec::ConvInRow& 
 }
 
 // the hist_len samples in front of the chunk of input channel `ch`: a span of a PlayableAudioBuffer, the node's own copy, or nothing yet
-static const float* coarseHistory(const NodeS& nd, int ch) {
+static const float* coarseHistory(const ConvolverS& nd, int ch) {
   if (ch < (int)nd.dHistExt.size() && nd.dHistExt[ch].first) return nd.dHistExt[ch].first;
   return nd.dHistZero ? nullptr : nd.dHist[nd.dHistCur] + (size_t)ch * nd.dHistLen;
 }
 
 // If the last hist_len samples of this chunk's input are device memory that stays (a PlayableAudioBuffer played zero-copy), the
 // next chunk's history is that span and nothing has to be written; otherwise the span is forgotten and the caller copies.
-static bool coarseHistoryStays(Context& c, NodeS& nd, int ch, const float* in, int64_t frames) {
+static bool coarseHistoryStays(Context& c, ConvolverS& nd, int ch, const float* in, int64_t frames) {
   if ((int)nd.dHistExt.size() < nd.bInCh) nd.dHistExt.resize(nd.bInCh, {nullptr, -1});
   const int64_t hl = nd.dHistLen;
   int buf = -1;
@@ -226,7 +227,7 @@ struct CoarseStage {
   void resolveInputs();    // chunk-long input views of every node (materialised where the segments disagree)
   void classifyGroups();   // which groups are pre-mixed, carry a tail, can use the one the previous chunk left
   void buildRows();        // signals to transform (pre-mixed groups: one per channel), history hand-over, pieces (signal x columns)
-  void addPieces(NodeS& nd, int leader, int nxr, const int* xFrame, const int* xIndex);
+  void addPieces(ConvolverS& nd, int leader, int nxr, const int* xFrame, const int* xIndex);
   void buildJobs();        // multiply-accumulate jobs and their terms
   void buildOutputs();     // inverse-transform outputs, tail buffers
   void enqueue();          // tables into the plan, launches
@@ -236,7 +237,7 @@ void CoarseStage::resolveInputs() {
   chInOf.resize(dNodes.size());
   for (size_t di = 0; di < dNodes.size(); di++) {
     const int id = dNodes[di];
-    NodeS& nd = *c.nodes[id];
+    ConvolverS& nd = rec<ConvolverS>(*c.nodes[id]);
     const int64_t hl = nd.dHistLen;
     const Exec::ConvInRow ci = ex.convIn[id];
     Views& chIn = chInOf[di];
@@ -279,7 +280,7 @@ void CoarseStage::classifyGroups() {
   {
     auto mix = [](uint64_t& h, uint64_t v) { h = (h ^ v) * 1099511628211ull; };
     for (int id : dNodes) {
-      NodeS& nd = *c.nodes[id];
+      ConvolverS& nd = rec<ConvolverS>(*c.nodes[id]);
       GroupInfo& g = groups[nd.dLeader >= 0 ? nd.dLeader : id];
       mix(g.sig, (uint64_t)id);
       mix(g.sig, (uint64_t)(uintptr_t)nd.ir.get());
@@ -303,7 +304,7 @@ void CoarseStage::classifyGroups() {
       }
     }
     for (auto& kv : groups) {
-      NodeS& ld = *c.nodes[kv.first];
+      ConvolverS& ld = rec<ConvolverS>(*c.nodes[kv.first]);
       // a tail costs P' more inverse transforms per output channel and chunk and saves P' - 2 forward transforms per input row:
       // worth it for sums of many signals, not for a convolver on its own.  The P' more output blocks are nearly free in the
       // reduction kernel (one impulse response for the whole group); the general kernel skips the partition blocks whose windows
@@ -322,7 +323,7 @@ void CoarseStage::classifyGroups() {
 
 // columns of a node's input rows: discrete -> slot c reads input c, IR channel c, output c ; true stereo -> (L,h0,outL) (L,h1,outR)
 // (R,h2,outL) (R,h3,outR)  (ConvolverNode.cs:127-151).  Pieces of 4, 2, 1 columns per row.
-void CoarseStage::addPieces(NodeS& nd, int leader, int nxr, const int* xFrame, const int* xIndex) {
+void CoarseStage::addPieces(ConvolverS& nd, int leader, int nxr, const int* xFrame, const int* xIndex) {
   IrSpectra& ir = *nd.ir;
   for (int xc = 0; xc < nxr; xc++) {
     int cols[32][2], ncols = 0;
@@ -361,7 +362,7 @@ void CoarseStage::addPieces(NodeS& nd, int leader, int nxr, const int* xFrame, c
 void CoarseStage::buildRows() {
   for (size_t di = 0; di < dNodes.size(); di++) {
     const int id = dNodes[di];
-    NodeS& nd = *c.nodes[id];
+    ConvolverS& nd = rec<ConvolverS>(*c.nodes[id]);
     IrSpectra& ir = *nd.ir;
     const int P = ir.coarseP;
     if (P < 1 || P > kCoarseMaxParts) fail(GA_ERR_INVALID_OPERATION, "internal: coarse partition count out of range");
@@ -441,7 +442,7 @@ void CoarseStage::buildRows() {
   for (auto& kv : groups) {
     GroupInfo& g = kv.second;
     if (!g.premix) continue;
-    NodeS& ld = *c.nodes[kv.first];
+    ConvolverS& ld = rec<ConvolverS>(*c.nodes[kv.first]);
     const int64_t hl = g.hl0;
     int xFrame[32], xIndex[32];
     for (int ch = 0; ch < g.nxr; ch++) {
@@ -641,7 +642,7 @@ void CoarseStage::buildOutputs() {
     for (auto& kv : outRows) chOf[kv.first.first] = std::max(chOf[kv.first.first], kv.first.second + 1);
     for (auto& kv : groups) {
       if (!kv.second.tail) continue;
-      NodeS& ld = *c.nodes[kv.first];
+      ConvolverS& ld = rec<ConvolverS>(*c.nodes[kv.first]);
       const int64_t len = (int64_t)(kv.second.maxP + 1) * kCoarseBlock;
       const int nch = chOf.count(kv.first) ? chOf[kv.first] : 0;
       if (nch == 0) continue;
@@ -666,7 +667,7 @@ void CoarseStage::buildOutputs() {
     o.ny = (int)kv.second.size();
     o.n_y = nT;
     if (groups[kv.first.first].tail) {
-      NodeS& ld = *c.nodes[kv.first.first];
+      ConvolverS& ld = rec<ConvolverS>(*c.nodes[kv.first.first]);
       const GroupInfo& gi = groups[kv.first.first];
       o.n_y = nT + gi.maxP;
       o.tail_len = ld.dTailLen;
@@ -683,7 +684,7 @@ void CoarseStage::buildOutputs() {
   }
   if (tails)
     for (auto& kv : groups) {   // this chunk's tails are the next chunk's, if the group is still the same then
-      NodeS& ld = *c.nodes[kv.first];
+      ConvolverS& ld = rec<ConvolverS>(*c.nodes[kv.first]);
       if (!kv.second.tail || !ld.dTail[0]) continue;
       ld.dTailCur ^= 1;
       ld.dTailSig = kv.second.sig;
@@ -817,8 +818,9 @@ void Context::aliasBusToLeader(ChunkRun& r) {
     if (sg.nodes.empty() || sg.nodes.back().id != 0 || sg.nodes.back().ins.empty()) return;   // (node 0 is the destination)
     const InSeg& is = sg.nodes.back().ins[0];
     for (const TermS& t : is.terms) {
-      const NodeS& nd = *nodes[t.node];
-      if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.convPath != 4 || nd.dLeader < 0 || t.out != 0 || t.ch != is.bufCh) return;
+      if (nodes[t.node]->type != GA_NODE_CONVOLVER) return;
+      const ConvolverS& nd = rec<ConvolverS>(*nodes[t.node]);
+      if (!nd.ir || nd.convPath != 4 || nd.dLeader < 0 || t.out != 0 || t.ch != is.bufCh) return;
       if (leader < 0) {
         leader = nd.dLeader;
         nch = is.bufCh;
@@ -828,7 +830,7 @@ void Context::aliasBusToLeader(ChunkRun& r) {
     }
   }
   if (leader < 0 || nch < 1 || nch > (int)busSlabs.size()) return;
-  const NodeS& ld = *nodes[leader];
+  const ConvolverS& ld = rec<ConvolverS>(*nodes[leader]);
   if (ld.outputs.empty() || ld.outputs[0].connectedInputs.size() != 1) return;
   const InRef& to = ld.outputs[0].connectedInputs[0];
   if (to.node != 0 || to.input != 0) return;
@@ -849,15 +851,17 @@ void Context::chunkConvScratch(ChunkRun& r) {
     refOrderSensitivity(topo);
     assignConvPaths(topo, n);
     for (int id : topo) {
-      NodeS& nd = *nodes[id];
-      if (nd.type == GA_NODE_CONVOLVER) nd.refOrder = nd.refSens && nd.ir && (nd.convPath == 2 || nd.convPath == 3);
+      if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+      ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+      nd.refOrder = nd.refSens && nd.ir && (nd.convPath == 2 || nd.convPath == 3);
     }
     planCoarseFusion(topo, r.segs);
     for (int id : topo)
-      if (nodes[id]->type == GA_NODE_CONVOLVER) nodes[id]->dGroupSize = 0;
+      if (nodes[id]->type == GA_NODE_CONVOLVER) rec<ConvolverS>(*nodes[id]).dGroupSize = 0;
     for (int id : topo) {
-      const NodeS& nd = *nodes[id];
-      if (nd.type == GA_NODE_CONVOLVER && nd.ir && nd.convPath == 4 && nd.dLeader >= 0) nodes[nd.dLeader]->dGroupSize++;
+      if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+      const ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+      if (nd.ir && nd.convPath == 4 && nd.dLeader >= 0) rec<ConvolverS>(*nodes[nd.dLeader]).dGroupSize++;
     }
     aliasBusToLeader(r);
   }
@@ -866,8 +870,9 @@ void Context::chunkConvScratch(ChunkRun& r) {
     size_t xMax = 0, yMax = 0;
     size_t bx = 0, by = 0;
     for (int id : topo) {
-      NodeS& nd = *nodes[id];
-      if (nd.type != GA_NODE_CONVOLVER || !nd.ir) continue;
+      if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+      ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+      if (!nd.ir) continue;
       if (nd.convPath == 2 || nd.convPath == 3) {
         bx += nd.bInCh;
         by += nd.bSlots;
@@ -892,8 +897,9 @@ void Context::chunkConvScratch(ChunkRun& r) {
       std::map<int, int> tailDepth;                        // depth -> longest carried tail a group of the stage can have (coarse blocks)
       const int64_t nT = (n * kBlock + kCoarseBlock - 1) / kCoarseBlock;
       for (int id : topo) {
-        NodeS& nd = *nodes[id];
-        if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.convPath != 4) continue;
+        if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+        ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+        if (!nd.ir || nd.convPath != 4) continue;
         auto& pd = perDepth[nd.depth];
         pd.first += (size_t)nd.bInCh * (size_t)(nT + nd.ir->coarseP);   // (+ the window behind the chunk's last block: carried tails)
         // Y rows: one per slot unless fused; fused groups need (members / 32 + 1) x channels rows, never more than the slots
@@ -915,13 +921,14 @@ void Context::chunkConvScratch(ChunkRun& r) {
       if (coarsePremix) {   // pre-mixed groups: [history | chunk] of the mixed signal per input channel of the group
         std::map<int, int> members;
         for (int id : topo) {
-          NodeS& nd = *nodes[id];
-          if (nd.type == GA_NODE_CONVOLVER && nd.ir && nd.convPath == 4) members[nd.dLeader >= 0 ? nd.dLeader : id]++;
+          if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+          const ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+          if (nd.ir && nd.convPath == 4) members[nd.dLeader >= 0 ? nd.dLeader : id]++;
         }
         std::map<int, size_t> pmDepth;
         for (auto& kv : members) {
           if (kv.second < 2) continue;
-          const NodeS& ld = *nodes[kv.first];
+          const ConvolverS& ld = rec<ConvolverS>(*nodes[kv.first]);
           pmDepth[ld.depth] += (size_t)ld.bInCh * ((((size_t)(ld.dHistLen + n * kBlock) * sizeof(float)) + 255) & ~(size_t)255);
         }
         size_t pm = 0;
@@ -949,8 +956,9 @@ void Context::chunkConvScratch(ChunkRun& r) {
 
   if (topoHasOscillators)
   for (int id : topo) {  // OscillatorNode._phase lives on the device (one double, zero at Start)
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_OSCILLATOR || nd.oscPhase) continue;
+    if (nodes[id]->type != GA_NODE_OSCILLATOR) continue;
+    OscillatorS& nd = rec<OscillatorS>(*nodes[id]);
+    if (nd.oscPhase) continue;
     nd.oscPhase = (double*)dalloc(64);
     GA_HIP(hipMemsetAsync(nd.oscPhase, 0, 64, stream));
   }
@@ -969,7 +977,7 @@ void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
     const int nrows = (int)g.rows.size();
     std::vector<ConvRowIO> rio(nrows, ConvRowIO{nullptr, nullptr});
     for (auto& ns_ : kv.second) {
-      NodeS& nd = *nodes[ns_.first];
+      ConvolverS& nd = rec<ConvolverS>(*nodes[ns_.first]);
       const int slot = ns_.second;
       const int idx = nd.convRows[slot].idx;
       // which input channel feeds this row: discrete -> slot ; true stereo -> L,L,R,R for h0,h1,h2,h3 (ConvolverNode.cs:127-151)
@@ -1093,7 +1101,7 @@ void Context::planConvolversPrivate(ChunkRun& r, int /*d*/, ConvPlanCtx& k, bool
   std::vector<float*> slotOut;
   std::vector<int> cols;
   for (int id : bNodes) {
-    NodeS& nd = *nodes[id];
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
     const int P = nd.ir->P, h = P - 1;
     const Exec::ConvInRow ci = ex.convIn[id];
     // chunk-long input pointer of every input channel (stable view, or a materialised copy)
@@ -1311,7 +1319,7 @@ void Context::planConvolversPrivate(ChunkRun& r, int /*d*/, ConvPlanCtx& k, bool
     std::map<std::pair<IrSpectra*, int>, int> distinct;
     double bytes = 0;
     for (int id : bNodes) {
-      NodeS& nd = *nodes[id];
+      ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
       const int P = nd.ir->P;
       bytes += ((double)P * kBins * 8.0 + kBins * 8.0 + 512.0) * nd.bSlots * (double)n;
       for (int sl = 0; sl < nd.bSlots; sl++) distinct[{nd.ir.get(), sl}] = P;
@@ -1332,8 +1340,9 @@ void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
   std::vector<int>& bNodes = k.bNodes;  // formulation B / C nodes of this depth
   std::vector<int>& dNodes = k.dNodes;  // formulation D nodes of this depth
   for (int id : r.topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_CONVOLVER || !nd.ir || nd.depth != d) continue;
+    if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+    if (!nd.ir || nd.depth != d) continue;
     if (!ex.convIn.has(id)) continue;
     if (nd.convPath == 4) {
       dNodes.push_back(id);
@@ -1353,7 +1362,7 @@ void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
   // transforms and launch_refmac instead of the matrix-core / block-axis-FFT partition sums)
   if (!bNodes.empty()) {
     std::vector<int> plain, ref;
-    for (int id : bNodes) (nodes[id]->refOrder ? ref : plain).push_back(id);
+    for (int id : bNodes) (rec<ConvolverS>(*nodes[id]).refOrder ? ref : plain).push_back(id);
     if (!plain.empty()) {
       bNodes = plain;
       planConvolversPrivate(r, d, k, false);

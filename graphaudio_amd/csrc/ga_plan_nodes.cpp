@@ -74,7 +74,7 @@ void Context::chunkParamCurves(ChunkRun& r) {
   }
 }
 
-void Context::ensureBiquadState(NodeS& bn) {
+void Context::ensureBiquadState(BiquadS& bn) {
     if (bn.bqDyn) return;
     const size_t per = (sizeof(BiquadDynState) + 31) & ~(size_t)31;
     const size_t blk = (size_t)1 << 20;
@@ -101,15 +101,16 @@ void Context::planConstantSource(NodePlanCtx& k) {
   cj.pad_ = 0;
   cj.f0 = f0;
   cj.n = nf;
-  cj.lo = nd.schedLo;
-  cj.hi = nd.schedHi;
+  const SchedState& sched = rec<ConstantSourceS>(nd);
+  cj.lo = sched.schedLo;
+  cj.hi = sched.schedHi;
   ex.constJobs.push_back(cj);
   ov[0] = cj.out;
 }
 
 // OscillatorNode.Process (OscillatorNode.cs:91-196)
 void Context::planOscillator(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; OscillatorS& nd = rec<OscillatorS>(k.nd); Views& ov = k.ov;
   const int64_t f0 = k.f0, nf = k.nf;
   if (ns.srcPhase != SRC_PLAY) return;
   OscJob oj;
@@ -130,7 +131,7 @@ void Context::planOscillator(NodePlanCtx& k) {
 
 // DelayNode.Process (DelayNode.cs:43-100): the segment's input appended to the rings, then a gather
 void Context::planDelay(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; DelayS& nd = rec<DelayS>(k.nd); Views& ov = k.ov;
   const int64_t f0 = k.f0, nf = k.nf;
   const int ch = ns.ins[0].bufCh;
   const int maxD = nd.maxDelaySamples;
@@ -153,7 +154,7 @@ void Context::planDelay(NodePlanCtx& k) {
   // a second job that copies a mixed slab into the ring would sit in the same launch as the mix that produces the slab -- no
   // order between them (until round 3 a DelayNode with two connections, or behind a folded GainNode, read a half-written slab).
   SmallVec<float*, 4> ring((size_t)std::max(ch, 1), nullptr);
-  // A DelayNode at which a feedback loop is cut (NodeS::delaySplit, Context::chunkTopology) is planned twice per segment: the READER
+  // A DelayNode at which a feedback loop is cut (DelayS::delaySplit, Context::chunkTopology) is planned twice per segment: the READER
   // in front of everything (its gather only touches what the ring held before the chunk), the WRITER at the node's level -- possibly
   // a convolver depth later, i.e. after the readers of ALL segments: the reader counts the ring positions on its own (delayR).
   const bool reader = k.delayPhase != 2, writer = k.delayPhase != 1;
@@ -200,7 +201,7 @@ void Context::planDelay(NodePlanCtx& k) {
 
 // StereoPannerNode.Process (StereoPannerNode.cs:36-153)
 void Context::planStereoPanner(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const size_t si = k.si; const NodeSeg& ns = k.ns; StereoPannerS& nd = rec<StereoPannerS>(k.nd); Views& ov = k.ov;
   const int64_t f0 = k.f0, nf = k.nf;
   if (ns.ins[0].silent) return;   // cleared 2-channel output (:49-54)
   auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
@@ -254,7 +255,7 @@ float Context::spatialParamAt(const NodeS& nd, int p, double t) const {   // Get
 // parameters.
 static_assert(GA_DISTANCE_LINEAR == kSpatialLinear && GA_DISTANCE_INVERSE == kSpatialInverse && GA_DISTANCE_EXPONENTIAL == kSpatialExponential &&
               GA_SPATIAL_PARAM_COUNT == kSpatialParams, "ga_spatial_geom.hpp restates the interface's constants");
-void Context::spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::SpatialPrev& o) const {
+void Context::spatialGeometry(const SpatialPannerS& nd, const float* pv, int D, SpatialPannerS::SpatialPrev& o) const {
   SpatialGeom gm;
   spatial_geometry<SpatialMathLibm>(pv, listener, nd.distanceModel, nd.hrirAzimuths, D, gm);
   for (int q = 0; q < 4; q++) {
@@ -269,7 +270,7 @@ void Context::spatialGeometry(const NodeS& nd, const float* pv, int D, NodeS::Sp
 // Occlusion and transmission (option "spatial_occlusion"): one job of spatial_direct_kernel for the node over this segment.  x' goes to
 // two chunk planes of the node's own, and the panner's input views of the segment (sgs[si]) are redirected to them.  `prev`, `open`
 // and `prevValid` are the carried state at the segment's first block.
-void Context::planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, NodeS& nd, const SpatialEq& prev, int open, bool prevValid) {
+void Context::planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, SpatialPannerS& nd, const SpatialEq& prev, int open, bool prevValid) {
   if (!spBandsMade) {
     spBands = spatial_bands(sampleRate);
     spBandsMade = true;
@@ -297,7 +298,7 @@ void Context::planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const No
   ex.spatialDirectJobs.push_back(j);
 }
 // the node's per-block triples of this chunk: every entry the identity until a segment fills its blocks in
-void Context::spatialEqTable(Exec& ex, NodeS& nd, int64_t n) {
+void Context::spatialEqTable(Exec& ex, SpatialPannerS& nd, int64_t n) {
   if (nd.spEqSeq == chunkSeq && nd.spExec == &ex) return;
   std::vector<SpatialEqEntry> eqs((size_t)n + 1, SpatialEqEntry{SpatialEq{1.0f, 0.0f, 0.0f}, 0});
   nd.spEqOff = ex.plan.putv(eqs);
@@ -307,7 +308,7 @@ void Context::spatialEqTable(Exec& ex, NodeS& nd, int64_t n) {
 // One descriptor per block, made here (not in the simulation, so that a moving source does not cut the chunk into one-block
 // segments for every other node), the segment's workgroups, and -- in the chunk's last segment -- the history of the next chunk.
 void Context::planSpatialPanner(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; SpatialPannerS& nd = rec<SpatialPannerS>(k.nd); Views& ov = k.ov;
   const int64_t n = k.r.n;
   PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
   if (!hb || hb->length < 1 || hb->length > kSpatialMaxTaps || (hb->channels & 1)) fail(GA_ERR_DEVICE, "internal: spatial panner without a valid HRIR set");
@@ -436,7 +437,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
     }
     bool moving = false;
     for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) moving = moving || !nd.params[p].events.empty();
-    NodeS::SpatialPrev cur;
+    SpatialPannerS::SpatialPrev cur;
     const int T = (int)hb->length;
     // option "spatial_occlusion": the block's EQ triple beside its descriptor; the segment gets a job of spatial_direct_kernel when one
     // of its blocks is active (its own triple or the previous processed block's is not the identity)
@@ -465,7 +466,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
         nd.spEqOpen = active ? (stereo ? 3 : 1) : 0;
         eqv.push_back(eqCur);
       }
-      const NodeS::SpatialPrev& pr = nd.spPrev;
+      const SpatialPannerS::SpatialPrev& pr = nd.spPrev;
       bool fade = false;
       if (pr.valid) {
         fade = !(pr.g == cur.g) || !(pr.beta == cur.beta);
@@ -536,7 +537,7 @@ bool Context::ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto) {
 
 // AudioBufferSourceNode.Process (AudioBufferSourceNode.cs:150-260): zero-copy windows, loop walks, resampler jobs, general replay
 void Context::planBufferSource(NodePlanCtx& k) {
-  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; BufferSourceS& nd = rec<BufferSourceS>(k.nd); Views& ov = k.ov;
   const int64_t f0 = k.f0, nf = k.nf, nb = k.nb;
   const std::vector<int>& srcIds = k.r.srcIds; const std::vector<SrcPlanOut>& srcPlans = k.r.srcPlans;
   if (ns.srcPhase != SRC_PLAY) return;  // silent: ZERO views
@@ -642,7 +643,7 @@ void Context::planBufferSource(NodePlanCtx& k) {
 
 // AudioStreamSourceNodeBase.Process (AudioStreamSourceNodeBase.cs:132-301), replayed by the host (streamReplay)
 void Context::planStreamSource(NodePlanCtx& k) {
-  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; StreamSourceS& nd = rec<StreamSourceS>(k.nd); Views& ov = k.ov;
   const int64_t nb = k.nb;
   if (ns.outSilent) return;   // ProduceSilence / nothing rendered: cleared buffer
   if (!nd.stUploaded) {
@@ -727,7 +728,7 @@ void Context::planGain(NodePlanCtx& k) {
 
 // BiQuadFilterNode.Process (BiQuadFilterNode.cs:96-143): automated parameters, fused constant-coefficient cascades, cascades split along time
 void Context::planBiquad(NodePlanCtx& k) {
-  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; NodeS& nd = k.nd; Views& ov = k.ov;
+  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; BiquadS& nd = rec<BiquadS>(k.nd); Views& ov = k.ov;
   const int64_t f0 = k.f0, nf = k.nf, nb = k.nb;
   const DenseSeg& segNode = k.segNode; const DenseInt& absorbedBy = k.absorbedBy; const int levelBqHeads = k.levelBqHeads;
   if (!ns.bqActive) {  // silent input: cleared output, state frozen (BiQuadFilterNode.cs:103-108)
@@ -786,7 +787,7 @@ void Context::planBiquad(NodePlanCtx& k) {
   }
   auto iv = ex.resolveInput((int)si, *chain.front(), 0, false, nullptr);
   for (const NodeSeg* cn : chain) {
-    NodeS& cnd = *nodes[cn->id];
+    BiquadS& cnd = rec<BiquadS>(*nodes[cn->id]);
     ensureBiquadState(cnd);
   }
   // pieces along time (ga_kernels.hpp, BiquadScanJob): as many as keep every lane of the chip busy, each >= 1024 frames;
@@ -812,17 +813,17 @@ void Context::planBiquad(NodePlanCtx& k) {
   if (G > 1 && (G != ex.bqG || K != ex.bqK)) G = 1;   // (one cut per level: the pieces of a level are expanded by one launch)
   const std::vector<float>* AK = G > 1 ? &biquadTransition(coefs, (int)chain.size(), K).M : nullptr;
   // Twin channels: a mono signal in a stereo node arrives as the SAME view on every channel (AudioNodeInput.cs:182-244 copies the
-  // mono mix to all of them), and while every channel's state has been the same so far (NodeS::bqTwinN) the reference computes
+  // mono mix to all of them), and while every channel's state has been the same so far (BiquadS::bqTwinN) the reference computes
   // the same numbers once per channel (BiQuadFilterNode.cs:117-146).  One job then stands for all of them: every channel's output
   // view is the one row, the end state goes to every channel's slot.
   int twins = 1;
   if (twinChannels && ns.outCh > 1) {
     bool same = true;
     for (int ch = 1; ch < ns.outCh; ch++) same = same && iv[ch] == iv[0];
-    for (const NodeSeg* cn : chain) same = same && nodes[cn->id]->bqTwinN >= ns.outCh;
+    for (const NodeSeg* cn : chain) same = same && rec<BiquadS>(*nodes[cn->id]).bqTwinN >= ns.outCh;
     if (same) twins = ns.outCh;
   }
-  for (const NodeSeg* cn : chain) nodes[cn->id]->bqTwinN = twins;   // (channels beyond outCh are not advanced: no longer the same)
+  for (const NodeSeg* cn : chain) rec<BiquadS>(*nodes[cn->id]).bqTwinN = twins;   // (channels beyond outCh are not advanced: no longer the same)
   if (twins > 1) stats.twin_rows += twins - 1;
   for (int ch = 0; ch < ns.outCh; ch++) {
     if (twins > 1 && ch > 0) {
@@ -842,7 +843,7 @@ void Context::planBiquad(NodePlanCtx& k) {
       BiquadSection sc;
       sc.b0 = cn->b0; sc.b1 = cn->b1; sc.b2 = cn->b2; sc.a1 = cn->a1; sc.a2 = cn->a2;
       sc.pad_ = 0.f;
-      sc.state = nodes[cn->id]->bqState + 2 * ch;
+      sc.state = rec<BiquadS>(*nodes[cn->id]).bqState + 2 * ch;
       ex.bqSecs.push_back(sc);
     }
     ov[ch] = bj.out;
@@ -927,7 +928,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
     if (d == 0 && topoHasCycles && cycleBlocks > 1) {   // the readers of the DelayNodes at which this chunk's loops are cut: sources
       for (const NodeSeg& ns : sg.nodes) {
         NodeS& nd = *nodes[ns.id];
-        if (nd.type != GA_NODE_DELAY || !nd.delaySplit) continue;
+        if (nd.type != GA_NODE_DELAY || !rec<DelayS>(nd).delaySplit) continue;
         auto& ov = ex.outViews[si][ns.id];
         ov.assign(std::max(ns.outCh, 1), nullptr);
         NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, 0};
@@ -939,10 +940,8 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
     for (size_t ti = 0; ti < todo.size(); ti++) {
       const NodeSeg* nsp = todo[ti];
       if (ti + 4 < todo.size()) {   // (the sweep is bound by cache misses on the node records)
-        const char* nx = (const char*)nodes[todo[ti + 4]->id].get();
-        __builtin_prefetch(nx);
-        __builtin_prefetch(nx + 64);
-        __builtin_prefetch(nx + 128);
+        const char* nx = (const char*)nodes[todo[ti + 4]->id].get();   // the common part and about a line of the typed part behind it (records are not line aligned)
+        for (size_t o = 0; o < sizeof(NodeS) + 64; o += 64) __builtin_prefetch(nx + o);
       }
       const NodeSeg& ns = *nsp;
       NodeS& nd = *nodes[ns.id];
@@ -956,7 +955,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
         }
       }
       auto& ov = ex.outViews[si][ns.id];
-      const bool cutDelay = nd.type == GA_NODE_DELAY && nd.delaySplit && topoHasCycles && cycleBlocks > 1;   // (its reader set the views)
+      const bool cutDelay = nd.type == GA_NODE_DELAY && rec<DelayS>(nd).delaySplit && topoHasCycles && cycleBlocks > 1;   // (its reader set the views)
       if (!cutDelay) ov.assign(nd.type == GA_NODE_CHANNEL_SPLITTER ? (int)nd.outputs.size() : std::max(ns.outCh, 1), nullptr);
       NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, levelBqHeads};
       if (cutDelay) k.delayPhase = 2;
@@ -987,11 +986,12 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
         case GA_NODE_BIQUAD: planBiquad(k); break;
         case GA_NODE_CONVOLVER: {
           auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
-          if (!nd.ir) break;  // no IR: cleared output (ConvolverNode.cs:107-119)
+          const ConvolverS& cv = rec<ConvolverS>(nd);
+          if (!cv.ir) break;  // no IR: cleared output (ConvolverNode.cs:107-119)
           ex.convIn[ns.id][si] = iv;
           // formulation D: the outputs of a fused group are summed as spectra; the sum is the LEADER's output, the other
           // members hand their consumer a null (= contributes nothing) view (Context::planCoarseFusion)
-          if (nd.convPath == 4 && nd.dLeader >= 0 && nd.dLeader != ns.id) break;
+          if (cv.convPath == 4 && cv.dLeader >= 0 && cv.dLeader != ns.id) break;
           // Nothing has reached this convolver since its delay line was created: the reference's partition sum is a sum of
           // exact zeros (PartitionedConvolver.cs:154-223), and consumers that compare values -- StereoPannerNode's `pan !=
           // _lastPan` (StereoPannerNode.cs:92-99), DelayNode's (int)(delayTime * sampleRate) -- see that.  The transform
@@ -1003,7 +1003,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
 #else
           constexpr bool noZeroPage = false;
 #endif
-          if (!noZeroPage && ns.outZero && !(nd.convPath == 4 && nd.dGroupSize > 1)) {
+          if (!noZeroPage && ns.outZero && !(cv.convPath == 4 && cv.dGroupSize > 1)) {
             for (int ch = 0; ch < ns.outCh; ch++) ov[ch] = zeros;
             break;
           }
@@ -1138,8 +1138,9 @@ void Context::chunkDelayCommit(ChunkRun& r) {
   Exec& ex = *r.ex;
   // DelayNode: the last maxDelay samples every ring has seen become the history of the next chunk
   for (int id : r.topo) {
-    NodeS& nd = *nodes[id];
-    if (nd.type != GA_NODE_DELAY || !nd.delayLoaded) continue;
+    if (nodes[id]->type != GA_NODE_DELAY) continue;
+    DelayS& nd = rec<DelayS>(*nodes[id]);
+    if (!nd.delayLoaded) continue;
     const size_t maxD = (size_t)nd.maxDelaySamples, pitch = maxD + (size_t)nd.delayCap;
     for (int r = 0; r < nd.delayHistRings; r++) {
       if (nd.delayW[r] == 0) continue;

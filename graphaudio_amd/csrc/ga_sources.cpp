@@ -5,7 +5,7 @@
 
 namespace ga {
 
-SrcGeom sourceGeom(Context& c, NodeS& s, PlayBuf& b) {
+SrcGeom sourceGeom(Context& c, BufferSourceS& s, PlayBuf& b) {
   SrcGeom g;
   float playbackRate = s.params[0].value;  // k-rate; a timeline on it is handled by the general replay (gsrReplayBlock)
   double sampleRateRatio = b.sampleRate / (double)c.sampleRate;
@@ -60,7 +60,7 @@ static void resampleBlockBounded(const ResampleBlock& st, double rate, int64_t a
 }
 
 // ---- general source replay (ga_gsr.hpp): what a replay needs of the source ----
-static GsrGeom gsrGeom(Context& c, const SrcGeom& g, const NodeS& s, const PlayBuf& b) {
+static GsrGeom gsrGeom(Context& c, const SrcGeom& g, const BufferSourceS& s, const PlayBuf& b) {
   GsrGeom q;
   q.loopStart = g.loopStartFrame;
   q.loopEnd = g.loopEndFrame;
@@ -72,7 +72,7 @@ static GsrGeom gsrGeom(Context& c, const SrcGeom& g, const NodeS& s, const PlayB
   return q;
 }
 
-static GsrState gsrStateOf(const NodeS& s) {
+static GsrState gsrStateOf(const BufferSourceS& s) {
   GsrState st;
   for (int k = 0; k < 4; k++) st.w[k] = s.gsrW[k];
   st.pos = s.gsrPos;
@@ -89,7 +89,7 @@ struct SrcStart {
   int64_t bs = 0, kTime = 0;
 };
 static const int64_t kSrcInf = std::numeric_limits<int64_t>::max() / 4;
-static SrcStart srcStart(Context& c, const NodeS& s, int64_t n, const std::vector<double>& bt) {
+static SrcStart srcStart(Context& c, const BufferSourceS& s, int64_t n, const std::vector<double>& bt) {
   SrcStart r;
   r.kTime = kSrcInf;
   const PlayBuf* b = s.bufId >= 0 ? c.buffers[s.bufId].get() : nullptr;
@@ -103,7 +103,7 @@ static SrcStart srcStart(Context& c, const NodeS& s, int64_t n, const std::vecto
 }
 
 // general replay mode is entered for good: the state after rsBlocks blocks of a resampler trajectory becomes explicit
-static void gsrEnter(Context& c, NodeS& s, PlayBuf& b, const SrcGeom& g) {
+static void gsrEnter(Context& c, BufferSourceS& s, PlayBuf& b, const SrcGeom& g) {
   if (s.gsr) return;
   if (s.rsBlocks > 0) {
     Resampler& rs = resamplerFor(c, s.rsRate);
@@ -137,14 +137,14 @@ static void gsrEnter(Context& c, NodeS& s, PlayBuf& b, const SrcGeom& g) {
   s.gsr = true;
 }
 
-static void checkResamplerBuffer(NodeS& s) {
+static void checkResamplerBuffer(BufferSourceS& s) {
   const bool resamplerLive = s.gsr ? s.gsrReady > 0 : s.rsBlocks > 0;
   if (resamplerLive && s.rsBufId != s.bufId)
     fail(GA_ERR_UNSUPPORTED, "the Buffer of a source was replaced while its resampler holds samples of the old one");
   if (!resamplerLive) s.rsBufId = s.bufId;
 }
 
-bool rateModWalkJob(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j) {
+bool rateModWalkJob(Context& c, BufferSourceS& s, int64_t n, const std::vector<double>& bt, GsrWalkJob& j) {
   const SrcStart ss = srcStart(c, s, n, bt);
   if (!ss.plays) return false;
   PlayBuf& b = *c.buffers[s.bufId];
@@ -162,7 +162,7 @@ bool rateModWalkJob(Context& c, NodeS& s, int64_t n, const std::vector<double>& 
   return true;
 }
 
-SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm) {
+SrcPlanOut planSource(Context& c, BufferSourceS& s, int64_t n, const std::vector<double>& bt, const RateModIn* rm) {
   SrcPlanOut po;
   s.spans.clear();
   s.gsrDesc = nullptr;
@@ -327,7 +327,8 @@ SrcPlanOut planSource(Context& c, NodeS& s, int64_t n, const std::vector<double>
 
 // ConstantSourceNode / OscillatorNode scheduling (ConstantSourceNode.cs:83-110,143-152; OscillatorNode.cs:97-118,160-169):
 // sample-accurate start and stop inside a block, Ended + queued Dispose after the first block whose end reaches stopTime
-SrcPlanOut planScheduled(Context& c, NodeS& s, int64_t n, const std::vector<double>& bt) {
+SrcPlanOut planScheduled(Context& c, NodeS& nd, int64_t n, const std::vector<double>& bt) {
+  SchedState& s = schedOf(nd);
   SrcPlanOut po;
   s.spans.clear();
   s.schedLo = s.schedHi = 0;
@@ -337,7 +338,7 @@ SrcPlanOut planScheduled(Context& c, NodeS& s, int64_t n, const std::vector<doub
   if (s.hasStarted && s.hasStopped && !s.endedRaised && !std::isnan(s.stopTime))
     kEnd = std::lower_bound(bt.begin() + 1, bt.begin() + 1 + n, s.stopTime) - (bt.begin() + 1);   // may be n: not in this chunk
   s.spans.push_back(SrcSpan{0, SRC_IDLE, 0, 0});
-  if (s.hasStarted && !s.disposed) {
+  if (s.hasStarted && !nd.disposed) {
     // first block with t1 > startTime, last block with t0 < stopTime
     int64_t bs = std::upper_bound(bt.begin() + 1, bt.begin() + 1 + n, s.startTime) - (bt.begin() + 1);
     int64_t be = n - 1;
@@ -370,7 +371,7 @@ SrcPlanOut planScheduled(Context& c, NodeS& s, int64_t n, const std::vector<doub
 // ======================================================================================================
 // AudioStreamNodeBase.Process on indices (GraphAudio.IO/AudioStreamSourceNodeBase.cs:132-301)
 // ======================================================================================================
-void Context::streamReplay(NodeS& s, int64_t nblocks, const std::vector<double>& bt, bool commit) {
+void Context::streamReplay(StreamSourceS& s, int64_t nblocks, const std::vector<double>& bt, bool commit) {
   // working copy of the node's state
   std::deque<int> queued = s.stQueued, processed = s.stProcessed;
   int cur = s.stCurrent;
@@ -391,7 +392,7 @@ void Context::streamReplay(NodeS& s, int64_t nblocks, const std::vector<double>&
   };
   bool fed = false;
   if (!commit) {
-    s.stInfo.assign(nblocks, NodeS::StreamBlockInfo{1, true});
+    s.stInfo.assign(nblocks, StreamSourceS::StreamBlockInfo{1, true});
     s.stBlocks.assign(nblocks, StreamBlock{0, 0});
     s.stPieces.clear();
     s.stSegs.clear();
@@ -507,7 +508,7 @@ void Context::streamReplay(NodeS& s, int64_t nblocks, const std::vector<double>&
       }
     }
     if (!commit) {
-      s.stInfo[blk] = NodeS::StreamBlockInfo{channelCount, rendered == 0};
+      s.stInfo[blk] = StreamSourceS::StreamBlockInfo{channelCount, rendered == 0};
       s.stBlocks[blk] = StreamBlock{piece0, (int)s.stPieces.size() - piece0};
     }
   }

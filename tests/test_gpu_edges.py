@@ -85,6 +85,20 @@ def test_errors_after_dispose_and_bad_arguments():
         ctx.Render(out, 256)
 
 
+def test_destination_cannot_be_created_by_a_caller():
+    """The destination is the context's own node 0 (graphaudio_hip.h): node_create refuses its type like any unknown one, and no node
+    is added."""
+    import ctypes as C
+
+    def run(ctx):
+        out = C.c_int(-1)
+        for fn, args in (("node_create", ()), ("node_create_ex", (2.0,))):
+            with pytest.raises(ArgumentException, match="unknown node type"):
+                ctx._call(fn, 0, *args, C.byref(out))
+        return out.value, GainNode(ctx).NodeId
+    assert both(run) == [(-1, 1), (-1, 1)]          # nothing was created: the next node is still the first after the destination
+
+
 def test_many_control_segments_in_one_render():
     """150 voices that start and end at different blocks: far more than 96 control segments, so the engine closes chunks early
     (kMaxSegs) and continues -- the result must not depend on where the chunks end."""
