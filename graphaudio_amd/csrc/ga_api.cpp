@@ -370,7 +370,10 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "rate_mod_walk") c.rateModWalk = value != 0;
     else if (k == "spatial_param_signals") c.spatialParamSignals = value != 0;
     else if (k == "spatial_occlusion") c.spatialOcclusion = value != 0;
-    else if (k == "delay_flag_exact") c.delayFlagExact = value != 0;
+    else if (k == "delay_flag_exact") {
+      if (value != 0 && value != 1 && value != 2) fail(GA_ERR_OUT_OF_RANGE, "delay_flag_exact is 0, 1 or 2");
+      c.delayFlagExact = (int)value;
+    }
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);
     else if (k == "coarse_premix") c.coarsePremix = value != 0;

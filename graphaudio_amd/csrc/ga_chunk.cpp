@@ -87,6 +87,48 @@ void Context::chunkTopology(ChunkRun& r) {
   for (int id : probeDelays)   // (the previous chunk's choice, if a failure kept it from being cleared: runTwoStageChunk)
     if (id < (int)nodes.size() && nodes[id]) rec<DelayS>(*nodes[id]).delayProbe = false;
   probeDelays.clear();
+#ifdef GA_EXPERIMENTS
+  // (which condition keeps a delay on the prediction: one line per delay and chunk on stderr)
+  auto kept = [&](int id, const char* why, int at) {
+    if (expenv("GA_DEBUG_DELAY_FLAG")) fprintf(stderr, "[delay flag] chunk %lld delay %d keeps the prediction: %s (node %d)\n", (long long)stats.chunks, id, why, at);
+  };
+#else
+  auto kept = [](int, const char*, int) {};
+#endif
+  // the sources whose playbackRate a signal modulates and the cone of their modulation inputs (cached per graph version)
+  auto updateRateCone = [&](const std::vector<int>& topo) {
+    if (rateModsVersion == graphVersion && rateCone.size() == nodes.size()) return;
+    topoRateMods.clear();
+    for (int id : topo) {
+      const NodeS& nd = *nodes[id];
+      if ((nd.type == GA_NODE_BUFFER_SOURCE || nd.type == GA_NODE_STREAM_SOURCE) && !nd.params.empty() && !nd.params[0].modulation.empty())
+        topoRateMods.push_back({id, 0});
+    }
+    // the cone: every node the modulation inputs reach backwards (params before inputs, as Nodes/AudioNode.cs:167-175 pulls them)
+    rateCone.assign(nodes.size(), 0);
+    std::vector<int> stack;
+    for (const auto& pm : topoRateMods)
+      for (const auto& m : nodes[pm.first]->params[pm.second].modulation)
+        if (!rateCone[m.first]) {
+          rateCone[m.first] = 1;
+          stack.push_back(m.first);
+        }
+    while (!stack.empty()) {
+      const NodeS& nd = *nodes[stack.back()];
+      stack.pop_back();
+      auto visit = [&](int up) {
+        if (!rateCone[up]) {
+          rateCone[up] = 1;
+          stack.push_back(up);
+        }
+      };
+      for (const auto& p : nd.params)
+        for (const auto& m : p.modulation) visit(m.first);
+      for (const auto& in : nd.inputs)
+        for (const Conn& cn : in.connected) visit(cn.node);
+    }
+    rateModsVersion = graphVersion;
+  };
   // ---- reachability, level, convolver depth on the graph as it stands after the queued commands ----
   // (cached while no connection, disposal or impulse response changed since the last chunk)
   // (a graph with feedback is walked again every chunk: whether its loops can be cut at their DelayNodes depends on the delay
@@ -109,6 +151,9 @@ void Context::chunkTopology(ChunkRun& r) {
   }
   cycleBlocks = 1;
   loopGainBound = 0.0;
+  topoStaleEdges.clear();
+  loopProbeDelays.clear();
+  loopProbeCone.clear();
   std::vector<int> color(nodes.size(), 0);
   std::vector<char> candidate;   // DelayNodes on a loop whose delay is a constant of at least two blocks
   bool unbreakable = false;
@@ -131,6 +176,7 @@ void Context::chunkTopology(ChunkRun& r) {
     std::function<bool(int)> dfs = [&](int id) {   // false: `id` is being processed (the edge that led here is a feedback edge)
       if (color[id] == 2) return true;
       if (color[id] == 1) {
+        if (delayFlagExact >= 2 && !stack.empty()) topoStaleEdges.push_back(((uint64_t)stack.back() << 32) | (uint64_t)id);
         if (!nodes[id]->staleProducer) staleProducers.push_back(id);
         nodes[id]->staleProducer = true;
         // the loop this edge closes: the nodes on the stack from `id` up.  It can be cut where a DelayNode delays by >= 2 blocks.
@@ -207,7 +253,82 @@ void Context::chunkTopology(ChunkRun& r) {
     // without inputs), and its input appended afterwards (the WRITER).  With every loop cut that way the chunk's graph is acyclic; the
     // reference's stale edge becomes an ordinary edge that reads its producer ONE BLOCK LATE (Exec::resolveInSeg).  Chunks of K blocks
     // instead of one: a 0.25 s echo renders 93 blocks per chunk.
-    if (!staleProducers.empty() && !unbreakable && cycleDelaySplit) {
+    // ---- DelayNodes on a loop whose output flag this chunk reads from their samples (option "delay_flag_exact" = 2) ----
+    // In a chunk of ONE block with no loop cut, the edges that read a producer's previous block (recorded above) resolve to kept blocks
+    // of the previous chunk and the other edges form a DAG: everything a delay D depends on in this block lies in front of it in the
+    // walk, and every consumer of D either comes after it or reads the block before, whose flag was read a block ago.  Accepted, while
+    // nothing has moved: a reachable D with its flag down that is on a loop (among the stack nodes of a back edge, or reached by its
+    // own cone) and not in front of a modulated playbackRate, whose cone over the edges that are not stale holds no ConvolverNode, no
+    // source with a modulated playbackRate and no other DelayNode with its flag down -- the conditions of the delays on no loop (below),
+    // on the smaller cone.  While one is accepted the chunk is one block and no loop is cut; the flag is sticky, so chunks of
+    // `cycleBlocks` blocks return once it is up.
+    if (delayFlagExact >= 2 && !staleProducers.empty()) {
+      std::sort(topoStaleEdges.begin(), topoStaleEdges.end());
+      auto staleEdge = [&](int from, int up) { return std::binary_search(topoStaleEdges.begin(), topoStaleEdges.end(), ((uint64_t)from << 32) | (uint64_t)up); };
+      std::vector<int> seen(nodes.size(), -1), work, cone;
+      for (int id : topo) {
+        if (nodes[id]->type != GA_NODE_DELAY) continue;
+        const DelayS& d = rec<DelayS>(*nodes[id]);
+        if (d.delayAudible) continue;
+        // on a loop?  (the whole cone, as the acceptance of the other delays walks it)
+        bool onLoop = d.delayOnLoop;
+        if (!onLoop) {
+          work.assign(1, id);
+          seen[id] = id;
+          while (!work.empty() && !onLoop) {
+            const NodeS& nd = *nodes[work.back()];
+            work.pop_back();
+            auto visit = [&](int up) {
+              if (up == id) onLoop = true;
+              if (seen[up] == id) return;
+              seen[up] = id;
+              work.push_back(up);
+            };
+            for (const auto& p : nd.params)
+              for (const auto& m : p.modulation) visit(m.first);
+            for (const auto& in : nd.inputs)
+              for (const Conn& cn : in.connected) visit(cn.node);
+          }
+        }
+        if (!onLoop) continue;
+        bool ok = true;
+        const int mark = id + (int)nodes.size();   // (a second stamp per delay: the cone over the edges that are not stale)
+        cone.clear();
+        work.assign(1, id);
+        seen[id] = mark;
+        while (!work.empty() && ok) {
+          const int from = work.back();
+          const NodeS& nd = *nodes[from];
+          work.pop_back();
+          auto visit = [&](int up) {
+            if (seen[up] == mark || staleEdge(from, up)) return;
+            seen[up] = mark;
+            const NodeS& u = *nodes[up];
+            if ((u.type == GA_NODE_DELAY && !rec<DelayS>(u).delayAudible) || u.type == GA_NODE_CONVOLVER ||
+                ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty())) {
+              if (ok) kept(id, u.type == GA_NODE_DELAY ? "on a loop, another delay with its flag down in its cone" : u.type == GA_NODE_CONVOLVER ? "on a loop, a convolver in its cone" : "on a loop, a modulated rate in its cone", up);
+              ok = false;
+            }
+            cone.push_back(up);
+            work.push_back(up);
+          };
+          for (const auto& p : nd.params)
+            for (const auto& m : p.modulation) visit(m.first);
+          for (const auto& in : nd.inputs)
+            for (const Conn& cn : in.connected) visit(cn.node);
+        }
+        if (!ok) continue;
+        updateRateCone(topo);
+        if (!topoRateMods.empty() && rateCone[id]) {
+          kept(id, "on a loop, in front of a modulated rate", id);
+          continue;
+        }
+        if (loopProbeCone.empty()) loopProbeCone.assign(nodes.size(), 0);
+        for (int up : cone) loopProbeCone[up] = 1;
+        loopProbeDelays.push_back(id);
+      }
+    }
+    if (!staleProducers.empty() && !unbreakable && cycleDelaySplit && loopProbeDelays.empty()) {
       int K = 1 << 30;
       for (size_t m = 0; m < candidate.size(); m++)
         if (candidate[m]) K = std::min(K, splittable(*nodes[m]));
@@ -287,38 +408,7 @@ void Context::chunkTopology(ChunkRun& r) {
   // The rate decides how many samples each block consumes and where a one-shot source ends, and the planner needs that before it can
   // plan the rest: the modulation inputs' cone is rendered first.  The cases that cannot be split so are refused here, before any state
   // moves (the context stays usable).
-  if (rateModsVersion != graphVersion || rateCone.size() != nodes.size()) {
-    topoRateMods.clear();
-    for (int id : topo) {
-      const NodeS& nd = *nodes[id];
-      if ((nd.type == GA_NODE_BUFFER_SOURCE || nd.type == GA_NODE_STREAM_SOURCE) && !nd.params.empty() && !nd.params[0].modulation.empty())
-        topoRateMods.push_back({id, 0});
-    }
-    // the cone: every node the modulation inputs reach backwards (params before inputs, as Nodes/AudioNode.cs:167-175 pulls them)
-    rateCone.assign(nodes.size(), 0);
-    std::vector<int> stack;
-    for (const auto& pm : topoRateMods)
-      for (const auto& m : nodes[pm.first]->params[pm.second].modulation)
-        if (!rateCone[m.first]) {
-          rateCone[m.first] = 1;
-          stack.push_back(m.first);
-        }
-    while (!stack.empty()) {
-      const NodeS& nd = *nodes[stack.back()];
-      stack.pop_back();
-      auto visit = [&](int up) {
-        if (!rateCone[up]) {
-          rateCone[up] = 1;
-          stack.push_back(up);
-        }
-      };
-      for (const auto& p : nd.params)
-        for (const auto& m : p.modulation) visit(m.first);
-      for (const auto& in : nd.inputs)
-        for (const Conn& cn : in.connected) visit(cn.node);
-    }
-    rateModsVersion = graphVersion;
-  }
+  updateRateCone(topo);
   if (!topoRateMods.empty()) {
     for (const auto& pm : topoRateMods)
       if (rateCone[pm.first])
@@ -354,8 +444,24 @@ void Context::chunkTopology(ChunkRun& r) {
     for (int id : topo) {
       if (nodes[id]->type != GA_NODE_DELAY) continue;
       DelayS& d = rec<DelayS>(*nodes[id]);
-      if (d.delayAudible || d.delayOnLoop || d.delaySplit) continue;
-      if (!topoRateMods.empty() && rateCone[id]) continue;
+      if (std::find(loopProbeDelays.begin(), loopProbeDelays.end(), id) != loopProbeDelays.end()) {   // (a delay on a loop, accepted above: value 2)
+        if (r.stage1.empty()) r.stage1.assign(nodes.size(), 0);
+        r.stage1[id] = 1;
+        d.delayProbe = true;
+        d.delayShadow = false;
+        d.delaySpans.clear();
+        probeDelays.push_back(id);
+        continue;
+      }
+      if (d.delayAudible) continue;
+      if (d.delayOnLoop || d.delaySplit) {
+        kept(id, "on a loop", id);
+        continue;
+      }
+      if (!topoRateMods.empty() && rateCone[id]) {
+        kept(id, "in front of a modulated rate", id);
+        continue;
+      }
       if (seen.empty()) seen.assign(nodes.size(), -1);
       bool ok = true;
       cone.clear();
@@ -367,13 +473,18 @@ void Context::chunkTopology(ChunkRun& r) {
         auto visit = [&](int up) {
           // (the cone reaches D itself: D is on a loop that the walk from the destination closed through a node it had finished
           // already, so D was never on the stack of a back edge -- a consumer of D would be stage 1's and read a view D does not hand out)
-          if (up == id) ok = false;
+          if (up == id) {
+            if (ok) kept(id, "on a loop closed through a finished node", up);
+            ok = false;
+          }
           if (seen[up] == id) return;
           seen[up] = id;
           const NodeS& u = *nodes[up];
           if ((u.type == GA_NODE_DELAY && !rec<DelayS>(u).delayAudible) || u.type == GA_NODE_CONVOLVER ||
-              ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty()))
+              ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty())) {
+            if (ok) kept(id, u.type == GA_NODE_DELAY ? "another delay with its flag down in front of it" : u.type == GA_NODE_CONVOLVER ? "a convolver in front of it" : "a modulated rate in front of it", up);
             ok = false;
+          }
           cone.push_back(up);
           stack.push_back(up);
         };
@@ -392,12 +503,19 @@ void Context::chunkTopology(ChunkRun& r) {
       probeDelays.push_back(id);
     }
     r.probeDelays = probeDelays;
+    if (!loopProbeDelays.empty()) {
+      for (size_t id = 0; id < loopProbeCone.size(); id++)
+        if (loopProbeCone[id]) r.stage1[id] = 1;
+      r.loopProbe = true;
+    }
   }
-  if (!r.stage1.empty()) {
+  if (!r.stage1.empty() && !r.loopProbe) {
     // A feedback loop lies entirely inside stage 1's set or entirely outside it (the set is closed upstream; a loop through a modulated
     // source is refused above, a delay on a loop is not accepted): a loop outside is stage 2's alone, the same walk from the destination
     // as a one-pass chunk.  A loop inside is stage 1's, and stage 1 has to enter the set where the reference's walk does
     // (Sim::evalProbe): the nodes of the set first reached from a node outside it, in the order the walk reaches them.
+    // (A chunk with an accepted delay on a loop, ChunkRun::loopProbe, has loops that lie partly in each stage: stage 1 walks from the
+    // destination and passes through the nodes outside the set, Sim::passThrough.)
     bool coneLoop = false;
     for (int id : staleProducers) coneLoop = coneLoop || r.stage1[id];
     if (coneLoop)
@@ -575,6 +693,7 @@ void Context::chunkSimulate(ChunkRun& r) {
   // ---- simulate ----
   Sim sim{*this, n};
   sim.pre = r.pre;
+  if (r.stage == 1 && r.loopProbe) sim.passSet = &r.stage1;
   std::vector<int64_t> extraBreaks;
   sim.extraBreaks = &extraBreaks;
   sim.blockTimes = &bt;
@@ -1081,6 +1200,10 @@ void Context::chunkRetire(ChunkRun& r) {
 // once, in front of stage 1 (nothing has overwritten the previous chunk's slabs yet), and committed once, behind stage 2: stage 2's
 // output views hold the cone's views (and folded gains / gain curves) copied from stage 1, and its commit stamps NodeS::staleSeq with
 // the chunk number the next chunk's seed checks -- a commit in stage 1 would carry the number before and be seeded over again.
+// Option "delay_flag_exact" = 2, a delay on a loop accepted (ChunkRun::loopProbe, chunkTopology): the chunk is one block, no loop is
+// cut, and the loop lies partly in each stage.  Stage 1 holds the delay and its cone over the edges that are not stale, and walks
+// from the destination, passing through the other nodes (Sim::passThrough); a stale term across the split is the kept block seeded
+// in front of stage 1.  The gather and the test of the delay's block are one launch (delay_probe_kernel, chunkRateProbe).
 void Context::runTwoStageChunk(ChunkRun& r) {
   // ---- stage 1: the modulator cone ----
   ChunkRun r1;
@@ -1092,6 +1215,8 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   r1.rateMods = r.rateMods;
   r1.coneRoots = std::move(r.coneRoots);
   r1.probeDelays = r.probeDelays;
+  r1.loopProbe = r.loopProbe;
+  if (r.loopProbe) r1.stage1 = r.stage1;   // (Sim::passThrough)
   const std::vector<char>& stage1 = r.stage1;
   for (int id : r.topo)
     if (stage1[id]) r1.topo.push_back(id);
@@ -1132,6 +1257,9 @@ void Context::runTwoStageChunk(ChunkRun& r) {
     }
     d.delayAudible = !d.delaySpans.empty() && d.delaySpans.back().onset != std::numeric_limits<int64_t>::max();
     if (read) stats.delay_flags_read++;
+    // (a loop: a consumer that reads this node's previous block takes the flag from the node's output state, and stage 2 may hold no
+    // consumer that puts it there -- Sim::restorePre)
+    if (r.loopProbe && !d.outputs.empty()) d.outputs[0].silent = !d.delayAudible;
   }
 
   // ---- stage 2: everything else ----
@@ -1235,7 +1363,11 @@ void Context::chunkRateProbe(ChunkRun& r) {
   const size_t ratesBytes = (size_t)roundup((int64_t)nm * n * (int64_t)sizeof(float), 16);
   // the accepted delays (option "delay_flag_exact"): one job per span between two re-rents in which the prediction raises the flag --
   // the samples cannot raise it earlier -- over the blocks from there to the span's end; its word travels with the rates
+  // (a one-block chunk with an accepted delay on a loop, delay_flag_exact = 2: planDelay has kept the gather of every such span back --
+  // Exec::delayProbeJobs -- and delay_probe_kernel gathers, tests and lowers the word in one launch)
   std::vector<DelayOnsetJob> onsets;
+  std::vector<int> onsetWord;   // the word of each job
+  size_t nwords = 0;
   for (int id : r.probeDelays) {
     DelayS& d = rec<DelayS>(*nodes[id]);
     for (size_t k = 0; k < d.delaySpans.size(); k++) {
@@ -1243,18 +1375,26 @@ void Context::chunkRateProbe(ChunkRun& r) {
       const int64_t end = std::min<int64_t>(k + 1 < d.delaySpans.size() ? d.delaySpans[k + 1].b0 : n, n);
       sp.word = -1;
       if (sp.rise < 0 || sp.rise >= end || sp.ch < 1) continue;
+      bool fused = false;
+      for (size_t q = 0; q < ex.delayProbeNode.size(); q++)
+        if (ex.delayProbeNode[q] == id) fused = true;
+      if (fused) {
+        sp.word = (int)nwords++;
+        continue;
+      }
       DelayOnsetJob oj{};
       oj.nrows = std::min(sp.ch, kDelayOnsetRows);
       for (int ch = 0; ch < oj.nrows; ch++) oj.rows[ch] = ex.nodeOut(id, ch);   // (planDelay wrote every block of the span)
       oj.first = (int32_t)sp.rise;
       oj.count = (int32_t)(end - sp.rise);
-      sp.word = (int)onsets.size();
+      sp.word = (int)nwords++;
+      onsetWord.push_back(sp.word);
       onsets.push_back(oj);
     }
   }
   const size_t onsetOff = (size_t)roundup((int64_t)(ratesBytes + walks.size() * sizeof(GsrWalkOut)), 16);
-  const size_t readBytes = onsets.empty() ? ratesBytes + walks.size() * sizeof(GsrWalkOut)
-                                          : (size_t)roundup((int64_t)(onsetOff + onsets.size() * sizeof(int32_t)), 16);
+  const size_t readBytes = nwords == 0 ? ratesBytes + walks.size() * sizeof(GsrWalkOut)
+                                       : (size_t)roundup((int64_t)(onsetOff + nwords * sizeof(int32_t)), 16);
   r.waited = readBytes > 0;
   if (!r.waited) return;
   size_t descCount = 0;
@@ -1317,14 +1457,21 @@ void Context::chunkRateProbe(ChunkRun& r) {
   }
   const size_t btOff = ex.plan.putv(r.bt);
   hipStream_t st = stream;
-  if (!onsets.empty()) {
+  if (nwords > 0) {
     int32_t* wordsDev = (int32_t*)((char*)rateModDev + onsetOff);
     r.onsetWords = (const int32_t*)((const char*)rateModHost + onsetOff);
-    for (size_t k = 0; k < onsets.size(); k++) onsets[k].out = wordsDev + k;
-    const std::vector<int32_t> none(onsets.size(), std::numeric_limits<int32_t>::max());
+    for (size_t k = 0; k < onsets.size(); k++) onsets[k].out = wordsDev + onsetWord[k];
+    for (size_t q = 0; q < ex.delayProbeJobs.size(); q++) {   // (all rows of a node lower the node's word)
+      const DelayS& d = rec<DelayS>(*nodes[ex.delayProbeNode[q]]);
+      if (d.delaySpans.empty() || d.delaySpans.back().word < 0) fail(GA_ERR_DEVICE, "internal: a delay probe job without a word");
+      ex.delayProbeJobs[q].word = wordsDev + d.delaySpans.back().word;
+    }
+    ex.delayProbeNode.clear();
+    const std::vector<int32_t> none(nwords, std::numeric_limits<int32_t>::max());
     const size_t noneOff = ex.plan.putv(none), noneBytes = none.size() * sizeof(int32_t);
     ex.plan.add(LK_OTHER, [=](uint8_t* base) { GA_HIP(hipMemcpyAsync(wordsDev, base + noneOff, noneBytes, hipMemcpyDeviceToDevice, st)); });
     ex.flush(onsets, LK_OTHER, &DelayOnsetJob::count, [=](const DelayOnsetJob* t, int nj, int64_t mx, uint8_t*) { launch_delay_onset(st, t, nj, mx); });
+    ex.flush(ex.delayProbeJobs, LK_OTHER, nullptr, [=](const DelayProbeJob* t, int nj, int64_t, uint8_t*) { launch_delay_probe(st, t, nj); });
   }
   ex.flush(pjobs, LK_OTHER, nullptr, [=](const KrateProbeJob* t, int nj, int64_t, uint8_t* base) { launch_krate_probe(st, t, nj, base, (const double*)(base + btOff), n); });
   ex.flush(walks, LK_OTHER, nullptr, [=](const GsrWalkJob* t, int nw, int64_t, uint8_t*) { launch_gsr_walk(st, t, nw); });

@@ -124,7 +124,29 @@ struct Sim {
   // walk between two roots only visits nodes outside it, which leave the cone's state alone.
   // The DelayNodes whose flag is read from their samples (option "delay_flag_exact", Context::chunkTopology) are evaluated after the
   // roots: their cones are stage 1's as well, and nothing in stage 1 reads their output.
+  // A chunk with an accepted delay on a loop (delay_flag_exact = 2, ChunkRun::loopProbe): the loop lies partly in stage 1's set and
+  // partly outside it, and which of its edges reads the previous block is decided by the walk from the DESTINATION (`pull` takes it
+  // from isProcessing).  Stage 1 therefore walks from the destination and passes through the nodes outside the set (`passSet`): they
+  // are marked as being processed while their connections are followed, params before inputs, in order -- every node of the set is
+  // met with the stack the whole walk would have -- but they are not processed, recorded or stamped: stage 2 does that.
+  const std::vector<char>* passSet = nullptr;   // node id -> in stage 1's set; null = no passing through
+  std::vector<char> passSeen;
+  void passThrough(int id) {
+    NodeS& n_ = *c.nodes[id];
+    if (passSeen[id] || n_.isProcessing) return;   // (being processed: the edge that led here reads the node's previous block)
+    n_.isProcessing = true;
+    for (auto& ps : n_.params)
+      for (auto& m : ps.modulation) evalNode(m.first);
+    for (auto& in : n_.inputs)
+      for (const Conn& cn : in.connected) evalNode(cn.node);
+    n_.isProcessing = false;
+    passSeen[id] = 1;
+  }
   void evalProbe(const std::vector<std::pair<int, int>>& mods, const std::vector<int>& roots, const std::vector<int>& delays) {
+    if (passSet) {
+      passSeen.assign(c.nodes.size(), 0);
+      evalNode(0);
+    }
     for (int id : roots)
       if (!c.nodes[id]->disposed) evalNode(id);   // (a source of the cone disposed at the chunk's first block: chunkSimulate)
     for (int id : delays)
@@ -211,6 +233,7 @@ struct Sim {
 
   void evalNode(int id) {  // AudioNode.ProcessInternal, Nodes/AudioNode.cs:152-183
     if (pre && restorePre(id)) return;   // (before the memo check: the first stage stamped these nodes with this chunk's block numbers)
+    if (passSet && !(*passSet)[id]) return passThrough(id);
     NodeS& n_ = *c.nodes[id];
     if (n_.lastProcessedBlock == blockNumber) return;
     if (n_.isProcessing) fail(GA_ERR_CYCLE, "Audio graph cycle detected at node " + std::to_string(id));   // (unreachable, as in the reference)
@@ -589,6 +612,10 @@ struct Exec {
   std::vector<OscJob> oscJobs;
   std::vector<PanJob> panJobs;
   std::vector<DelayJob> delayJobs;
+  // accepted DelayNodes of a one-block chunk whose prediction rises (delay_flag_exact = 2): one job per channel row, launched with
+  // their words by Context::chunkRateProbe -- nothing in stage 1 reads the rows
+  std::vector<DelayProbeJob> delayProbeJobs;
+  std::vector<int> delayProbeNode;               // parallel: the node of the job
   std::vector<PanDynJob> panDynJobs;
   std::vector<SpatialJob> spatialJobs;     // one per spatial node of the chunk (all levels: SpatialWork::job indexes it) ...
   std::vector<SpatialWork> spatialWorks;   // ... and the workgroups of the level being planned
@@ -1018,6 +1045,7 @@ struct ChunkRun {
   std::vector<int> coneRoots;                    // stage 1 of a cone with a feedback loop: where the reference's walk enters the cone, in order
   std::vector<int> probeDelays;                  // DelayNodes whose flag this chunk reads from their samples (option "delay_flag_exact")
   std::vector<char> stage1;                      // node id -> rendered by stage 1: the modulator cone, the accepted delays and their cones
+  bool loopProbe = false;                        // a delay on a feedback loop is accepted (delay_flag_exact = 2): one block, stage 1 walks from the destination
   bool waited = true;                            // stage 1: the host waited for the probe's words (false: nothing to read back)
   const int32_t* onsetWords = nullptr;           // stage 1: the words of delay_onset_kernel, read back (DelayS::DelaySpan::word indexes them)
   struct PreOut { int bufCh; bool silent, zero; };

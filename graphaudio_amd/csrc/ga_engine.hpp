@@ -928,8 +928,15 @@ struct Context {
   bool spatialOcclusion = false;      // option "spatial_occlusion": occlusion > 0 and the three-band transmission are rendered (spatial_direct_kernel); 0 = refused
   SpatialBands spBands{};             // the band filters of that stage: fixed per context (made when the first job is planned)
   bool spBandsMade = false;
-  bool delayFlagExact = false;   // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology)
+  int delayFlagExact = 0;        // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology);
+                                 // 1 = delays on no feedback loop, 2 = also delays on a loop, in chunks of one block
   std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (DelayS::delayProbe)
+  // delay_flag_exact = 2, a graph with feedback (walked every chunk, chunkTopology): the edges of the reference's walk that read their
+  // producer's previous block, as (consumer << 32 | producer), sorted; the DelayNodes on a loop accepted for this chunk and the union of
+  // their cones over the other edges
+  std::vector<uint64_t> topoStaleEdges;
+  std::vector<int> loopProbeDelays;
+  std::vector<char> loopProbeCone;
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);

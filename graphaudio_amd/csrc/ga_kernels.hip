@@ -3453,6 +3453,24 @@ void launch_delay_onset(hipStream_t s, const DelayOnsetJob* jobs_dev, int njobs,
   GA_LAUNCH_JOBS(delay_onset_kernel, gx, 256, jobs_dev, njobs);
 }
 
+// delay_kernel and delay_onset_kernel for one block in one launch (see DelayProbeJob): two waves, lane l of wave w computes frame
+// 64 w + l, one ballot per wave, one lane per wave lowers the word and only on a hit.
+__global__ __launch_bounds__(kBlock) void delay_probe_kernel(const DelayProbeJob* __restrict jobs) {
+  const DelayProbeJob job = jobs[blockIdx.y];
+  const int64_t f = job.f0 + threadIdx.x;
+  const float dt = job.curve ? gptr(job.curve)[f] : job.value;
+  int d = (int)(dt * (float)job.sample_rate);   // float * int -> float, truncated (:68, :88)
+  d = min(max(d, 0), job.max_delay);
+  const float v = d > 0 ? gptr(job.line)[f - d] : 0.f;
+  gptr(job.out)[f] = v;
+  // -0.0f is zero, a NaN and a denormal are not: the bit pattern without its sign, whatever the wave's denormal mode
+  if (__ballot((__float_as_uint(v) << 1) != 0u) != 0ull && (threadIdx.x & 63) == 0) atomicMin(job.word, job.block);
+}
+void launch_delay_probe(hipStream_t s, const DelayProbeJob* jobs_dev, int njobs) {
+  if (njobs <= 0) return;
+  GA_LAUNCH_JOBS(delay_probe_kernel, 1, kBlock, jobs_dev, njobs);
+}
+
 
 __device__ __forceinline__ void pan_gains(float pan, int stereo, float& gl, float& gr) {   // :94-98 / :129-133
   const float PIf = 3.14159265358979323846f;

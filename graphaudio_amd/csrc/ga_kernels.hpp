@@ -636,6 +636,23 @@ struct DelayOnsetJob {
 };
 void launch_delay_onset(hipStream_t s, const DelayOnsetJob* jobs_dev, int njobs, int64_t max_blocks);
 
+// One 128-frame block of an accepted DelayNode in a one-block chunk (option "delay_flag_exact" = 2: a delay on a feedback loop; those
+// chunks are launch bound): DelayJob's gather and DelayOnsetJob's test in one launch.  out[f0 + i] is computed with delay_kernel's
+// statements; if any of the 128 samples is `!= 0f` by its bit pattern without the sign, `*word` (INT32_MAX from the plan) is lowered
+// to `block` with atomicMin.  One job per channel row; the rows of a node share the node's word.
+struct DelayProbeJob {
+  const float* line;    // line[f0 - max_delay .. f0 + 128) must be readable
+  const float* curve;   // a-rate delayTime curve or null -> `value`
+  float* out;           // out[f0 .. f0 + 128) is written
+  int32_t* word;
+  float value;
+  int sample_rate;
+  int max_delay;
+  int32_t block;        // the chunk block the word is lowered to
+  int64_t f0;
+};
+void launch_delay_probe(hipStream_t s, const DelayProbeJob* jobs_dev, int njobs);
+
 // AudioParam.ComputeARate / ComputeKRate with a non-silent modulation input (AudioParam.cs:123-135,148-160):
 //   a-rate: out[f] = clamp(intrinsic[f] + mod[f], min, max) ; k-rate: the block's first sample of both, repeated over the block
 struct ParamModJob {

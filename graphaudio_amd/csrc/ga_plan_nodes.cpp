@@ -180,6 +180,32 @@ void Context::planDelay(NodePlanCtx& k) {
     return;
   }
   const float* delayCurve = ex.paramView((int)si, ns, 0);
+  // An accepted node of a one-block chunk whose prediction rises in it (delay_flag_exact = 2): the gather and the test of its samples
+  // are one launch (delay_probe_kernel), queued with the node's word by Context::chunkRateProbe.  One-block chunks are launch bound.
+#ifdef GA_EXPERIMENTS
+  static const bool probeSeparate = expenv("GA_DELAY_PROBE_SEPARATE") != nullptr;   // A/B: delay_kernel + delay_onset_kernel, as in longer chunks
+#else
+  constexpr bool probeSeparate = false;
+#endif
+  if (nd.delayProbe && k.r.loopProbe && !probeSeparate && k.delayPhase == 0 && f0 == 0 && nf == kBlock && !nd.delaySpans.empty() &&
+      nd.delaySpans.back().rise == 0) {
+    for (int cch = 0; cch < ch; cch++) {
+      DelayProbeJob pj{};
+      pj.line = ring[cch];
+      pj.curve = delayCurve;
+      pj.out = ex.nodeOut(ns.id, cch);
+      pj.word = nullptr;   // (chunkRateProbe)
+      pj.value = nd.params[0].value;
+      pj.sample_rate = sampleRate;
+      pj.max_delay = maxD;
+      pj.block = 0;
+      pj.f0 = f0;
+      ex.delayProbeJobs.push_back(pj);
+      ex.delayProbeNode.push_back(ns.id);
+      nd.delayW[cch] += nf;
+    }
+    return;
+  }
   for (int cch = 0; cch < ch; cch++) {
     float* base = ring[cch];
     DelayJob dj;

@@ -141,10 +141,13 @@ typedef struct ga_stats {
                                    last segment were taken over (steady renders, option "sim_replay") */
   int64_t twin_rows;            /* channel rows that were not computed a second time: a mono signal in a stereo node or input is the
                                    same numbers on every channel (AudioNodeInput.cs:182-244), evaluated once (option "twin_channels") */
-  int64_t delay_flags_read;     /* option "delay_flag_exact": (DelayNode, chunk) pairs whose output flag was taken from the node's output
-                                   samples (the first sample != 0f, DelayNode.cs:72,92,96-97) */
+  int64_t delay_flags_read;     /* option "delay_flag_exact" (ga_set_option; 0 = off, the default; 1 = DelayNodes on no feedback loop;
+                                   2 = also DelayNodes on a feedback loop, rendered one block per chunk while such a node's flag is
+                                   down; any other value is GA_ERR_OUT_OF_RANGE): (DelayNode, chunk) pairs whose output flag was taken
+                                   from the node's output samples (the first sample != 0f, DelayNode.cs:72,92,96-97) */
   int64_t delay_flags_predicted; /* (DelayNode, chunk) pairs whose output flag rose by the host's prediction while the option was on: a
-                                    delay on a feedback loop, behind another undecided delay, a modulated playbackRate or a convolver */
+                                    delay behind another undecided delay, a modulated playbackRate or a convolver, and with value 1 a
+                                    delay on a feedback loop */
 } ga_stats;
 enum {
   GA_STAGE_OTHER = 0,        /* sources, biquads, gains, parameter curves, ... */

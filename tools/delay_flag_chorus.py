@@ -6,6 +6,15 @@ Renders SECONDS of audio in chunks of CHUNK blocks with the option off and on, p
 stage 1 and the mean stage-1 wait (from the library's GA_TIMING log), and whether the two outputs differ.
 
     python tools/delay_flag_chorus.py [--voices 256] [--seconds 4] [--chunk 64]
+
+--loop: every voice's delay sits on a feedback loop (gain -> low-pass -> delay -> gain 0.1 -> back) and is fed by a one-shot that
+starts with digital silence; the burst that goes round the loop starts at 0.25 s, after the last delay's flag is up.  The option is
+compared at 0 and 2 (value 1 leaves a delay on a loop to the prediction).  The delay time is modulated, so no loop can be cut: both
+settings render one block per chunk, and the difference is the second stage and the wait (--seconds 0.25 renders that phase alone).
+--loop --constant: the same voices with a constant delay time.  With the option off every loop is cut at its delay and the chunks
+are 7 blocks; with 2 the chunks are one block until the last delay's flag is up: what reading the flags costs in chunk length.
+--library PATH loads another build of the library (tools/build_variant.sh); with a -DGA_EXPERIMENTS build, GA_DELAY_PROBE_SEPARATE=1
+plans the accepted delays as delay_kernel + delay_onset_kernel instead of the fused delay_probe_kernel.
 """
 import argparse
 import os
@@ -79,10 +88,55 @@ def build(ctx, voices):
     return hold
 
 
+def build_loop(ctx, voices, constant=False):
+    ctx.Destination.SetChannelCount(1)
+    hold = []
+    mix = GainNode(ctx)
+    mix.Gain.Value = 1.0 / 16.0
+    mix.Connect(ctx.Destination)
+    for v in range(voices):
+        rng = np.random.default_rng(100 + v)
+        burst = AudioBufferSourceNode(ctx)
+        burst.Buffer = PlayableAudioBuffer.FromMonoArray((rng.standard_normal(384) * 0.25).astype(np.float32), SR)
+        g1, g2 = GainNode(ctx), GainNode(ctx)
+        g2.Gain.Value = 0.1   # (the low-pass peaks at Q = 8: the loop's gain stays below 1)
+        bq = BiQuadFilterNode(ctx)
+        bq.Type = FilterType.Lowpass
+        bq.Frequency.Value = 200.0 + 3.0 * v
+        bq.Q.Value = 8.0
+        z = 805 + 37 * v
+        x = (rng.standard_normal(z + 2560) * 0.25).astype(np.float32)
+        x[:z] = 0.0
+        late = AudioBufferSourceNode(ctx)
+        late.Buffer = PlayableAudioBuffer.FromMonoArray(x, SR)
+        d = DelayNode(ctx, 0.05)
+        d.DelayTime.Value = 0.02
+        lfo = OscillatorNode(ctx)
+        lfo.Type = OscillatorType.Triangle
+        lfo.Frequency.Value = 2.0
+        depth = GainNode(ctx)
+        depth.Gain.Value = 0.005
+        lfo.Connect(depth)
+        if not constant:
+            depth.Connect(d.DelayTime)
+        burst.Connect(g1)
+        g1.Connect(bq)
+        bq.Connect(d)
+        d.Connect(g2)
+        g2.Connect(g1)
+        late.Connect(d)
+        g1.Connect(mix)
+        burst.Start(0.25)
+        late.Start()
+        lfo.Start()
+        hold += [burst, g1, g2, bq, late, d, lfo, depth]
+    return hold
+
+
 def run(voices, frames, chunk, on, build=build):
     ctx = OfflineAudioContext(SR)
     ctx.SetOption("max_chunk_blocks", chunk)
-    ctx.SetOption("delay_flag_exact", 1 if on else 0)
+    ctx.SetOption("delay_flag_exact", int(on))
     hold = build(ctx, voices)
     out = np.zeros((1, frames), np.float32)
     sys.stderr.flush()
@@ -111,12 +165,21 @@ def main():
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--idle", action="store_true", help="the idle-delay scene instead: the option must cost no stage-1 wait")
+    ap.add_argument("--loop", action="store_true", help="every delay on a feedback loop: the option at 0 and at 2")
+    ap.add_argument("--constant", action="store_true", help="with --loop: constant delay times, so the loops can be cut at the delays")
+    ap.add_argument("--library", default="", help="load this build of the library instead of the product (tools/build_variant.sh)")
     a = ap.parse_args()
-    scene = build_idle if a.idle else build
+    if a.library:
+        from graphaudio_amd import _capi
+        _capi.use_library(a.library)
+    scene = build_idle if a.idle else build_loop if a.loop else build
+    if a.loop and a.constant:
+        scene = lambda ctx, voices: build_loop(ctx, voices, constant=True)
+    top = 2 if a.loop else 1
     frames = int(a.seconds * SR) // 128 * 128
-    run(min(a.voices, 8), 128 * 64, a.chunk, True, scene)   # (warm-up: module load, allocations)
+    run(min(a.voices, 8), 128 * 64, a.chunk, top, scene)   # (warm-up: module load, allocations)
     res = {}
-    for on in (0, 1):
+    for on in (0, top):
         out, dt, waits, st = run(a.voices, frames, a.chunk, on, scene)
         res[on] = out
         print(f"delay_flag_exact={on}: {frames / dt:,.0f} frames/s ({dt * 1e3:.1f} ms for {frames} frames, {st['chunks']} chunks), "
@@ -124,8 +187,8 @@ def main():
               f"flags read {st['delay_flags_read']}, predicted {st['delay_flags_predicted']}")
     if a.idle:
         return
-    d = res[0] - res[1]
-    print(f"outputs differ by {float(np.sqrt(np.mean(d * d))):.3e} RMS on {float(np.sqrt(np.mean(res[1] ** 2))):.3e} RMS")
+    d = res[0] - res[top]
+    print(f"outputs differ by {float(np.sqrt(np.mean(d * d))):.3e} RMS on {float(np.sqrt(np.mean(res[top] ** 2))):.3e} RMS")
 
 
 if __name__ == "__main__":
