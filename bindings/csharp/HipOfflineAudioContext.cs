@@ -109,6 +109,23 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _convMigrate;
+    /// <summary>Option "conv_migrate" (default off): a ConvolverNode that is already running on a fast formulation when an edit makes
+    /// it sensitive (its output reaches an AudioParam, a resonant low BiQuadFilterNode or a feedback loop whose gain comes near 1) is
+    /// moved to the reference-order formulation.  From the coarse-partition formulation its state is rebuilt from its input history:
+    /// from that chunk on its output is what a node on the reference-order formulation from its first block would give, bit for
+    /// bit; from a shared-impulse-response group the state is copied and the same holds P blocks later.  One way: the node never
+    /// returns to the fast formulation (Stats.conv_migrations counts the nodes moved).</summary>
+    public bool ConvMigrate
+    {
+        get => _convMigrate;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "conv_migrate", value ? 1 : 0));
+            _convMigrate = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

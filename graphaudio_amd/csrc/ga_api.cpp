@@ -374,6 +374,10 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
       if (value != 0 && value != 1 && value != 2) fail(GA_ERR_OUT_OF_RANGE, "delay_flag_exact is 0, 1 or 2");
       c.delayFlagExact = (int)value;
     }
+    else if (k == "conv_migrate") {
+      if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "conv_migrate is 0 or 1");
+      c.convMigrate = value != 0;
+    }
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);
     else if (k == "coarse_premix") c.coarsePremix = value != 0;

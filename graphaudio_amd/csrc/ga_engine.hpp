@@ -969,6 +969,20 @@ struct Context {
   int convRefOrder = 1;               // option "conv_reference_order": 0 = never, 1 = where refOrderSensitivity() asks for it, 2 = every convolver
   double convRefMinDeviation = 2.5e-6;  // option "conv_ref_min_deviation": a downstream biquad counts as sensitive above this predicted deviation
   std::vector<char> refSensScratch;
+  // option "conv_migrate": a convolver that is on formulation D or A when it becomes sensitive moves to the B / C state layout (which R
+  // shares) and never returns.  migrateConvolvers (per chunk, between refOrderSensitivity and assignConvPaths) gives the node its
+  // private stores; from A it copies the node's columns of the group state, from D it notes where the last P blocks of every input
+  // channel lie and planConvMigration (in front of the chunk's first convolver stage) turns the notes into three launches for all
+  // nodes: conv_rebuild_kernel (spectra of blocks T-P .. T-1 into a scratch plane, T-P+1 .. T-1 into the stores), launch_refmac and
+  // launch_irfft_ola_b over block T-1 alone (its tail is the overlap).  D's stores go to `retired`: freed after the stream has run the rebuild.
+  bool convMigrate = false;
+  struct ConvMigration {
+    int id;
+    const float* src[32];   // per input channel: the first sample of block T-P (nullptr: zeros)
+  };
+  std::vector<ConvMigration> convMigrations;   // of the chunk being planned
+  void migrateConvolvers(const std::vector<int>& topo);
+  void planConvMigration(ChunkRun& r);
   bool coarseTailPrivate = false;  // option "coarse_tail_private": also groups whose members have impulse responses of their own (measured: the forward
                                    // stage saves P' - 1 windows per signal, the multiply-accumulate and inverse stages pay for the tail blocks -- 2.95 vs 2.97 ms at
                                    // 1024 voices per 10 s step, 0.50 vs 0.43 ms at 64 voices per 2.5 s call: off)

@@ -660,6 +660,124 @@ void launch_rfft_fwd_b(hipStream_t s, const ConvRowIO* xrows_dev, int nx, int nb
   }
 }
 
+// Option "conv_migrate": the spectra history of a convolver that leaves formulation D, rebuilt from D's input history (ga_conv_rebuild.hpp).
+// Workgroup = (job, run of 32 blocks), wave w transforms blocks w, w+4, ..., w+28 of the run, four in flight: the arithmetic of
+// rfft_fwd_b_kernel<double>, operation for operation (formulation R's forward transform: the spectra must be the floats that route
+// would have written), on a source that is a plain run of P x 128 samples.  Each value goes to the scratch plane (all P blocks: the
+// partition sum of block T-1 reads them) and to the node's [129][P-1] store (blocks T-P+1 .. T-1).
+__global__ __launch_bounds__(256) void conv_rebuild_kernel(const ConvRebuildJob* __restrict jobs, ConvPlanesB pl, int hist, Twiddles tw,
+                                                           int job0) {
+  typedef double T;
+  __shared__ __attribute__((aligned(16))) float st_r[FB_RUN * FB_KP];
+  __shared__ __attribute__((aligned(16))) float st_i[FB_RUN * FB_KP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ConvRebuildJob* __restrict Jp = &jobs[job0 + blockIdx.y];
+  const int P = Jp->P, xrow = Jp->xrow;
+  const int t0 = blockIdx.x * FB_RUN;
+  if (t0 >= P) return;   // (uniform: the grid is sized for the longest job)
+  const LaneTwT<T> ltw = load_lane_tw_t<T>(tw.w128, lane);
+  const int m = rev6(lane);
+  const int k0 = 2 * m, k1 = 2 * m + 1;
+  const int src0 = rev6((64 - m) & 63), src1 = 63 - lane;
+  const T wk0x = (T)tw.w256[k0].x, wk0y = (T)tw.w256[k0].y;
+  const T wk1x = (T)tw.w256[k1].x, wk1y = (T)tw.w256[k1].y;
+  const GA_GLOBAL float* in = gptr(Jp->src);
+
+  float inr[FB_RUN / 4], ini[FB_RUN / 4];
+#pragma unroll
+  for (int q = 0; q < FB_RUN / 4; q++) {
+    const int t = t0 + wave + 4 * q;
+    inr[q] = 0.f;
+    ini[q] = 0.f;
+    if (in && t < P) {
+      const GA_GLOBAL float* p = in + (int64_t)t * kBlock + 2 * lane;
+      inr[q] = p[0];
+      ini[q] = p[1];
+    }
+  }
+#pragma unroll
+  for (int bq = 0; bq < FB_RUN / 16; bq++) {
+    T s0r[4], s0i[4], s1r[4], s1i[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      s0r[u] = (T)inr[bq * 4 + u];
+      s0i[u] = (T)ini[bq * 4 + u];
+      s1r[u] = fma(s0r[u], ltw.c1, -(s0i[u] * ltw.s1));
+      s1i[u] = fma(s0r[u], ltw.s1, s0i[u] * ltw.c1);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<32, 0>(s0r[u], s0i[u], ltw); dif_stage<32, 0>(s1r[u], s1i[u], ltw); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<16, 1>(s0r[u], s0i[u], ltw); dif_stage<16, 1>(s1r[u], s1i[u], ltw); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<8, 2>(s0r[u], s0i[u], ltw); dif_stage<8, 2>(s1r[u], s1i[u], ltw); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<4, 3>(s0r[u], s0i[u], ltw); dif_stage<4, 3>(s1r[u], s1i[u], ltw); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<2, 4>(s0r[u], s0i[u], ltw); dif_stage<2, 4>(s1r[u], s1i[u], ltw); }
+#pragma unroll
+    for (int u = 0; u < 4; u++) { dif_stage<1, 5>(s0r[u], s0i[u], ltw); dif_stage<1, 5>(s1r[u], s1i[u], ltw); }
+
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int tl = wave + 4 * (bq * 4 + u);   // block within the run
+      float x0r, x0i;
+      {
+        T ax = s0r[u], ay = s0i[u];
+        T bx = shfl_d(ax, src0), by = shfl_d(ay, src0);
+        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
+        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
+        T pr = fma(dr, wk0x, -(di * wk0y)), pi = fma(dr, wk0y, di * wk0x);
+        float xr = (float)(er + pi), xi = (float)(ei - pr);
+        if (k0 == 0) {
+          xi = 0.f;
+          st_r[tl * FB_KP + 64] = (float)(ax - ay);   // bin 128 = E[64]
+          st_i[tl * FB_KP + 64] = 0.f;
+        }
+        x0r = xr;
+        x0i = xi;
+      }
+      {
+        T ax = s1r[u], ay = s1i[u];
+        T bx = shfl_d(ax, src1), by = shfl_d(ay, src1);
+        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
+        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
+        T pr = fma(dr, wk1x, -(di * wk1y)), pi = fma(dr, wk1y, di * wk1x);
+        st_r[tl * FB_KP + m] = x0r;                           // bin 2m
+        st_i[tl * FB_KP + m] = x0i;
+        st_r[tl * FB_KP + FB_OB + m] = (float)(er + pi);      // bin 2m + 1
+        st_i[tl * FB_KP + FB_OB + m] = (float)(ei - pr);
+      }
+    }
+  }
+  __syncthreads();
+  // store: a wave writes the 32 blocks of two bins -- runs of 128 bytes in the plane, and in the store where P - 1 allows
+  float* __restrict dr_ = Jp->dst_r;
+  float* __restrict di_ = Jp->dst_i;
+  for (int idx = tid; idx < kBins * FB_RUN; idx += 256) {
+    const int k = idx >> 5, q = idx & (FB_RUN - 1);
+    const int j = t0 + q;
+    if (j >= P) continue;
+    const int pk = q * FB_KP + fb_pos(k);
+    const float vr = st_r[pk], vi = st_i[pk];
+    const size_t po = conv_rebuild_plane_index(xrow, pl.tx, hist, P, k, j);
+    pl.xr[po] = vr;
+    pl.xi[po] = vi;
+    if (j >= 1) {
+      const size_t so = conv_rebuild_store_index(P, k, j);
+      dr_[so] = vr;
+      di_[so] = vi;
+    }
+  }
+}
+void launch_conv_rebuild(hipStream_t s, const ConvRebuildJob* jobs_dev, int njobs, int max_P, ConvPlanesB pl, int hist, Twiddles tw) {
+  if (njobs <= 0 || max_P <= 0) return;
+  for (int j0 = 0; j0 < njobs; j0 += 65535) {   // gridDim.y limit
+    dim3 grid((max_P + FB_RUN - 1) / FB_RUN, std::min(65535, njobs - j0));
+    hipLaunchKernelGGL(conv_rebuild_kernel, grid, dim3(256), 0, s, jobs_dev, pl, hist, tw, j0);
+  }
+}
+
 // MAC B: workgroup = (set, bin, 256-block time tile); wave = 64 blocks (4 M-tiles) x 16 columns; taps in segments of 256
 constexpr int MB_TW = 256;
 constexpr int MB_PSEG = 256;

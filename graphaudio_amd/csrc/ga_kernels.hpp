@@ -8,6 +8,7 @@
 
 #include "ga_spatial_geom.hpp"
 #include "ga_spatial_direct.hpp"
+#include "ga_conv_rebuild.hpp"
 
 namespace ga {
 
@@ -101,6 +102,11 @@ void launch_refmac(hipStream_t s, const ConvSetB* sets_dev, int nsets, int nbloc
 void launch_irfft_ola_b(hipStream_t s, const ConvRowIO* yrows_dev, int ny, int nblocks, ConvPlanesB pl,
                         const float* const* overlap_in_dev, float* const* overlap_out_dev, Twiddles tw, bool fp64);
 void launch_hist_copy_b(hipStream_t s, const HistJobB* jobs_dev, int njobs, int max_n);
+// A convolver leaves formulation D for this state layout (option "conv_migrate", ga_conv_rebuild.hpp): the last P blocks of every
+// input channel, read from D's input history, are transformed exactly as launch_rfft_fwd_b(fp64 = true) transforms them -- blocks
+// T-P .. T-1 into columns hist-(P-1) .. hist of the scratch planes `pl` (pl.yr / pl.yi are not touched), blocks T-P+1 .. T-1 into the
+// job's [129][P-1] store.  Columns in front of a job's first block are not written (the caller clears the planes).
+void launch_conv_rebuild(hipStream_t s, const ConvRebuildJob* jobs_dev, int njobs, int max_P, ConvPlanesB pl, int hist, Twiddles tw);
 // feedback cycles: dst[0..128) = src[0..128) * scale (src == nullptr: zeros) -- the block a producer put out, kept for the consumers
 // that pull it while it is being processed in the NEXT block (Nodes/AudioNode.cs:153-156)
 struct StaleJob {

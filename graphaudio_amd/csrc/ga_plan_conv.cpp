@@ -837,6 +837,185 @@ void Context::aliasBusToLeader(ChunkRun& r) {
   for (int ch = 0; ch < nch; ch++) ex.setNodeOut(leader, ch, busTarget[ch] ? busTarget[ch] : busSlabs[ch]);
 }
 
+// ======================================================================================================
+// option "conv_migrate": a convolver on formulation D becomes sensitive -> the B / C state layout, evaluated on R
+// ======================================================================================================
+// Formulation D's state is the node's last coarseP x 8192 input samples, and that is everything R's state is a function of: the
+// spectra history is the forward transform of the last P - 1 blocks, the overlap is the second half of block T-1's inverse
+// transform (T = first block of this chunk), whose partition sum reads blocks T-P .. T-1.  This pass only moves the node: it
+// gets the private stores, notes where block T-P of every input channel lies and hands D's stores to the retire list (freed after
+// the stream has run the rebuild, Context::freeRetired); planConvMigration enqueues the rebuild in front of the first convolver stage.
+void Context::migrateConvolvers(const std::vector<int>& topo) {
+  convMigrations.clear();
+  if (!convMigrate) return;
+  for (int id : topo) {
+    if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
+    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
+    if (!nd.ir || !nd.refSens || (nd.convPath != 4 && nd.convPath != 1)) continue;
+    const int P = nd.ir->P;
+    if (nd.convPath == 1) {
+      // Formulation A keeps a spectra history and an overlap of the same meaning as B's, in the columns of its groups ([129 (P-1)][rp],
+      // column idx; rows of a node = impulse-response channels = slots): a state copy.  A's spectra come from float32 transforms, so
+      // the P - 1 blocks behind the move are R's arithmetic over A's spectra (inside the convolver tolerance), and one block later --
+      // the overlap it reads is the first one made of R's spectra alone -- the output is that of a node on R from its first block.
+      const int channels = nd.ir->nch, h = P - 1;
+      if ((int)nd.convRows.size() != channels) continue;   // (rows not made yet: assignConvPaths decides)
+      nd.bInCh = nd.isTrueStereo ? 2 : channels;
+      nd.bSlots = nd.isTrueStereo ? 4 : channels;
+      const size_t hstride = (size_t)kBins * std::max(h, 1);
+      const size_t hb = (size_t)nd.bInCh * hstride * sizeof(float), ob = (size_t)nd.bSlots * 2 * kBlock * sizeof(float);
+      nd.bHistR = (float*)dalloc(hb);
+      nd.bHistI = (float*)dalloc(hb);
+      nd.bOverlap = (float*)dalloc(ob);
+      GA_HIP(hipMemsetAsync(nd.bHistR, 0, hb, stream));
+      GA_HIP(hipMemsetAsync(nd.bHistI, 0, hb, stream));
+      GA_HIP(hipMemsetAsync(nd.bOverlap, 0, ob, stream));
+      bool any = false;
+      for (int c = 0; c < nd.bInCh && h > 0; c++) {   // the row of a slot that reads input channel c
+        const ConvRowRef& rr = nd.convRows[nd.isTrueStereo ? 2 * c : c];
+        const ConvGroup& g = *rr.group;
+        if (g.histZero || !g.histR) continue;
+        GA_HIP(hipMemcpy2DAsync(nd.bHistR + c * hstride, 4, g.histR + rr.idx, (size_t)g.rp * 4, 4, (size_t)kBins * h, hipMemcpyDeviceToDevice, stream));
+        GA_HIP(hipMemcpy2DAsync(nd.bHistI + c * hstride, 4, g.histI + rr.idx, (size_t)g.rp * 4, 4, (size_t)kBins * h, hipMemcpyDeviceToDevice, stream));
+        any = true;
+      }
+      for (int slot = 0; slot < nd.bSlots && slot < (int)nd.convRows.size(); slot++) {
+        const ConvRowRef& rr = nd.convRows[slot];
+        ConvGroup& g = *rr.group;
+        if (g.overlap[g.ovCur] && !g.histZero) {
+          GA_HIP(hipMemcpyAsync(nd.bOverlap + (size_t)slot * 2 * kBlock, g.overlap[g.ovCur] + (size_t)rr.idx * kBlock, kBlock * 4, hipMemcpyDeviceToDevice, stream));
+          any = true;
+        }
+        g.rows[rr.idx] = {-1, 0};   // (released as moveRows releases them)
+      }
+      nd.convRows.clear();
+      nd.bShared = false;
+      nd.bHistZero = !any;
+      nd.bHistPlane = -1;
+      nd.bOvCur = 0;
+      nd.convPath = 2;   // (P <= 64, or no block-axis transforms: formulation A is never taken where C would be)
+      stats.conv_migrations++;
+      continue;
+    }
+    ConvMigration mg{};
+    mg.id = id;
+    const int nxr = nd.bShared ? 1 : nd.bInCh;   // (bInCh / bSlots / bShared carry over: both layouts define them alike)
+    bool any = false;
+    for (int ch = 0; ch < nxr && ch < 32; ch++) {
+      const float* h = coarseHistory(nd, ch);
+      mg.src[ch] = h ? h + conv_rebuild_src_offset(nd.dHistLen, P) : nullptr;
+      any = any || h != nullptr;
+    }
+    const size_t hb = (size_t)nd.bInCh * kBins * std::max(P - 1, 1) * sizeof(float);
+    const size_t ob = (size_t)nd.bSlots * 2 * kBlock * sizeof(float);
+    nd.bHistR = (float*)dalloc(hb);
+    nd.bHistI = (float*)dalloc(hb);
+    nd.bOverlap = (float*)dalloc(ob);
+    GA_HIP(hipMemsetAsync(nd.bHistR, 0, hb, stream));
+    GA_HIP(hipMemsetAsync(nd.bHistI, 0, hb, stream));
+    GA_HIP(hipMemsetAsync(nd.bOverlap, 0, ob, stream));
+    nd.bHistZero = !any;   // (nothing in front of the chunk yet: an empty delay line, no launch)
+    nd.bHistPlane = -1;
+    nd.bOvCur = 0;
+    nd.convPath = (useTimeFft && P > 64 && P <= 1024) ? 3 : 2;   // (the rule of assignConvPaths)
+    for (int b = 0; b < 2; b++) {
+      if (nd.dHistBase[b]) retired.push_back({nd.dHistBase[b], nd.dHistBytes});
+      if (nd.dTail[b]) retired.push_back({nd.dTail[b], (size_t)nd.dTailLen * nd.dTailCh * sizeof(float)});
+      nd.dHistBase[b] = nullptr;
+      nd.dHist[b] = nd.dTail[b] = nullptr;
+    }
+    nd.dHistExt.clear();   // (a buffer it referred to is released behind a stream wait: Context::collectGarbage)
+    nd.dHistBytes = 0;
+    nd.dHistLen = 0;
+    nd.dHistCur = 0;
+    nd.dHistZero = true;
+    nd.dTailLen = 0;
+    nd.dTailCh = nd.dTailCur = 0;
+    nd.dTailSig = 0;
+    nd.dTailSeq = ~0ull - 1;
+    nd.dLeader = -1;
+    nd.dGroupSize = 0;
+    fusionKeyValid = false;
+    stats.conv_migrations++;
+    if (any) convMigrations.push_back(mg);
+  }
+}
+
+// The rebuild of every node that leaves formulation D in this chunk, in three launches whatever their number: conv_rebuild_kernel
+// (job = input channel), then block T-1 alone through R's own partition sum and inverse transform on scratch planes -- an
+// overlap-in of zeros (the overlap-add touches the first half only) and no output row; what it leaves is the overlap the chunk's
+// first block reads.  Plan entries: ordered with the chunk's launches, no host wait.
+void Context::planConvMigration(ChunkRun& r) {
+  Exec& ex = *r.ex;
+  const std::vector<ConvMigration> all = std::move(convMigrations);
+  convMigrations.clear();
+  std::vector<const ConvMigration*> mine;
+  int maxP = 1;
+  for (const ConvMigration& mg : all) {
+    mine.push_back(&mg);
+    maxP = std::max(maxP, rec<ConvolverS>(*nodes[mg.id]).ir->P);
+  }
+  const int hist = conv_rebuild_hist(maxP), tx = conv_rebuild_tx(maxP), ty = kRebuildTy;
+  std::vector<ConvRebuildJob> jobs;
+  std::vector<ConvSetB> sets;
+  std::vector<ConvRowIO> yrows;
+  std::vector<const float*> ovIn;
+  std::vector<float*> ovOut;
+  double flops = 0;
+  for (const ConvMigration* mg : mine) {
+    ConvolverS& nd = rec<ConvolverS>(*nodes[mg->id]);
+    const int P = nd.ir->P;
+    const size_t hstride = (size_t)kBins * std::max(P - 1, 1);
+    const int nxr = nd.bShared ? 1 : nd.bInCh;
+    const int x0 = (int)jobs.size();
+    for (int ch = 0; ch < nxr; ch++) jobs.push_back(ConvRebuildJob{mg->src[ch], nd.bHistR + ch * hstride, nd.bHistI + ch * hstride, P, x0 + ch});
+    for (int xc = 0; xc < nxr; xc++) {   // sets as planConvolversPrivate makes them: columns by the x-row they read, 16 per set
+      std::vector<int> cols;
+      for (int slot = 0; slot < nd.bSlots; slot++)
+        if (nd.bShared || conv_slot_input(nd.isTrueStereo, slot) == xc) cols.push_back(slot);
+      for (size_t c0 = 0; c0 < cols.size(); c0 += 16) {
+        ConvSetB st{};
+        st.x = x0 + xc;
+        st.y0 = (int)yrows.size();
+        st.ncol = (int)std::min<size_t>(16, cols.size() - c0);
+        st.P = P;
+        for (int j = 0; j < st.ncol; j++) {
+          const int slot = cols[c0 + j];
+          st.hr[j] = nd.ir->hr + (size_t)slot * kBins * P;
+          st.hi[j] = nd.ir->hi + (size_t)slot * kBins * P;
+          yrows.push_back(ConvRowIO{nullptr, nullptr});
+          ovIn.push_back(zeros);
+          ovOut.push_back(nd.bOverlap + ((size_t)slot * 2 + nd.bOvCur) * kBlock);
+        }
+        sets.push_back(st);
+      }
+    }
+    flops += 8.0 * P * kBins * (double)nd.bSlots;
+  }
+  // scratch planes of this chunk alone: freed with the retire list, after the stream has run the launches below
+  const size_t xb = jobs.size() * kBins * (size_t)tx * sizeof(float), yb = yrows.size() * kBins * (size_t)ty * sizeof(float);
+  float* scratch = (float*)dalloc(2 * xb + 2 * yb);
+  retired.push_back({scratch, 2 * xb + 2 * yb});
+  ConvPlanesB plb{scratch, scratch + xb / sizeof(float), scratch + 2 * xb / sizeof(float), scratch + (2 * xb + yb) / sizeof(float), tx, ty};
+  const size_t jo = ex.plan.putv(jobs), so = ex.plan.putv(sets), yo = ex.plan.putv(yrows), oi = ex.plan.putv(ovIn), oo = ex.plan.putv(ovOut);
+  const int nj = (int)jobs.size(), ns_ = (int)sets.size(), ny = (int)yrows.size();
+  hipStream_t st = stream;
+  Twiddles tw{w128, w256};
+  Context* cp = this;
+  ex.plan.add(LK_FFT, [=](uint8_t* base) {
+    GA_HIP(hipMemsetAsync(scratch, 0, 2 * xb, st));   // (columns in front of a shorter node's first block)
+    launch_conv_rebuild(st, (const ConvRebuildJob*)(base + jo), nj, maxP, plb, hist, tw);
+    cp->noteKernel(LK_FFT, "conv_rebuild_kernel");
+  });
+  ex.plan.add(LK_MAC, [=](uint8_t* base) {
+    launch_refmac(st, (const ConvSetB*)(base + so), ns_, 1, hist, plb);
+    cp->noteKernel(LK_MAC, "refmac_kernel");
+  }, 0.0, flops);
+  ex.plan.add(LK_FFT, [=](uint8_t* base) {
+    launch_irfft_ola_b(st, (const ConvRowIO*)(base + yo), ny, 1, plb, (const float* const*)(base + oi), (float* const*)(base + oo), tw, true);
+  });
+}
+
 // pass 5: convolver formulations of new nodes, fusion groups, scratch arenas (sized before any recorded launch captures them)
 void Context::chunkConvScratch(ChunkRun& r) {
   std::vector<int>& topo = r.topo;
@@ -849,6 +1028,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
   //      launch captures their address ----
   if (topoHasConvolvers && r.stage != 1) {   // (no convolver in the first stage of a two-stage chunk: chunkTopology) (a graph without convolvers -- tens of thousands of nodes of config 4 -- skips these sweeps)
     refOrderSensitivity(topo);
+    migrateConvolvers(topo);   // (option "conv_migrate": before the paths, the fusion groups and the scratch sizes are decided)
     assignConvPaths(topo, n);
     for (int id : topo) {
       if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
@@ -1335,6 +1515,9 @@ void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
   Exec& ex = *r.ex;
   // ---- convolvers whose inputs are complete (depth d): once per chunk over all blocks ----
   // group -> (node, slot); ordered by (IR buffer, IR channel) so groups fed by the same inputs are adjacent
+  // (option "conv_migrate": the state of the nodes that left formulation D in this chunk is a function of earlier chunks' input alone --
+  // rebuilt in front of the first convolver stage, for every depth at once)
+  if (!convMigrations.empty()) planConvMigration(r);
   ConvPlanCtx k;
   auto& active = k.active;
   std::vector<int>& bNodes = k.bNodes;  // formulation B / C nodes of this depth

@@ -148,6 +148,15 @@ typedef struct ga_stats {
   int64_t delay_flags_predicted; /* (DelayNode, chunk) pairs whose output flag rose by the host's prediction while the option was on: a
                                     delay behind another undecided delay, a modulated playbackRate or a convolver, and with value 1 a
                                     delay on a feedback loop */
+  int64_t conv_migrations;      /* option "conv_migrate" (ga_set_option; 0 = off, the default; 1 = on; any other value is
+                                   GA_ERR_OUT_OF_RANGE): ConvolverNodes that were running on formulation D (coarse partitions) or A
+                                   (shared-IR groups) when an edit made them sensitive (a consumer that amplifies or quantises
+                                   last-bit differences, see ref_order_rows) and were moved to the B / C state layout, which
+                                   formulation R shares.  From D the spectra history and the overlap are rebuilt from the node's
+                                   input history: from the migrating chunk on the output is bit-identical to that of a node that
+                                   was on R from its first block.  From A the state is copied: the same holds from block P behind
+                                   the move on (P = partitions), inside the convolver tolerance until then.  One way: the node never
+                                   returns to A or D, which is why the option is off by default */
 } ga_stats;
 enum {
   GA_STAGE_OTHER = 0,        /* sources, biquads, gains, parameter curves, ... */
