@@ -1,6 +1,6 @@
 // ga_conv_rebuild.hpp -- index arithmetic of the convolver migration (option "conv_migrate"): a node leaves formulation D
 // for the B / C / R state layout and its spectra history is rebuilt from D's input history.  Plain C++: the kernel, the planner and
-// the stand-alone host check (tools/check_conv_rebuild.cpp) share these functions.
+// the stand-alone host check (tests/conv_rebuild_main.cpp) share these functions.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -2,8 +2,7 @@
 //
 // Reference semantics each kernel reproduces are cited as (file:line) of the-byte-bender/GraphAudio.
 // Design notes (DESIGN.md has the full account):
-//  * wavefront = 64 lanes everywhere; one 256-point real FFT per wavefront, two complex points per lane,
-//    radix-2 butterflies exchanged with wave shuffles, double precision like the reference's FftFlat.
+//  * wavefront = 64 lanes everywhere; the 256-point real FFT (one per wavefront) and its five kernels live in ga_rfft.hip.
 //  * the spectral multiply-accumulate runs over ALL blocks of a render chunk at once: for one frequency bin it is
 //    a banded-Toeplitz GEMM  Y[rows x time] = X[rows x time'] * T(H)  executed on the f32 matrix cores
 //    (v_mfma_f32_16x16x4_f32, exact f32 fma chain), rows = convolver channel-instances sharing one IR channel.
@@ -31,312 +30,7 @@ constexpr int kMaxGridY = 32768;
   for (int j0_ = 0; j0_ < (njobs_); j0_ += kMaxGridY)                                                                \
     hipLaunchKernelGGL(kernel, dim3((gx_), std::min(kMaxGridY, (njobs_) - j0_)), dim3(block_), 0, s, (jobs_) + j0_, ##__VA_ARGS__)
 
-// phase timestamps for tools/micro/rfft_phase.hip (compiled out of the product)
-#ifdef GA_EXP_TIMELINE
-__device__ unsigned long long* ga_tl = nullptr;
-#define GA_TL(i) do { if (ga_tl && threadIdx.x == 0) ga_tl[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define GA_TL(i) do { } while (0)
-#endif
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// =====================================================================================================
-//  256-point real FFT on one wavefront (forward: RealFourierTransform.cs:62-88; inverse: :101-131), double precision.
-//  z[n] = x[2n] + i x[2n+1] (n < 128); lane l owns z[l] (slot 0) and z[l+64] (slot 1).  One in-lane radix-2 stage
-//  and six cross-lane stages; the cross-lane exchanges are DPP moves (xor 1,2,4,8), ds_swizzle (xor 16) and one
-//  ds_bpermute (xor 32) -- no LDS storage, no barriers.  Butterflies are select-free: every lane evaluates
-//  d = fma(sigma, mine, partner) followed by one complex multiply whose twiddle is (1, 0) on the "lower" lanes.
-//  Each wavefront keeps FFT_ILP independent transforms in flight to hide the exchange latency.
-// =====================================================================================================
-template <int MASK>
-__device__ __forceinline__ int xchg32(int v) {
-  if constexpr (MASK == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);           // quad_perm [1,0,3,2]
-  else if constexpr (MASK == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
-  else if constexpr (MASK == 4) {                                                                // xor 7 then xor 3
-    int t = __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);                                  // row_half_mirror
-    return __builtin_amdgcn_mov_dpp(t, 0x1B, 0xF, 0xF, true);                                    // quad_perm [3,2,1,0]
-  } else if constexpr (MASK == 8) {                                                              // xor 15 then xor 7
-    int t = __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);                                  // row_mirror
-    return __builtin_amdgcn_mov_dpp(t, 0x141, 0xF, 0xF, true);
-  } else if constexpr (MASK == 16) return __builtin_amdgcn_ds_swizzle(v, 0x401F);                // bit mode: xor 0x10
-  else return __shfl_xor(v, MASK, 64);
-}
-template <int MASK>
-__device__ __forceinline__ double xchg(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  return __hiloint2double(xchg32<MASK>(hi), xchg32<MASK>(lo));
-}
-template <int MASK>
-__device__ __forceinline__ float xchg(float v) { return __int_as_float(xchg32<MASK>(__float_as_int(v))); }
-__device__ __forceinline__ double shfl_d(double v, int src) { return __shfl(v, src, 64); }
-__device__ __forceinline__ float shfl_d(float v, int src) { return __shfl(v, src, 64); }
-__device__ __forceinline__ int rev6(int l) { return (int)(__brev((unsigned)l) >> 26); }
-
-// T = double reproduces the reference's double-precision FftFlat transform (spectra equal after the float32 cast with
-// overwhelming probability); T = float is the default fast path: the transform error (~1e-7 relative) stays an order of
-// magnitude inside the float32 accumulation noise of the partition sum that follows.
-template <class T>
-struct LaneTwT {   // per-lane constants, loaded once per kernel
-  T c[6], s[6];    // stage twiddle for half = 32,16,8,4,2,1: W128^{(l & (half-1)) * 64/half} on upper lanes, (1,0) on lower
-  T sg[6];         // -1 on upper lanes (l & half), +1 on lower lanes
-  T c1, s1;        // W128^l  (the in-lane stage)
-};
-using LaneTw = LaneTwT<double>;
-template <class T>
-__device__ __forceinline__ LaneTwT<T> load_lane_tw_t(const double2* __restrict w128, int lane) {
-  LaneTwT<T> t;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    int half = 32 >> i;
-    bool up = (lane & half) != 0;
-    double2 w = w128[(lane & (half - 1)) * (64 / half)];
-    t.c[i] = up ? (T)w.x : (T)1.0;
-    t.s[i] = up ? (T)w.y : (T)0.0;
-    t.sg[i] = up ? (T)-1.0 : (T)1.0;
-  }
-  double2 w = w128[lane];
-  t.c1 = (T)w.x;
-  t.s1 = (T)w.y;
-  return t;
-}
-__device__ __forceinline__ LaneTw load_lane_tw(const double2* __restrict w128, int lane) { return load_lane_tw_t<double>(w128, lane); }
-// decimation in frequency: lower <- a + b ; upper <- (a - b) W   (natural order in, bit-reversed out)
-template <int HALF, int IDX, class T>
-__device__ __forceinline__ void dif_stage(T& ar, T& ai, const LaneTwT<T>& t) {
-  T pr = xchg<HALF>(ar), pi = xchg<HALF>(ai);
-  T dr = fma(t.sg[IDX], ar, pr), di = fma(t.sg[IDX], ai, pi);   // lower: mine + partner ; upper: partner - mine
-  ar = fma(dr, t.c[IDX], -(di * t.s[IDX]));
-  ai = fma(dr, t.s[IDX], di * t.c[IDX]);
-}
-// decimation in time with conjugated twiddles: lower <- a + b conj(W) ; upper <- a - b conj(W)  (bit-reversed in, natural out)
-template <int HALF, int IDX, class T>
-__device__ __forceinline__ void dit_stage(T& ar, T& ai, const LaneTwT<T>& t) {
-  T qr = fma(ar, t.c[IDX], ai * t.s[IDX]);       // mine * conj(tw)   (tw = (1,0) on lower lanes)
-  T qi = fma(ai, t.c[IDX], -(ar * t.s[IDX]));
-  T pr = xchg<HALF>(qr), pi = xchg<HALF>(qi);
-  ar = fma(t.sg[IDX], qr, pr);                   // lower: a + q_partner ; upper: partner - q_mine
-  ai = fma(t.sg[IDX], qi, pi);
-}
-
-constexpr int FFT_ROWS = 32;        // rows (channel-instances) per workgroup
-constexpr int STAGE_LD = 132;       // staging tile is [row][bin], bins fastest, 129 padded to 132 floats
-constexpr int FFT_ILP = 4;          // independent transforms in flight per wavefront
-
-// ---- forward ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rfft_fwd_kernel(const ConvRowIO* __restrict rows, int nrows, int nblocks, int hist,
-                                                       ConvPlanes pl, Twiddles tw) {
-  __shared__ float st_r[FFT_ROWS * STAGE_LD];
-  __shared__ float st_i[FFT_ROWS * STAGE_LD];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rowtile = blockIdx.x;
-  const int t = blockIdx.y;
-  const LaneTw ltw = load_lane_tw(tw.w128, lane);
-  // after the DIF stages slot j of lane l holds Z[k], k = 2 m + j, m = rev6(l).  X[k] needs Z[128 - k]:
-  //   j = 0: index 2 ((64 - m) & 63) -> lane rev6((64 - m) & 63) ; j = 1: index 2 (63 - m) + 1 -> lane 63 - l
-  const int m = rev6(lane);
-  const int k0 = 2 * m, k1 = 2 * m + 1;
-  const int src0 = rev6((64 - m) & 63), src1 = 63 - lane;
-  const double2 wk0 = tw.w256[k0];
-  const double2 wk1 = tw.w256[k1];
-
-  for (int q0 = 0; q0 < FFT_ROWS / 4; q0 += FFT_ILP) {
-    double s0r[FFT_ILP], s0i[FFT_ILP], s1r[FFT_ILP], s1i[FFT_ILP];
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) {
-      const int row = rowtile * FFT_ROWS + wave * (FFT_ROWS / 4) + q0 + u;
-      const float* in = row < nrows ? rows[row].in : nullptr;
-      s0r[u] = 0.0;
-      s0i[u] = 0.0;
-      if (in) {
-        const GA_GLOBAL float* p = gptr(in) + (int64_t)t * kBlock + 2 * lane;
-        s0r[u] = (double)p[0];     // float -> double, PartitionedConvolver.cs:106
-        s0i[u] = (double)p[1];
-      }
-      // in-lane stage with the zero upper half (PartitionedConvolver.cs:107): (a + 0, (a - 0) * W128^l)
-      s1r[u] = fma(s0r[u], ltw.c1, -(s0i[u] * ltw.s1));
-      s1i[u] = fma(s0r[u], ltw.s1, s0i[u] * ltw.c1);
-    }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<32, 0>(s0r[u], s0i[u], ltw); dif_stage<32, 0>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<16, 1>(s0r[u], s0i[u], ltw); dif_stage<16, 1>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<8, 2>(s0r[u], s0i[u], ltw); dif_stage<8, 2>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<4, 3>(s0r[u], s0i[u], ltw); dif_stage<4, 3>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<2, 4>(s0r[u], s0i[u], ltw); dif_stage<2, 4>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) { dif_stage<1, 5>(s0r[u], s0i[u], ltw); dif_stage<1, 5>(s1r[u], s1i[u], ltw); }
-    // real-FFT split: X[k] = E[k] + W256^k * (-i) * D[k],  E = (Z[k] + conj Z[128-k]) / 2,  D = (Z[k] - conj Z[128-k]) / 2
-#pragma unroll
-    for (int u = 0; u < FFT_ILP; u++) {
-      const int rl = wave * (FFT_ROWS / 4) + q0 + u;
-      {
-        double ax = s0r[u], ay = s0i[u];
-        double bx = shfl_d(ax, src0), by = shfl_d(ay, src0);
-        double er = 0.5 * (ax + bx), ei = 0.5 * (ay - by);
-        double dr = 0.5 * (ax - bx), di = 0.5 * (ay + by);
-        double pr = fma(dr, wk0.x, -(di * wk0.y)), pi = fma(dr, wk0.y, di * wk0.x);
-        float xr = (float)(er + pi), xi = (float)(ei - pr);   // double -> float, PartitionedConvolver.cs:117-118
-        if (k0 == 0) {  // lane 0: DC, plus Nyquist X[128] = Re Z[0] - Im Z[0]; both purely real (RealFourierTransform.cs:76-78)
-          xi = 0.f;
-          st_r[rl * STAGE_LD + 128] = (float)(ax - ay);
-          st_i[rl * STAGE_LD + 128] = 0.f;
-        }
-        st_r[rl * STAGE_LD + k0] = xr;
-        st_i[rl * STAGE_LD + k0] = xi;
-      }
-      {
-        double ax = s1r[u], ay = s1i[u];
-        double bx = shfl_d(ax, src1), by = shfl_d(ay, src1);
-        double er = 0.5 * (ax + bx), ei = 0.5 * (ay - by);
-        double dr = 0.5 * (ax - bx), di = 0.5 * (ay + by);
-        double pr = fma(dr, wk1.x, -(di * wk1.y)), pi = fma(dr, wk1.y, di * wk1.x);
-        st_r[rl * STAGE_LD + k1] = (float)(er + pi);
-        st_i[rl * STAGE_LD + k1] = (float)(ei - pr);
-      }
-    }
-  }
-  __syncthreads();
-  // coalesced 16-byte stores: 8 lanes cover the 32 consecutive rows (one 128-byte line) of one bin
-  const size_t plane_t = (size_t)pl.tx * pl.rp;
-  const size_t base = (size_t)(hist + t) * pl.rp + (size_t)rowtile * FFT_ROWS;
-  for (int idx = tid; idx < kBins * (FFT_ROWS / 4); idx += 256) {
-    int k = idx / (FFT_ROWS / 4), r4 = (idx % (FFT_ROWS / 4)) * 4;
-    size_t o = (size_t)k * plane_t + base + r4;
-    float4 vr = make_float4(st_r[(r4 + 0) * STAGE_LD + k], st_r[(r4 + 1) * STAGE_LD + k], st_r[(r4 + 2) * STAGE_LD + k], st_r[(r4 + 3) * STAGE_LD + k]);
-    float4 vi = make_float4(st_i[(r4 + 0) * STAGE_LD + k], st_i[(r4 + 1) * STAGE_LD + k], st_i[(r4 + 2) * STAGE_LD + k], st_i[(r4 + 3) * STAGE_LD + k]);
-    *reinterpret_cast<float4*>(pl.xr + o) = vr;
-    *reinterpret_cast<float4*>(pl.xi + o) = vi;
-  }
-}
-
-void launch_rfft_fwd(hipStream_t s, const ConvRowIO* rows_dev, int nrows, int nblocks, int hist, ConvPlanes pl, Twiddles tw) {
-  if (nrows <= 0 || nblocks <= 0) return;
-  dim3 grid((nrows + FFT_ROWS - 1) / FFT_ROWS, nblocks);
-  hipLaunchKernelGGL(rfft_fwd_kernel, grid, dim3(256), 0, s, rows_dev, nrows, nblocks, hist, pl, tw);
-}
-
-// ---- inverse + overlap-add ----------------------------------------------------------------------------
-constexpr int OLA_RUN = 16;   // consecutive blocks per workgroup (one extra inverse FFT recovers the incoming tail)
-
-__global__ __launch_bounds__(256) void irfft_ola_kernel(const ConvRowIO* __restrict rows, int nrows, int nblocks, ConvPlanes pl,
-                                                        const float* __restrict overlap_in, float* __restrict overlap_out, Twiddles tw) {
-  __shared__ float ys_r[FFT_ROWS * STAGE_LD];
-  __shared__ float ys_i[FFT_ROWS * STAGE_LD];
-  __shared__ float tail[FFT_ROWS][kBlock];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rowtile = blockIdx.x;
-  const int ta = blockIdx.y * OLA_RUN;
-  const int tb = min(ta + OLA_RUN, nblocks);
-  const LaneTw ltw = load_lane_tw(tw.w128, lane);
-  const int k0 = rev6(lane) << 1, k1 = k0 | 1;
-  const double2 wk0 = tw.w256[k0];
-  const double2 wk1 = tw.w256[k1];
-  const size_t plane_t = (size_t)pl.ty * pl.rp;
-
-  if (ta == 0) {  // incoming overlap of the chunk's first block = persistent _overlap (PartitionedConvolver.cs:28,148-149)
-    for (int idx = tid; idx < FFT_ROWS * kBlock; idx += 256) {
-      int r = idx / kBlock, i = idx % kBlock;
-      int row = rowtile * FFT_ROWS + r;
-      tail[r][i] = row < nrows ? overlap_in[(size_t)row * kBlock + i] : 0.f;
-    }
-  }
-  for (int t = (ta == 0 ? 0 : ta - 1); t < tb; t++) {
-    const bool pre = t < ta;   // only recompute block ta-1 to obtain its second half
-    __syncthreads();
-    const size_t base = (size_t)t * pl.rp + (size_t)rowtile * FFT_ROWS;
-    for (int idx = tid; idx < kBins * (FFT_ROWS / 4); idx += 256) {   // 16-byte loads, 8 lanes per 128-byte bin line
-      int k = idx / (FFT_ROWS / 4), r4 = (idx % (FFT_ROWS / 4)) * 4;
-      size_t o = (size_t)k * plane_t + base + r4;
-      float4 vr = *reinterpret_cast<const float4*>(pl.yr + o);
-      float4 vi = *reinterpret_cast<const float4*>(pl.yi + o);
-      ys_r[(r4 + 0) * STAGE_LD + k] = vr.x; ys_r[(r4 + 1) * STAGE_LD + k] = vr.y;
-      ys_r[(r4 + 2) * STAGE_LD + k] = vr.z; ys_r[(r4 + 3) * STAGE_LD + k] = vr.w;
-      ys_i[(r4 + 0) * STAGE_LD + k] = vi.x; ys_i[(r4 + 1) * STAGE_LD + k] = vi.y;
-      ys_i[(r4 + 2) * STAGE_LD + k] = vi.z; ys_i[(r4 + 3) * STAGE_LD + k] = vi.w;
-    }
-    __syncthreads();
-    for (int q0 = 0; q0 < FFT_ROWS / 4; q0 += FFT_ILP) {
-      double s0r[FFT_ILP], s0i[FFT_ILP], s1r[FFT_ILP], s1i[FFT_ILP];
-      // Z[k] = (X[k] + conj X[128-k]) + i conj(W256^k) (X[k] - conj X[128-k])   (float -> double, :136)
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) {
-        const int rl = wave * (FFT_ROWS / 4) + q0 + u;
-        {
-          double ar = ys_r[rl * STAGE_LD + k0], ai = ys_i[rl * STAGE_LD + k0];
-          double br = ys_r[rl * STAGE_LD + (128 - k0)], bi = -(double)ys_i[rl * STAGE_LD + (128 - k0)];
-          if (k0 == 0) { ai = 0.0; bi = 0.0; }   // rdft ignores Im of DC / Nyquist (RealFourierTransform.cs:120-123)
-          double er = ar + br, ei = ai + bi, dr = ar - br, di = ai - bi;
-          double pr = fma(dr, wk0.x, di * wk0.y), pi = fma(di, wk0.x, -(dr * wk0.y));   // d * conj(w)
-          s0r[u] = er - pi;
-          s0i[u] = ei + pr;
-        }
-        {
-          double ar = ys_r[rl * STAGE_LD + k1], ai = ys_i[rl * STAGE_LD + k1];
-          double br = ys_r[rl * STAGE_LD + (128 - k1)], bi = -(double)ys_i[rl * STAGE_LD + (128 - k1)];
-          double er = ar + br, ei = ai + bi, dr = ar - br, di = ai - bi;
-          double pr = fma(dr, wk1.x, di * wk1.y), pi = fma(di, wk1.x, -(dr * wk1.y));
-          s1r[u] = er - pi;
-          s1i[u] = ei + pr;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<1, 5>(s0r[u], s0i[u], ltw); dit_stage<1, 5>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<2, 4>(s0r[u], s0i[u], ltw); dit_stage<2, 4>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<4, 3>(s0r[u], s0i[u], ltw); dit_stage<4, 3>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<8, 2>(s0r[u], s0i[u], ltw); dit_stage<8, 2>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<16, 1>(s0r[u], s0i[u], ltw); dit_stage<16, 1>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) { dit_stage<32, 0>(s0r[u], s0i[u], ltw); dit_stage<32, 0>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < FFT_ILP; u++) {
-        const int rl = wave * (FFT_ROWS / 4) + q0 + u;
-        const int row = rowtile * FFT_ROWS + rl;
-        // in-lane stage: z[l] = s0 + s1 conj(W128^l), z[l+64] = s0 - s1 conj(W128^l); scale 2/n * 1/2 (:46,129)
-        double qr = fma(s1r[u], ltw.c1, s1i[u] * ltw.s1), qi = fma(s1i[u], ltw.c1, -(s1r[u] * ltw.s1));
-        const double scale = 1.0 / 256.0;
-        double h0 = (s0r[u] + qr) * scale, h1 = (s0i[u] + qi) * scale;   // time samples 2l, 2l+1
-        double g0 = (s0r[u] - qr) * scale, g1 = (s0i[u] - qi) * scale;   // time samples 128+2l, 128+2l+1
-        if (row < nrows) {
-          if (!pre) {
-            float* out = rows[row].out;
-            float o0 = (float)h0 + tail[rl][2 * lane];        // (float)y[i] + overlap[i]  (:148)
-            float o1 = (float)h1 + tail[rl][2 * lane + 1];
-            if (out) {
-              *reinterpret_cast<GA_GLOBAL v2f*>(gptr(out) + (int64_t)t * kBlock + 2 * lane) = v2f{o0, o1};
-            }
-          }
-          tail[rl][2 * lane] = (float)g0;                      // overlap[i] = (float)y[i + 128]  (:149)
-          tail[rl][2 * lane + 1] = (float)g1;
-        }
-      }
-    }
-  }
-  if (tb == nblocks) {
-    __syncthreads();
-    for (int idx = tid; idx < FFT_ROWS * kBlock; idx += 256) {
-      int r = idx / kBlock, i = idx % kBlock;
-      int row = rowtile * FFT_ROWS + r;
-      if (row < nrows) overlap_out[(size_t)row * kBlock + i] = tail[r][i];
-    }
-  }
-}
-
-void launch_irfft_ola(hipStream_t s, const ConvRowIO* rows_dev, int nrows, int nblocks, ConvPlanes pl, const float* overlap_in,
-                      float* overlap_out, Twiddles tw) {
-  if (nrows <= 0 || nblocks <= 0) return;
-  dim3 grid((nrows + FFT_ROWS - 1) / FFT_ROWS, (nblocks + OLA_RUN - 1) / OLA_RUN);
-  hipLaunchKernelGGL(irfft_ola_kernel, grid, dim3(256), 0, s, rows_dev, nrows, nblocks, pl, overlap_in, overlap_out, tw);
-}
 
 // =====================================================================================================
 //  Shared-IR spectral multiply-accumulate on the f32 matrix cores.
@@ -526,256 +220,6 @@ void launch_spectral_mac_shared(hipStream_t s, ConvPlanes pl, const float* hr, c
   int total = kBins * ntt * nrt;
   int grid = ((total + 7) / 8) * 8;
   hipLaunchKernelGGL(spectral_mac_shared_kernel, dim3(grid), dim3(256), 0, s, pl, hr, hi, P, ntt, nrt, total);
-}
-
-// =====================================================================================================
-//  Formulation B kernels (see ga_kernels.hpp): planes [row][bin][block], block index fastest.
-// =====================================================================================================
-constexpr int FB_RUN = 32;            // blocks per workgroup in the B-layout FFT kernels: 32 blocks = one 128-byte line per bin
-// Staging tile [block][bin] in LDS (64 banks of 4 bytes).  A lane of the 128-point transforms owns bins (2m, 2m + 1) with
-// m = rev6(lane) and needs their mirrors (128 - 2m, 127 - 2m): with the bins in natural order every one of those accesses
-// is a 2-way bank conflict (64 lanes on the even or the odd banks only).  So a column keeps its even bins packed in
-// E[0..64] (bin 2e at e) and its odd bins in O[0..63] (bin 2o + 1 at FB_OB + o): all four accesses become 4-byte operations
-// whose 64 lanes hit 64 different banks (m, 64 - m, FB_OB + m, FB_OB + 63 - m are permutations of the banks).
-// FB_OB == 4 (mod 8) and FB_KP == 18 (mod 64) keep the transposed side conflict-free too: a wave covers 8 consecutive bins
-// (banks b..b+3 from E, b+4..b+7 from O) of 8 columns 4 apart (4 * FB_KP == 8 mod 64).
-constexpr int FB_OB = 68;
-constexpr int FB_KP = 146;
-__device__ __forceinline__ int fb_pos(int k) { return (k & 1) * FB_OB + (k >> 1); }
-
-// forward: workgroup = (x-row, run of 32 blocks); wave w transforms blocks w, w+4, ..., w+28 of the run, 4 in flight
-template <class T>
-__global__ __launch_bounds__(256) void rfft_fwd_b_kernel(const ConvRowIO* __restrict xrows, int nx, int nblocks, int hist,
-                                                         ConvPlanesB pl, Twiddles tw, int row0) {
-  // staging tile [block of the run][bin] in the even/odd layout described at FB_KP
-  __shared__ __attribute__((aligned(16))) float st_r[FB_RUN * FB_KP];
-  __shared__ __attribute__((aligned(16))) float st_i[FB_RUN * FB_KP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // consecutive workgroups take consecutive runs of ONE row: their 128-byte pieces of every bin line are adjacent in HBM
-  const int xrow = row0 + blockIdx.y;
-  const int t0 = blockIdx.x * FB_RUN;
-  const LaneTwT<T> ltw = load_lane_tw_t<T>(tw.w128, lane);
-  const int m = rev6(lane);
-  const int k0 = 2 * m, k1 = 2 * m + 1;
-  const int src0 = rev6((64 - m) & 63), src1 = 63 - lane;
-  const T wk0x = (T)tw.w256[k0].x, wk0y = (T)tw.w256[k0].y;
-  const T wk1x = (T)tw.w256[k1].x, wk1y = (T)tw.w256[k1].y;
-  const GA_GLOBAL float* in = gptr(xrows[xrow].in);
-  GA_TL(0);
-
-  // all eight input blocks of this wave are requested up front: their HBM latency overlaps the first batch of transforms
-  float inr[FB_RUN / 4], ini[FB_RUN / 4];
-#pragma unroll
-  for (int q = 0; q < FB_RUN / 4; q++) {
-    const int t = t0 + wave + 4 * q;
-    inr[q] = 0.f;
-    ini[q] = 0.f;
-    if (in && t < nblocks) {
-      const GA_GLOBAL float* p = in + (int64_t)t * kBlock + 2 * lane;
-      inr[q] = p[0];
-      ini[q] = p[1];
-    }
-  }
-#pragma unroll
-  for (int bq = 0; bq < FB_RUN / 16; bq++) {
-    T s0r[4], s0i[4], s1r[4], s1i[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      s0r[u] = (T)inr[bq * 4 + u];   // float -> T, PartitionedConvolver.cs:106
-      s0i[u] = (T)ini[bq * 4 + u];
-      s1r[u] = fma(s0r[u], ltw.c1, -(s0i[u] * ltw.s1));
-      s1i[u] = fma(s0r[u], ltw.s1, s0i[u] * ltw.c1);
-    }
-#ifndef GA_EXP_SKIP_FFT
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<32, 0>(s0r[u], s0i[u], ltw); dif_stage<32, 0>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<16, 1>(s0r[u], s0i[u], ltw); dif_stage<16, 1>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<8, 2>(s0r[u], s0i[u], ltw); dif_stage<8, 2>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<4, 3>(s0r[u], s0i[u], ltw); dif_stage<4, 3>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<2, 4>(s0r[u], s0i[u], ltw); dif_stage<2, 4>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<1, 5>(s0r[u], s0i[u], ltw); dif_stage<1, 5>(s1r[u], s1i[u], ltw); }
-#endif
-
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int tl = wave + 4 * (bq * 4 + u);   // block within the run
-      float x0r, x0i;
-      {
-        T ax = s0r[u], ay = s0i[u];
-        T bx = shfl_d(ax, src0), by = shfl_d(ay, src0);
-        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
-        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
-        T pr = fma(dr, wk0x, -(di * wk0y)), pi = fma(dr, wk0y, di * wk0x);
-        float xr = (float)(er + pi), xi = (float)(ei - pr);
-        if (k0 == 0) {
-          xi = 0.f;
-          st_r[tl * FB_KP + 64] = (float)(ax - ay);   // bin 128 = E[64]
-          st_i[tl * FB_KP + 64] = 0.f;
-        }
-        x0r = xr;
-        x0i = xi;
-      }
-      {
-        T ax = s1r[u], ay = s1i[u];
-        T bx = shfl_d(ax, src1), by = shfl_d(ay, src1);
-        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
-        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
-        T pr = fma(dr, wk1x, -(di * wk1y)), pi = fma(dr, wk1y, di * wk1x);
-        st_r[tl * FB_KP + m] = x0r;                           // bin 2m
-        st_i[tl * FB_KP + m] = x0i;
-        st_r[tl * FB_KP + FB_OB + m] = (float)(er + pi);      // bin 2m + 1
-        st_i[tl * FB_KP + FB_OB + m] = (float)(ei - pr);
-      }
-    }
-  }
-  GA_TL(1);
-  __syncthreads();
-  GA_TL(2);
-  // store: per bin 32 consecutive blocks = 128 bytes, 8 lanes x 16 B
-  const size_t rowbase = (size_t)xrow * kBins * pl.tx + hist + t0;
-  for (int idx = tid; idx < kBins * 8; idx += 256) {
-    int k = idx >> 3, q = (idx & 7) * 4;
-    if (t0 + q >= nblocks) continue;
-    size_t o = rowbase + (size_t)k * pl.tx + q;
-#ifdef GA_EXP_CONTIG
-    o = ((size_t)(xrow * gridDim.x + blockIdx.x) * kBins + k) * 32 + q;
-#endif
-    const int pk = q * FB_KP + fb_pos(k);
-    *reinterpret_cast<float4*>(pl.xr + o) = make_float4(st_r[pk], st_r[pk + FB_KP], st_r[pk + 2 * FB_KP], st_r[pk + 3 * FB_KP]);
-    *reinterpret_cast<float4*>(pl.xi + o) = make_float4(st_i[pk], st_i[pk + FB_KP], st_i[pk + 2 * FB_KP], st_i[pk + 3 * FB_KP]);
-  }
-  GA_TL(3);
-}
-void launch_rfft_fwd_b(hipStream_t s, const ConvRowIO* xrows_dev, int nx, int nblocks, int hist, ConvPlanesB pl, Twiddles tw, bool fp64) {
-  if (nx <= 0 || nblocks <= 0) return;
-  for (int r0 = 0; r0 < nx; r0 += 65535) {   // gridDim.y limit
-    dim3 grid((nblocks + FB_RUN - 1) / FB_RUN, std::min(65535, nx - r0));
-    if (fp64) hipLaunchKernelGGL(rfft_fwd_b_kernel<double>, grid, dim3(256), 0, s, xrows_dev, nx, nblocks, hist, pl, tw, r0);
-    else hipLaunchKernelGGL(rfft_fwd_b_kernel<float>, grid, dim3(256), 0, s, xrows_dev, nx, nblocks, hist, pl, tw, r0);
-  }
-}
-
-// Option "conv_migrate": the spectra history of a convolver that leaves formulation D, rebuilt from D's input history (ga_conv_rebuild.hpp).
-// Workgroup = (job, run of 32 blocks), wave w transforms blocks w, w+4, ..., w+28 of the run, four in flight: the arithmetic of
-// rfft_fwd_b_kernel<double>, operation for operation (formulation R's forward transform: the spectra must be the floats that route
-// would have written), on a source that is a plain run of P x 128 samples.  Each value goes to the scratch plane (all P blocks: the
-// partition sum of block T-1 reads them) and to the node's [129][P-1] store (blocks T-P+1 .. T-1).
-__global__ __launch_bounds__(256) void conv_rebuild_kernel(const ConvRebuildJob* __restrict jobs, ConvPlanesB pl, int hist, Twiddles tw,
-                                                           int job0) {
-  typedef double T;
-  __shared__ __attribute__((aligned(16))) float st_r[FB_RUN * FB_KP];
-  __shared__ __attribute__((aligned(16))) float st_i[FB_RUN * FB_KP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const ConvRebuildJob* __restrict Jp = &jobs[job0 + blockIdx.y];
-  const int P = Jp->P, xrow = Jp->xrow;
-  const int t0 = blockIdx.x * FB_RUN;
-  if (t0 >= P) return;   // (uniform: the grid is sized for the longest job)
-  const LaneTwT<T> ltw = load_lane_tw_t<T>(tw.w128, lane);
-  const int m = rev6(lane);
-  const int k0 = 2 * m, k1 = 2 * m + 1;
-  const int src0 = rev6((64 - m) & 63), src1 = 63 - lane;
-  const T wk0x = (T)tw.w256[k0].x, wk0y = (T)tw.w256[k0].y;
-  const T wk1x = (T)tw.w256[k1].x, wk1y = (T)tw.w256[k1].y;
-  const GA_GLOBAL float* in = gptr(Jp->src);
-
-  float inr[FB_RUN / 4], ini[FB_RUN / 4];
-#pragma unroll
-  for (int q = 0; q < FB_RUN / 4; q++) {
-    const int t = t0 + wave + 4 * q;
-    inr[q] = 0.f;
-    ini[q] = 0.f;
-    if (in && t < P) {
-      const GA_GLOBAL float* p = in + (int64_t)t * kBlock + 2 * lane;
-      inr[q] = p[0];
-      ini[q] = p[1];
-    }
-  }
-#pragma unroll
-  for (int bq = 0; bq < FB_RUN / 16; bq++) {
-    T s0r[4], s0i[4], s1r[4], s1i[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      s0r[u] = (T)inr[bq * 4 + u];
-      s0i[u] = (T)ini[bq * 4 + u];
-      s1r[u] = fma(s0r[u], ltw.c1, -(s0i[u] * ltw.s1));
-      s1i[u] = fma(s0r[u], ltw.s1, s0i[u] * ltw.c1);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<32, 0>(s0r[u], s0i[u], ltw); dif_stage<32, 0>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<16, 1>(s0r[u], s0i[u], ltw); dif_stage<16, 1>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<8, 2>(s0r[u], s0i[u], ltw); dif_stage<8, 2>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<4, 3>(s0r[u], s0i[u], ltw); dif_stage<4, 3>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<2, 4>(s0r[u], s0i[u], ltw); dif_stage<2, 4>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-    for (int u = 0; u < 4; u++) { dif_stage<1, 5>(s0r[u], s0i[u], ltw); dif_stage<1, 5>(s1r[u], s1i[u], ltw); }
-
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int tl = wave + 4 * (bq * 4 + u);   // block within the run
-      float x0r, x0i;
-      {
-        T ax = s0r[u], ay = s0i[u];
-        T bx = shfl_d(ax, src0), by = shfl_d(ay, src0);
-        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
-        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
-        T pr = fma(dr, wk0x, -(di * wk0y)), pi = fma(dr, wk0y, di * wk0x);
-        float xr = (float)(er + pi), xi = (float)(ei - pr);
-        if (k0 == 0) {
-          xi = 0.f;
-          st_r[tl * FB_KP + 64] = (float)(ax - ay);   // bin 128 = E[64]
-          st_i[tl * FB_KP + 64] = 0.f;
-        }
-        x0r = xr;
-        x0i = xi;
-      }
-      {
-        T ax = s1r[u], ay = s1i[u];
-        T bx = shfl_d(ax, src1), by = shfl_d(ay, src1);
-        T er = (T)0.5 * (ax + bx), ei = (T)0.5 * (ay - by);
-        T dr = (T)0.5 * (ax - bx), di = (T)0.5 * (ay + by);
-        T pr = fma(dr, wk1x, -(di * wk1y)), pi = fma(dr, wk1y, di * wk1x);
-        st_r[tl * FB_KP + m] = x0r;                           // bin 2m
-        st_i[tl * FB_KP + m] = x0i;
-        st_r[tl * FB_KP + FB_OB + m] = (float)(er + pi);      // bin 2m + 1
-        st_i[tl * FB_KP + FB_OB + m] = (float)(ei - pr);
-      }
-    }
-  }
-  __syncthreads();
-  // store: a wave writes the 32 blocks of two bins -- runs of 128 bytes in the plane, and in the store where P - 1 allows
-  float* __restrict dr_ = Jp->dst_r;
-  float* __restrict di_ = Jp->dst_i;
-  for (int idx = tid; idx < kBins * FB_RUN; idx += 256) {
-    const int k = idx >> 5, q = idx & (FB_RUN - 1);
-    const int j = t0 + q;
-    if (j >= P) continue;
-    const int pk = q * FB_KP + fb_pos(k);
-    const float vr = st_r[pk], vi = st_i[pk];
-    const size_t po = conv_rebuild_plane_index(xrow, pl.tx, hist, P, k, j);
-    pl.xr[po] = vr;
-    pl.xi[po] = vi;
-    if (j >= 1) {
-      const size_t so = conv_rebuild_store_index(P, k, j);
-      dr_[so] = vr;
-      di_[so] = vi;
-    }
-  }
-}
-void launch_conv_rebuild(hipStream_t s, const ConvRebuildJob* jobs_dev, int njobs, int max_P, ConvPlanesB pl, int hist, Twiddles tw) {
-  if (njobs <= 0 || max_P <= 0) return;
-  for (int j0 = 0; j0 < njobs; j0 += 65535) {   // gridDim.y limit
-    dim3 grid((max_P + FB_RUN - 1) / FB_RUN, std::min(65535, njobs - j0));
-    hipLaunchKernelGGL(conv_rebuild_kernel, grid, dim3(256), 0, s, jobs_dev, pl, hist, tw, j0);
-  }
 }
 
 // MAC B: workgroup = (set, bin, 256-block time tile); wave = 64 blocks (4 M-tiles) x 16 columns; taps in segments of 256
@@ -1003,184 +447,6 @@ void launch_refmac(hipStream_t s, const ConvSetB* sets_dev, int nsets, int nbloc
   for (int z0 = 0; z0 < nsets; z0 += 32768) {   // gridDim.z limit
     const int nz = std::min(32768, nsets - z0);
     hipLaunchKernelGGL(refmac_kernel, dim3(ntt, kBins, nz), dim3(256), 0, s, sets_dev + z0, nblocks, hist, pl);
-  }
-}
-
-// inverse + overlap-add, B layout: workgroup = (y-row, run of 32 blocks).  All 33 inverse transforms of the run (the extra
-// one recovers the tail of the block before the run) are independent: 4 waves x 2 batches of 4, and the 33rd alone on one
-// wave.  Heads and tails land in LDS, then
-// out[t] = (float)head[t] + tail[t-1] is written as one contiguous, fully coalesced 16 KB range.
-template <class T>
-__global__ __launch_bounds__(256) void irfft_ola_b_kernel(const ConvRowIO* __restrict yrows, int ny, int nblocks, ConvPlanesB pl,
-                                                          const float* const* __restrict overlap_in, float* const* __restrict overlap_out,
-                                                          Twiddles tw, int row0) {
-  // staging tile [33 columns][bin] (even/odd layout, see FB_KP): column c <-> block ta - 1 + c ; the memory is reused for
-  // the head/tail tiles afterwards
-  constexpr int NC = FB_RUN + 1;
-  __shared__ __attribute__((aligned(16))) float smem[2 * NC * FB_KP];   // 9636 floats >= (33 + 33) * 128 = 8448
-  float* sr = smem;
-  float* si = smem + NC * FB_KP;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row = row0 + blockIdx.y;
-  const int ta = blockIdx.x * FB_RUN;
-  const int tb = min(ta + FB_RUN, nblocks);
-  const int nrun = tb - ta;
-  const LaneTwT<T> ltw = load_lane_tw_t<T>(tw.w128, lane);
-  const int k0 = rev6(lane) << 1, k1 = k0 | 1;
-  const T wk0x = (T)tw.w256[k0].x, wk0y = (T)tw.w256[k0].y;
-  const T wk1x = (T)tw.w256[k1].x, wk1y = (T)tw.w256[k1].y;
-  const float* __restrict yr = pl.yr + (size_t)row * kBins * pl.ty;
-  const float* __restrict yi = pl.yi + (size_t)row * kBins * pl.ty;
-  GA_TL(0);
-  // columns 1..nrun <- blocks ta .. tb-1 (16-byte loads, 8 lanes per 128-byte bin line); column 0 <- block ta - 1
-  {
-    // all global loads of the tile first (10 x 16 B in flight per thread), then the LDS transposition: one exposed HBM latency
-    // per workgroup instead of one per loop iteration
-    constexpr int NIT = (kBins * 8 + 255) / 256;   // 5
-    float4 vr[NIT], vi[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-      const int idx = tid + 256 * it;
-      const int k = idx >> 3, q = (idx & 7) * 4;
-      vr[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      vi[it] = vr[it];
-      if (idx < kBins * 8 && ta + q < nblocks) {
-#ifdef GA_EXP_CONTIG   // (measurement only: the tile as one contiguous 16.5 KB range per plane)
-        vr[it] = *reinterpret_cast<const float4*>(pl.yr + ((size_t)(row * gridDim.x + blockIdx.x) * kBins + k) * 32 + q);
-        vi[it] = *reinterpret_cast<const float4*>(pl.yi + ((size_t)(row * gridDim.x + blockIdx.x) * kBins + k) * 32 + q);
-#else
-        vr[it] = *reinterpret_cast<const float4*>(yr + (size_t)k * pl.ty + ta + q);
-        vi[it] = *reinterpret_cast<const float4*>(yi + (size_t)k * pl.ty + ta + q);
-#endif
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-      const int idx = tid + 256 * it;
-      const int k = idx >> 3, q = (idx & 7) * 4;
-      if (idx < kBins * 8) {
-        const int pk = (1 + q) * FB_KP + fb_pos(k);
-        sr[pk] = vr[it].x; sr[pk + FB_KP] = vr[it].y; sr[pk + 2 * FB_KP] = vr[it].z; sr[pk + 3 * FB_KP] = vr[it].w;
-        si[pk] = vi[it].x; si[pk + FB_KP] = vi[it].y; si[pk + 2 * FB_KP] = vi[it].z; si[pk + 3 * FB_KP] = vi[it].w;
-      }
-    }
-  }
-  if (tid < kBins) {
-    float vr = 0.f, vi = 0.f;
-    if (ta > 0) {
-      vr = yr[(size_t)tid * pl.ty + ta - 1];
-      vi = yi[(size_t)tid * pl.ty + ta - 1];
-    }
-    sr[fb_pos(tid)] = vr;
-    si[fb_pos(tid)] = vi;
-  }
-  GA_TL(1);
-  __syncthreads();
-  GA_TL(2);
-  // transform columns c = 0..nrun (c = 0 only when ta > 0); results kept in registers until the staging tile is dead.
-  // Batches 0 and 1: column (4 * bq + u) * 4 + wave ; batch 2: column 32 alone, on wave (run & 3) -- which wave takes it
-  // rotates with the run, so the extra work spreads over the SIMDs.  (As a fifth transform of batch 1 it costs 50 more
-  // VGPRs and a wave of occupancy: slower.)
-  const int m = rev6(lane);
-  float hd[3][4][2], tl[3][4][2];
-#pragma unroll
-  for (int bq = 0; bq < 3; bq++) {
-    constexpr int kFull = 4;
-    const int NU = bq < 2 ? kFull : 1;
-    const bool act = bq < 2 ? (bq * 16 <= nrun) : (wave == (int)(blockIdx.x & 3) && nrun == FB_RUN);   // wave uniform
-#pragma unroll
-    for (int u = 0; u < kFull; u++) hd[bq][u][0] = hd[bq][u][1] = tl[bq][u][0] = tl[bq][u][1] = 0.f;
-    if (act) {
-      T s0r[kFull], s0i[kFull], s1r[kFull], s1i[kFull];
-#pragma unroll
-      for (int u = 0; u < NU; u++) {
-        const int c = bq < 2 ? (bq * 4 + u) * 4 + wave : FB_RUN;
-        const float* cr = sr + c * FB_KP;
-        const float* ci = si + c * FB_KP;
-        {
-          T ar = cr[m], ai = ci[m];                               // bin 2m
-          T br = cr[64 - m], bi = -(T)ci[64 - m];                 // bin 128 - 2m
-          if (m == 0) { ai = (T)0.0; bi = (T)0.0; }
-          T er = ar + br, ei = ai + bi, dr = ar - br, di = ai - bi;
-          T pr = fma(dr, wk0x, di * wk0y), pi = fma(di, wk0x, -(dr * wk0y));
-          s0r[u] = er - pi;
-          s0i[u] = ei + pr;
-        }
-        {
-          T ar = cr[FB_OB + m], ai = ci[FB_OB + m];               // bin 2m + 1
-          T br = cr[FB_OB + 63 - m], bi = -(T)ci[FB_OB + 63 - m]; // bin 127 - 2m
-          T er = ar + br, ei = ai + bi, dr = ar - br, di = ai - bi;
-          T pr = fma(dr, wk1x, di * wk1y), pi = fma(di, wk1x, -(dr * wk1y));
-          s1r[u] = er - pi;
-          s1i[u] = ei + pr;
-        }
-      }
-#ifndef GA_EXP_SKIP_FFT
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<1, 5>(s0r[u], s0i[u], ltw); dit_stage<1, 5>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<2, 4>(s0r[u], s0i[u], ltw); dit_stage<2, 4>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<4, 3>(s0r[u], s0i[u], ltw); dit_stage<4, 3>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<8, 2>(s0r[u], s0i[u], ltw); dit_stage<8, 2>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<16, 1>(s0r[u], s0i[u], ltw); dit_stage<16, 1>(s1r[u], s1i[u], ltw); }
-#pragma unroll
-      for (int u = 0; u < NU; u++) { dit_stage<32, 0>(s0r[u], s0i[u], ltw); dit_stage<32, 0>(s1r[u], s1i[u], ltw); }
-#endif
-#pragma unroll
-      for (int u = 0; u < NU; u++) {
-        T qr = fma(s1r[u], ltw.c1, s1i[u] * ltw.s1), qi = fma(s1i[u], ltw.c1, -(s1r[u] * ltw.s1));
-        const T scale = (T)(1.0 / 256.0);
-        hd[bq][u][0] = (float)((s0r[u] + qr) * scale);   // time samples 2l, 2l+1
-        hd[bq][u][1] = (float)((s0i[u] + qi) * scale);
-        tl[bq][u][0] = (float)((s0r[u] - qr) * scale);   // time samples 128+2l, 128+2l+1
-        tl[bq][u][1] = (float)((s0i[u] - qi) * scale);
-      }
-    }
-  }
-  GA_TL(3);
-  __syncthreads();   // every wave is done reading the staging tile: reuse it as head[33][128] | tail[33][128]
-  GA_TL(4);
-  float* head = smem;
-  float* tail = smem + 33 * kBlock;
-#pragma unroll
-  for (int bq = 0; bq < 3; bq++) {
-    const int NU = bq < 2 ? 4 : 1;
-    const bool mine = bq < 2 || wave == (int)(blockIdx.x & 3);
-#pragma unroll
-    for (int u = 0; u < NU; u++) {
-      const int c = bq < 2 ? (bq * 4 + u) * 4 + wave : FB_RUN;
-      if (mine && c <= nrun && (c > 0 || ta > 0)) {
-        *reinterpret_cast<float2*>(&head[c * kBlock + 2 * lane]) = make_float2(hd[bq][u][0], hd[bq][u][1]);
-        *reinterpret_cast<float2*>(&tail[c * kBlock + 2 * lane]) = make_float2(tl[bq][u][0], tl[bq][u][1]);
-      }
-    }
-  }
-  if (ta == 0 && tid < kBlock) tail[tid] = ldg1(overlap_in[row] + tid);   // incoming overlap of the chunk's first block
-  __syncthreads();
-  GA_TL(5);
-  float* out = yrows[row].out;
-  if (out) {
-    float* o4 = out + (int64_t)ta * kBlock;
-    for (int idx = tid; idx < nrun * (kBlock / 4); idx += 256) {
-      const int c = idx / (kBlock / 4) + 1, s4 = (idx % (kBlock / 4)) * 4;
-      const float4 h = *reinterpret_cast<const float4*>(&head[c * kBlock + s4]);
-      const float4 t = *reinterpret_cast<const float4*>(&tail[(c - 1) * kBlock + s4]);
-      stg4(o4 + 4 * idx, v4f{h.x + t.x, h.y + t.y, h.z + t.z, h.w + t.w});   // (float)y[i] + overlap[i]  (:148)
-    }
-  }
-  if (tb == nblocks && tid < kBlock) stg1(overlap_out[row] + tid, tail[nrun * kBlock + tid]);   // overlap[i] = (float)y[i+128]  (:149)
-  GA_TL(6);
-}
-void launch_irfft_ola_b(hipStream_t s, const ConvRowIO* yrows_dev, int ny, int nblocks, ConvPlanesB pl,
-                        const float* const* overlap_in_dev, float* const* overlap_out_dev, Twiddles tw, bool fp64) {
-  if (ny <= 0 || nblocks <= 0) return;
-  for (int r0 = 0; r0 < ny; r0 += 65535) {   // gridDim.y limit
-    dim3 grid((nblocks + FB_RUN - 1) / FB_RUN, std::min(65535, ny - r0));
-    if (fp64) hipLaunchKernelGGL(irfft_ola_b_kernel<double>, grid, dim3(256), 0, s, yrows_dev, ny, nblocks, pl, overlap_in_dev, overlap_out_dev, tw, r0);
-    else hipLaunchKernelGGL(irfft_ola_b_kernel<float>, grid, dim3(256), 0, s, yrows_dev, ny, nblocks, pl, overlap_in_dev, overlap_out_dev, tw, r0);
   }
 }
 

@@ -1,4 +1,4 @@
-// ga_kernels.hpp -- launch wrappers of the hand-written gfx950 kernels (ga_kernels.hip).
+// ga_kernels.hpp -- launch wrappers of the hand-written gfx950 kernels (ga_kernels.hip; the 256-point real-FFT kernels: ga_rfft.hip).
 // Host code (ga_engine.cpp) builds small job tables in pinned memory, uploads them once per chunk and
 // calls these wrappers; every wrapper only enqueues work on `stream` (no allocation, no sync).
 #pragma once
@@ -103,7 +103,8 @@ void launch_irfft_ola_b(hipStream_t s, const ConvRowIO* yrows_dev, int ny, int n
                         const float* const* overlap_in_dev, float* const* overlap_out_dev, Twiddles tw, bool fp64);
 void launch_hist_copy_b(hipStream_t s, const HistJobB* jobs_dev, int njobs, int max_n);
 // A convolver leaves formulation D for this state layout (option "conv_migrate", ga_conv_rebuild.hpp): the last P blocks of every
-// input channel, read from D's input history, are transformed exactly as launch_rfft_fwd_b(fp64 = true) transforms them -- blocks
+// input channel, read from D's input history, are transformed exactly as launch_rfft_fwd_b(fp64 = true) transforms them (both kernels
+// call one function, rfft_fwd_b_run<double> of ga_rfft.hip) -- blocks
 // T-P .. T-1 into columns hist-(P-1) .. hist of the scratch planes `pl` (pl.yr / pl.yi are not touched), blocks T-P+1 .. T-1 into the
 // job's [129][P-1] store.  Columns in front of a job's first block are not written (the caller clears the planes).
 void launch_conv_rebuild(hipStream_t s, const ConvRebuildJob* jobs_dev, int njobs, int max_P, ConvPlanesB pl, int hist, Twiddles tw);

@@ -28,15 +28,6 @@ def flips(ref, got):
     return n, float(rel.max())
 
 
-def _unused_ulp_distance(a, b):
-    """distance in float32 representation steps (same-sign values)"""
-    ia = a.view(np.int32).astype(np.int64)
-    ib = b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
 def render_pair(builder, frames, pieces=None, **opts):
     o = OracleContext(SR)
     ch = builder(o)

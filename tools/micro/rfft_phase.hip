@@ -1,14 +1,17 @@
 // Phase timeline of the B-layout rFFT kernels (forward: planes <- signal ; inverse: signal <- planes), standalone.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DGA_EXP_TIMELINE tools/micro/rfft_phase.hip -o rfft_phase
+//   rfft_phase [rows [blocks [fp64]]]   (fp64 = 1: the double-precision transforms of formulation R / option fft64)
 // Prints the kernel time (HIP events) and, per phase, the mean shader-clock cycles seen by thread 0 of every workgroup.
-#include "../../graphaudio_amd/csrc/ga_kernels.hip"
+#include "../../graphaudio_amd/csrc/ga_rfft.hip"
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 #include <cmath>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 int main(int argc, char** argv) {
   using namespace ga;
   const int rows = argc > 1 ? atoi(argv[1]) : 256, nblocks = argc > 2 ? atoi(argv[2]) : 3750, hist = 512;
+  const bool fp64 = argc > 3 && atoi(argv[3]) != 0;
   const int tx = hist + ((nblocks + 15) / 16) * 16 + 16, ty = ((nblocks + 255) / 256) * 256;
   float *xr, *xi, *yr, *yi, *sig, *out, *ov;
   CK(hipMalloc(&xr, (size_t)rows * kBins * tx * 4)); CK(hipMalloc(&xi, (size_t)rows * kBins * tx * 4));
@@ -51,8 +54,8 @@ int main(int argc, char** argv) {
     float best = 1e9f;
     for (int rep = 0; rep < 4; rep++) {
       CK(hipEventRecord(e0, 0));
-      if (which == 0) launch_rfft_fwd_b(0, dx, rows, nblocks, hist, pl, tw, false);
-      else launch_irfft_ola_b(0, dy, rows, nblocks, pl, doi, doo, tw, false);
+      if (which == 0) launch_rfft_fwd_b(0, dx, rows, nblocks, hist, pl, tw, fp64);
+      else launch_irfft_ola_b(0, dy, rows, nblocks, pl, doi, doo, tw, fp64);
       CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms);
     }
