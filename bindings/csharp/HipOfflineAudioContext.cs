@@ -126,6 +126,21 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _libmExact;
+    /// <summary>Option "libm_exact" (default off): a BiQuadFilterNode or StereoPannerNode whose parameters move computes its
+    /// coefficients on the device with cosf / sinf / powf restated from glibc (2.28 and later), so they equal MathF.Cos / Sin / Pow of a
+    /// .NET host on glibc bit for bit.  Off: the double-precision functions rounded once, which differ from glibc's in the last bit
+    /// for 0.006 % .. 0.09 % of the arguments.  Leave it off where MathF is backed by another C library.</summary>
+    public bool LibmExact
+    {
+        get => _libmExact;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "libm_exact", value ? 1 : 0));
+            _libmExact = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

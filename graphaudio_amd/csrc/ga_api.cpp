@@ -378,6 +378,10 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
       if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "conv_migrate is 0 or 1");
       c.convMigrate = value != 0;
     }
+    else if (k == "libm_exact") {
+      if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "libm_exact is 0 or 1");
+      c.libmExact = value != 0;
+    }
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);
     else if (k == "coarse_premix") c.coarsePremix = value != 0;

@@ -923,6 +923,7 @@ struct Exec {
       launch_mix_wide(st, t, nj, termTable(base), mx, gainTable(base), curveTable(base));
     }, mixBytes(wideJobs));
     const bool v4 = mixAligned;
+    const bool lx = c.libmExact;   // option "libm_exact": the instance of the two kernels with automated coefficients
     flush(mixJobs, LK_MIX, &MixJob::n, [=](const MixJob* t, int nj, int64_t mx, uint8_t* base) {
       launch_mix(st, t, nj, termTable(base), mx, v4, gainTable(base), curveTable(base));
     }, mixBytes(mixJobs));
@@ -941,7 +942,7 @@ struct Exec {
     for (auto& j : oscJobs) anyCurve = anyCurve || j.curve != nullptr;
     flush(oscJobs, LK_OTHER, nullptr, [=](const OscJob* t, int nj, int64_t, uint8_t*) { launch_oscillator(st, t, nj, anyCurve); });
     flush(panJobs, LK_OTHER, &PanJob::n, [=](const PanJob* t, int nj, int64_t mx, uint8_t*) { launch_stereo_panner(st, t, nj, mx); });
-    flush(panDynJobs, LK_OTHER, nullptr, [=](const PanDynJob* t, int nj, int64_t, uint8_t*) { launch_stereo_panner_dynamic(st, t, nj); });
+    flush(panDynJobs, LK_OTHER, nullptr, [=](const PanDynJob* t, int nj, int64_t, uint8_t*) { launch_stereo_panner_dynamic(st, t, nj, lx); });
     // the descriptors of the level's signal-driven spatial panners: after the mixes, before the panners
     SpatialListener ls;
     std::memcpy(ls.v, c.listener, sizeof(ls.v));
@@ -1013,7 +1014,7 @@ struct Exec {
       bqG = 0;
       bqK = 0;
     }
-    flush(bqDynJobs, LK_OTHER, nullptr, [=](const BiquadDynJob* t, int nj, int64_t, uint8_t*) { launch_biquad_dynamic(st, t, nj); });
+    flush(bqDynJobs, LK_OTHER, nullptr, [=](const BiquadDynJob* t, int nj, int64_t, uint8_t*) { launch_biquad_dynamic(st, t, nj, lx); });
     // what is left are tables, not queues
     bqSecs.clear();
     terms.clear();

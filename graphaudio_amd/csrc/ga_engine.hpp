@@ -976,6 +976,9 @@ struct Context {
   // nodes: conv_rebuild_kernel (spectra of blocks T-P .. T-1 into a scratch plane, T-P+1 .. T-1 into the stores), launch_refmac and
   // launch_irfft_ola_b over block T-1 alone (its tail is the overlap).  D's stores go to `retired`: freed after the stream has run the rebuild.
   bool convMigrate = false;
+  // option "libm_exact": biquad_dynamic_kernel and stereo_panner_dynamic_kernel evaluate cosf / sinf / powf as glibc does (ga_libmf.hpp)
+  // instead of the double-precision functions rounded once; read when a level's launches are planned
+  bool libmExact = false;
   struct ConvMigration {
     int id;
     const float* src[32];   // per input channel: the first sample of block T-P (nullptr: zeros)

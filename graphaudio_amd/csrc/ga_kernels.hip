@@ -13,6 +13,7 @@
 #include "ga_kernels.hpp"
 #include "ga_gsr.hpp"
 #include "ga_fft16.hpp"
+#include "ga_libmf.hpp"
 #include <type_traits>
 
 #include <hip/hip_runtime.h>
@@ -1906,6 +1907,8 @@ void launch_biquad(hipStream_t s, const BiquadJob* jobs_dev, int njobs, const Bi
 }
 
 // ---- BiQuadFilterNode with automated parameters --------------------------------------------------------
+// LX (option "libm_exact"): cosf / sinf / powf as glibc computes them (ga_libmf.hpp) in place of the double-precision functions rounded once
+template <bool LX>
 __device__ void biquad_update_coefficients(int type, float frequency, float q, float gain, float sample_rate, float& b0, float& b1,
                                            float& b2, float& a1, float& a2) {   // BiQuadFilterNode.cs:149-258
   const float PI = 3.14159274f;
@@ -1913,8 +1916,8 @@ __device__ void biquad_update_coefficients(int type, float frequency, float q, f
   // The reference's MathF.Cos / MathF.Sin are the C library's, which evaluate in double and round once; the device library's
   // single-precision versions are 1-2 ulp off that, which a resonant section amplifies ~fs/(pi*f/Q) times.  Evaluating in
   // double here lands on the same float except when the true value sits within ~1e-9 of a rounding boundary.
-  float cosW0 = (float)cos((double)w0);
-  float sinW0 = (float)sin((double)w0);
+  float cosW0 = LX ? ga_cosf(w0) : (float)cos((double)w0);
+  float sinW0 = LX ? ga_sinf(w0) : (float)sin((double)w0);
   float alpha = sinW0 / (2.f * q);
   float a0, A1, A2, B0, B1, B2;
   switch (type) {
@@ -1924,12 +1927,12 @@ __device__ void biquad_update_coefficients(int type, float frequency, float q, f
     case 3: B0 = 1.f; B1 = -2.f * cosW0; B2 = 1.f; a0 = 1.f + alpha; A1 = -2.f * cosW0; A2 = 1.f - alpha; break;
     case 4: B0 = 1.f - alpha; B1 = -2.f * cosW0; B2 = 1.f + alpha; a0 = 1.f + alpha; A1 = -2.f * cosW0; A2 = 1.f - alpha; break;
     case 5: {
-      float A = (float)pow(10.0, (double)(gain / 40.f));
+      float A = LX ? ga_powf(10.f, gain / 40.f) : (float)pow(10.0, (double)(gain / 40.f));
       B0 = 1.f + alpha * A; B1 = -2.f * cosW0; B2 = 1.f - alpha * A; a0 = 1.f + alpha / A; A1 = -2.f * cosW0; A2 = 1.f - alpha / A;
       break;
     }
     case 6: {
-      float A = (float)pow(10.0, (double)(gain / 40.f));
+      float A = LX ? ga_powf(10.f, gain / 40.f) : (float)pow(10.0, (double)(gain / 40.f));
       float beta = sqrtf(A) / q;
       B0 = A * ((A + 1.f) - (A - 1.f) * cosW0 + beta * sinW0);
       B1 = 2.f * A * ((A - 1.f) - (A + 1.f) * cosW0);
@@ -1940,7 +1943,7 @@ __device__ void biquad_update_coefficients(int type, float frequency, float q, f
       break;
     }
     case 7: {
-      float A = (float)pow(10.0, (double)(gain / 40.f));
+      float A = LX ? ga_powf(10.f, gain / 40.f) : (float)pow(10.0, (double)(gain / 40.f));
       float beta = sqrtf(A) / q;
       B0 = A * ((A + 1.f) + (A - 1.f) * cosW0 + beta * sinW0);
       B1 = -2.f * A * ((A - 1.f) + (A + 1.f) * cosW0);
@@ -1958,6 +1961,7 @@ __device__ void biquad_update_coefficients(int type, float frequency, float q, f
   a1 = A1 / a0;
   a2 = A2 / a0;
 }
+template <bool LX>
 __global__ __launch_bounds__(64) void biquad_dynamic_kernel(const BiquadDynJob* __restrict jobs, int njobs) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= njobs) return;
@@ -1984,7 +1988,7 @@ __global__ __launch_bounds__(64) void biquad_dynamic_kernel(const BiquadDynJob* 
         float q = job->qcurve ? ldg1(job->qcurve + f0 + i) : job->qval;
         q = max_ref(0.001f, q);   // Math.Max (:124): a NaN Q stays NaN -- no update unless the frequency moves, then NaN coefficients
         if (dirty || fabsf(f - usedFreq) > 0.001f || fabsf(q - usedQ) > 0.0001f) {   // usedGain == gainDb always (:113,126)
-          biquad_update_coefficients(type, f, q, gainDb, sr, b0, b1, b2, a1, a2);
+          biquad_update_coefficients<LX>(type, f, q, gainDb, sr, b0, b1, b2, a1, a2);
           usedFreq = f;
           usedQ = q;
           dirty = false;
@@ -2004,9 +2008,10 @@ __global__ __launch_bounds__(64) void biquad_dynamic_kernel(const BiquadDynJob* 
   st->b0 = b0; st->b1 = b1; st->b2 = b2; st->a1 = a1; st->a2 = a2;
   st->dirty = dirty ? 1 : 0;
 }
-void launch_biquad_dynamic(hipStream_t s, const BiquadDynJob* jobs_dev, int njobs) {
+void launch_biquad_dynamic(hipStream_t s, const BiquadDynJob* jobs_dev, int njobs, bool libm_exact) {
   if (njobs <= 0) return;
-  hipLaunchKernelGGL(biquad_dynamic_kernel, dim3((njobs + 63) / 64), dim3(64), 0, s, jobs_dev, njobs);
+  if (libm_exact) hipLaunchKernelGGL(biquad_dynamic_kernel<true>, dim3((njobs + 63) / 64), dim3(64), 0, s, jobs_dev, njobs);
+  else hipLaunchKernelGGL(biquad_dynamic_kernel<false>, dim3((njobs + 63) / 64), dim3(64), 0, s, jobs_dev, njobs);
 }
 
 // =====================================================================================================
@@ -2856,13 +2861,15 @@ void launch_delay_probe(hipStream_t s, const DelayProbeJob* jobs_dev, int njobs)
 }
 
 
+template <bool LX>   // (option "libm_exact", as biquad_update_coefficients)
 __device__ __forceinline__ void pan_gains(float pan, int stereo, float& gl, float& gr) {   // :94-98 / :129-133
   const float PIf = 3.14159265358979323846f;
   const float x = stereo ? (pan <= 0.0f ? pan + 1.0f : pan) : (pan + 1.0f) * 0.5f;
   const float a = x * PIf / 2.0f;
-  gl = (float)cos((double)a);   // rounded once from double, as the C library's cosf / sinf behind MathF are
-  gr = (float)sin((double)a);
+  gl = LX ? ga_cosf(a) : (float)cos((double)a);   // (rounded once from double: the C library's cosf / sinf behind MathF up to their last bit)
+  gr = LX ? ga_sinf(a) : (float)sin((double)a);
 }
+template <bool LX>
 __global__ __launch_bounds__(64) void stereo_panner_dynamic_kernel(const PanDynJob* __restrict jobs) {
   __shared__ float chg_pan[64];
   __shared__ int chg_has[64];
@@ -2897,7 +2904,7 @@ __global__ __launch_bounds__(64) void stereo_panner_dynamic_kernel(const PanDynJ
         carry[r] = cur;
         if (chg_has[r]) {
           cur.last_pan = chg_pan[r];
-          pan_gains(cur.last_pan, job.stereo, cur.gain_l, cur.gain_r);
+          pan_gains<LX>(cur.last_pan, job.stereo, cur.gain_l, cur.gain_r);
         }   // no change in the block: every pan of the block equals the carried _lastPan
       }
       carry[nb] = cur;
@@ -2910,7 +2917,7 @@ __global__ __launch_bounds__(64) void stereo_panner_dynamic_kernel(const PanDynJ
         const int64_t f = fb + i;
         const float pan = panAt(f);
         if (pan != lp) {
-          pan_gains(pan, job.stereo, gl, gr);
+          pan_gains<LX>(pan, job.stereo, gl, gr);
           lp = pan;
         }
         if (!job.stereo) {
@@ -2938,9 +2945,10 @@ __global__ __launch_bounds__(64) void stereo_panner_dynamic_kernel(const PanDynJ
     pdst[0] = st.last_pan; pdst[1] = st.gain_l; pdst[2] = st.gain_r; pdst[3] = st.pad_;
   }
 }
-void launch_stereo_panner_dynamic(hipStream_t s, const PanDynJob* jobs_dev, int njobs) {
+void launch_stereo_panner_dynamic(hipStream_t s, const PanDynJob* jobs_dev, int njobs, bool libm_exact) {
   if (njobs <= 0) return;
-  hipLaunchKernelGGL(stereo_panner_dynamic_kernel, dim3(njobs), dim3(64), 0, s, jobs_dev);
+  if (libm_exact) hipLaunchKernelGGL(stereo_panner_dynamic_kernel<true>, dim3(njobs), dim3(64), 0, s, jobs_dev);
+  else hipLaunchKernelGGL(stereo_panner_dynamic_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs_dev);
 }
 
 

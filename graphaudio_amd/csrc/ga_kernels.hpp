@@ -366,7 +366,7 @@ struct BiquadDynJob {
   int64_t b0;             // first block (chunk relative)
   int64_t nblocks;
 };
-void launch_biquad_dynamic(hipStream_t s, const BiquadDynJob* jobs_dev, int njobs);
+void launch_biquad_dynamic(hipStream_t s, const BiquadDynJob* jobs_dev, int njobs, bool libm_exact);
 
 // AudioParam timeline evaluation (AudioParam.cs:114-247)
 struct ParamEvent {
@@ -613,7 +613,7 @@ struct PanDynJob {
   int pad_;
   int64_t f0, n;         // multiples of 128
 };
-void launch_stereo_panner_dynamic(hipStream_t s, const PanDynJob* jobs_dev, int njobs);
+void launch_stereo_panner_dynamic(hipStream_t s, const PanDynJob* jobs_dev, int njobs, bool libm_exact);
 
 // DelayNode.Process (DelayNode.cs:43-100): out[f] = line[f - d(f)], d(f) = clamp((int)(delayTime[f] * sampleRate), 0, max);
 // d = 0 reads 0 (CircularBuffer.Read, :136-144).  `line` is indexed like the chunk (line[f] = input sample of frame f) and

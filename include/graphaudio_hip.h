@@ -186,7 +186,10 @@ GA_EXPORT int GA_FN(context_destroy)(ga_context* ctx);         /* AudioContextBa
 GA_EXPORT const char* GA_FN(last_error)(ga_context* ctx);      /* message of the last failing call on this context */
 GA_EXPORT double GA_FN(current_time)(ga_context* ctx);         /* AudioContextBase.CurrentTime, AudioContextBase.cs:28 */
 GA_EXPORT int64_t GA_FN(current_block)(ga_context* ctx);       /* AudioContextBase.CurrentBlock, AudioContextBase.cs:223 */
-GA_EXPORT int GA_FN(set_option)(ga_context* ctx, const char* key, double value); /* tuning knobs, see DESIGN.md ("coarse_long", default 1: impulse responses of 131,073 .. 1,048,576 taps take the coarse-partition formulation D as well -- segmented partition sum; 0: the direct formulations, as for longer ones) */
+GA_EXPORT int GA_FN(set_option)(ga_context* ctx, const char* key, double value); /* tuning knobs, see DESIGN.md ("coarse_long", default 1: impulse responses of 131,073 .. 1,048,576 taps take the coarse-partition formulation D as well -- segmented partition sum; 0: the direct formulations, as for longer ones;
+   "libm_exact", default 0: 1 makes an automated BiQuadFilterNode and an automated StereoPannerNode compute their per-sample coefficients
+   with cosf / sinf / powf as glibc >= 2.28 computes them, bit for bit, instead of the double-precision functions rounded once -- for a
+   host whose MathF.Cos / Sin / Pow are glibc's; any other value is GA_ERR_OUT_OF_RANGE; DESIGN.md section 8 "libm class") */
 GA_EXPORT int GA_FN(get_stats)(ga_context* ctx, ga_stats* out);
 
 /* ---- PlayableAudioBuffer.FromChannelArrays (PlayableAudioBuffer.cs:122-145): immutable sample storage ----
