@@ -81,343 +81,25 @@ void Context::runChunk(int64_t n, float* const* bus) {
   }
 }
 
-// pass 1: reachability, level and convolver depth of every node; state handed back by automated runs that ended
+// pass 1: the graph analysis (ga_topology.cpp) and what it refuses, while nothing has moved: every failure here leaves the context usable
 void Context::chunkTopology(ChunkRun& r) {
-  std::vector<int>& topo = r.topo;
-  for (int id : probeDelays)   // (the previous chunk's choice, if a failure kept it from being cleared: runTwoStageChunk)
-    if (id < (int)nodes.size() && nodes[id]) rec<DelayS>(*nodes[id]).delayProbe = false;
-  probeDelays.clear();
-#ifdef GA_EXPERIMENTS
-  // (which condition keeps a delay on the prediction: one line per delay and chunk on stderr)
-  auto kept = [&](int id, const char* why, int at) {
-    if (expenv("GA_DEBUG_DELAY_FLAG")) fprintf(stderr, "[delay flag] chunk %lld delay %d keeps the prediction: %s (node %d)\n", (long long)stats.chunks, id, why, at);
-  };
-#else
-  auto kept = [](int, const char*, int) {};
-#endif
-  // the sources whose playbackRate a signal modulates and the cone of their modulation inputs (cached per graph version)
-  auto updateRateCone = [&](const std::vector<int>& topo) {
-    if (rateModsVersion == graphVersion && rateCone.size() == nodes.size()) return;
-    topoRateMods.clear();
-    for (int id : topo) {
-      const NodeS& nd = *nodes[id];
-      if ((nd.type == GA_NODE_BUFFER_SOURCE || nd.type == GA_NODE_STREAM_SOURCE) && !nd.params.empty() && !nd.params[0].modulation.empty())
-        topoRateMods.push_back({id, 0});
-    }
-    // the cone: every node the modulation inputs reach backwards (params before inputs, as Nodes/AudioNode.cs:167-175 pulls them)
-    rateCone.assign(nodes.size(), 0);
-    std::vector<int> stack;
-    for (const auto& pm : topoRateMods)
-      for (const auto& m : nodes[pm.first]->params[pm.second].modulation)
-        if (!rateCone[m.first]) {
-          rateCone[m.first] = 1;
-          stack.push_back(m.first);
-        }
-    while (!stack.empty()) {
-      const NodeS& nd = *nodes[stack.back()];
-      stack.pop_back();
-      auto visit = [&](int up) {
-        if (!rateCone[up]) {
-          rateCone[up] = 1;
-          stack.push_back(up);
-        }
-      };
-      for (const auto& p : nd.params)
-        for (const auto& m : p.modulation) visit(m.first);
-      for (const auto& in : nd.inputs)
-        for (const Conn& cn : in.connected) visit(cn.node);
-    }
-    rateModsVersion = graphVersion;
-  };
-  // ---- reachability, level, convolver depth on the graph as it stands after the queued commands ----
-  // (cached while no connection, disposal or impulse response changed since the last chunk)
-  // (a graph with feedback is walked again every chunk: whether its loops can be cut at their DelayNodes depends on the delay
-  // times, which are parameters, not graph structure)
-  if (topoVersion == graphVersion && !topoCache.empty() && !topoHasCycles) {
-    topo = topoCache;
-  } else {
-  staleLeavers.clear();
-  for (auto& np : nodes) {
-    np->prevReachable = np->reachable;
-    np->reachable = false;
-    np->isProcessing = false;
-    np->level = 0;
-    np->depth = 0;
-    if (np->type == GA_NODE_DELAY) {
-      DelayS& dl = rec<DelayS>(*np);
-      dl.delaySplit = false;
-      dl.delayOnLoop = false;
-    }
-  }
-  cycleBlocks = 1;
-  loopGainBound = 0.0;
-  topoStaleEdges.clear();
-  loopProbeDelays.clear();
-  loopProbeCone.clear();
-  std::vector<int> color(nodes.size(), 0);
-  std::vector<char> candidate;   // DelayNodes on a loop whose delay is a constant of at least two blocks
-  bool unbreakable = false;
-  {
-    // The traversal order is the reference's (parameters first, then the inputs, connections in order: Nodes/AudioNode.cs:167-175).
-    // A node met again while it is still being processed closes a feedback cycle.  The reference does not refuse that: its memo
-    // check (Nodes/AudioNode.cs:153-156) returns before the "cycle detected" test can fire, and the consumer mixes the producer's
-    // PREVIOUS block.  Such an edge carries no ordering constraint -- the producer is processed later in the block, as there.
-    for (int id : staleProducers)
-      if (id < (int)nodes.size() && nodes[id]) nodes[id]->staleProducer = false;
-    staleProducers.clear();
-    std::vector<int> stack;
-    std::vector<std::pair<int, int>> entry;   // (node, the node it was reached from) in the order the walk enters them
-    auto splittable = [&](const NodeS& d) {
-      if (d.type != GA_NODE_DELAY || !d.params[0].events.empty() || !d.params[0].modulation.empty()) return 0;
-      int dl = (int)(d.params[0].value * (float)sampleRate);   // DelayNode.cs:66 (float * int -> float, truncated)
-      dl = std::min(std::max(dl, 0), rec<DelayS>(d).maxDelaySamples);
-      return dl / kBlock;   // whole blocks of delay
-    };
-    std::function<bool(int)> dfs = [&](int id) {   // false: `id` is being processed (the edge that led here is a feedback edge)
-      if (color[id] == 2) return true;
-      if (color[id] == 1) {
-        if (delayFlagExact >= 2 && !stack.empty()) topoStaleEdges.push_back(((uint64_t)stack.back() << 32) | (uint64_t)id);
-        if (!nodes[id]->staleProducer) staleProducers.push_back(id);
-        nodes[id]->staleProducer = true;
-        // the loop this edge closes: the nodes on the stack from `id` up.  It can be cut where a DelayNode delays by >= 2 blocks.
-        if (candidate.empty()) candidate.assign(nodes.size(), 0);
-        bool any = false;
-        double bound = 1.0;   // an upper estimate of the loop's gain: what a last-bit difference that enters it is multiplied by per turn
-        for (size_t q = stack.size(); q-- > 0;) {
-          const int m = stack[q];
-          NodeS& mn = *nodes[m];
-          if (mn.type == GA_NODE_DELAY) rec<DelayS>(mn).delayOnLoop = true;   // (option "delay_flag_exact", below)
-          if (splittable(mn) >= 2) {
-            candidate[m] = 1;
-            any = true;
-          }
-          bool moving = false;
-          for (auto& p : mn.params) moving = moving || !p.events.empty() || !p.modulation.empty();
-          switch (mn.type) {
-            case GA_NODE_GAIN: bound *= moving ? 1e9 : std::fabs((double)mn.params[0].value); break;
-            case GA_NODE_BIQUAD: {
-              const int ft = rec<BiquadS>(mn).filterType;
-              if (moving) bound *= 1e9;
-              else if (ft == GA_FILTER_PEAKING || ft == GA_FILTER_LOWSHELF || ft == GA_FILTER_HIGHSHELF)
-                bound *= std::max(1.0, std::pow(10.0, (double)mn.params[2].value / 20.0));
-              else bound *= std::max(1.0, (double)mn.params[1].value);   // (the resonance peak of a low / high / band pass is ~Q)
-              break;
-            }
-            case GA_NODE_CONVOLVER: bound *= rec<ConvolverS>(mn).normalize ? 2.0 : 1e9; break;   // (normalised responses: broadband gain well below 1, peaks unknown)
-            case GA_NODE_STEREO_PANNER: bound *= 2.0; break;                    // (oL = inL + inR * gainL)
-            case GA_NODE_SPATIAL_PANNER: bound *= (double)rec<SpatialPannerS>(mn).spGainBound; break;   // (sum |F| + |D| <= max(1, sum |h|): g <= 1, the weights sum to 1)
-            default: break;
-          }
-          if (m == id) break;
-        }
-        loopGainBound = std::max(loopGainBound, bound);
-        if (!any) unbreakable = true;
-        return false;
-      }
-      color[id] = 1;
-      entry.push_back({id, stack.empty() ? -1 : stack.back()});
-      stack.push_back(id);
-      NodeS& nd = *nodes[id];
-      nd.reachable = true;
-      int lvl = 0, dep = 0;
-      for (auto& p : nd.params)
-        if (!p.modulation.empty()) {
-          for (auto& m : p.modulation) {
-            if (!dfs(m.first)) continue;
-            NodeS& up = *nodes[m.first];
-            lvl = std::max(lvl, up.level + 1);
-            dep = std::max(dep, up.depth + (hasImpulseResponse(up) ? 1 : 0));
-          }
-        }
-      for (auto& in : nd.inputs)
-        for (const Conn& cn : in.connected) {
-          if (!dfs(cn.node)) continue;
-          NodeS& up = *nodes[cn.node];
-          lvl = std::max(lvl, up.level + 1);
-          dep = std::max(dep, up.depth + (hasImpulseResponse(up) ? 1 : 0));
-        }
-      nd.level = lvl;
-      nd.depth = dep;
-      color[id] = 2;
-      stack.pop_back();
-      topo.push_back(id);
-      return true;
-    };
-    dfs(0);
-    topoRefOrder = staleProducers.empty() ? std::vector<int>() : topo;   // (the reference's processing order: Context::refOrderSensitivity)
-    if (staleProducers.empty()) topoRefEntry.clear();
-    else topoRefEntry.swap(entry);   // (where the walk enters a modulator cone: runTwoStageChunk)
-    // ---- loops that can be cut at a DelayNode (option "cycle_delay_split") ----
-    // A DelayNode whose delay is a constant of d >= 128 K samples reads, for any K consecutive blocks, only samples its ring held
-    // BEFORE those blocks: its output for the whole K-block chunk can be produced first (a gather from the history: the READER, a node
-    // without inputs), and its input appended afterwards (the WRITER).  With every loop cut that way the chunk's graph is acyclic; the
-    // reference's stale edge becomes an ordinary edge that reads its producer ONE BLOCK LATE (Exec::resolveInSeg).  Chunks of K blocks
-    // instead of one: a 0.25 s echo renders 93 blocks per chunk.
-    // ---- DelayNodes on a loop whose output flag this chunk reads from their samples (option "delay_flag_exact" = 2) ----
-    // In a chunk of ONE block with no loop cut, the edges that read a producer's previous block (recorded above) resolve to kept blocks
-    // of the previous chunk and the other edges form a DAG: everything a delay D depends on in this block lies in front of it in the
-    // walk, and every consumer of D either comes after it or reads the block before, whose flag was read a block ago.  Accepted, while
-    // nothing has moved: a reachable D with its flag down that is on a loop (among the stack nodes of a back edge, or reached by its
-    // own cone) and not in front of a modulated playbackRate, whose cone over the edges that are not stale holds no ConvolverNode, no
-    // source with a modulated playbackRate and no other DelayNode with its flag down -- the conditions of the delays on no loop (below),
-    // on the smaller cone.  While one is accepted the chunk is one block and no loop is cut; the flag is sticky, so chunks of
-    // `cycleBlocks` blocks return once it is up.
-    if (delayFlagExact >= 2 && !staleProducers.empty()) {
-      std::sort(topoStaleEdges.begin(), topoStaleEdges.end());
-      auto staleEdge = [&](int from, int up) { return std::binary_search(topoStaleEdges.begin(), topoStaleEdges.end(), ((uint64_t)from << 32) | (uint64_t)up); };
-      std::vector<int> seen(nodes.size(), -1), work, cone;
-      for (int id : topo) {
-        if (nodes[id]->type != GA_NODE_DELAY) continue;
-        const DelayS& d = rec<DelayS>(*nodes[id]);
-        if (d.delayAudible) continue;
-        // on a loop?  (the whole cone, as the acceptance of the other delays walks it)
-        bool onLoop = d.delayOnLoop;
-        if (!onLoop) {
-          work.assign(1, id);
-          seen[id] = id;
-          while (!work.empty() && !onLoop) {
-            const NodeS& nd = *nodes[work.back()];
-            work.pop_back();
-            auto visit = [&](int up) {
-              if (up == id) onLoop = true;
-              if (seen[up] == id) return;
-              seen[up] = id;
-              work.push_back(up);
-            };
-            for (const auto& p : nd.params)
-              for (const auto& m : p.modulation) visit(m.first);
-            for (const auto& in : nd.inputs)
-              for (const Conn& cn : in.connected) visit(cn.node);
-          }
-        }
-        if (!onLoop) continue;
-        bool ok = true;
-        const int mark = id + (int)nodes.size();   // (a second stamp per delay: the cone over the edges that are not stale)
-        cone.clear();
-        work.assign(1, id);
-        seen[id] = mark;
-        while (!work.empty() && ok) {
-          const int from = work.back();
-          const NodeS& nd = *nodes[from];
-          work.pop_back();
-          auto visit = [&](int up) {
-            if (seen[up] == mark || staleEdge(from, up)) return;
-            seen[up] = mark;
-            const NodeS& u = *nodes[up];
-            if ((u.type == GA_NODE_DELAY && !rec<DelayS>(u).delayAudible) || u.type == GA_NODE_CONVOLVER ||
-                ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty())) {
-              if (ok) kept(id, u.type == GA_NODE_DELAY ? "on a loop, another delay with its flag down in its cone" : u.type == GA_NODE_CONVOLVER ? "on a loop, a convolver in its cone" : "on a loop, a modulated rate in its cone", up);
-              ok = false;
-            }
-            cone.push_back(up);
-            work.push_back(up);
-          };
-          for (const auto& p : nd.params)
-            for (const auto& m : p.modulation) visit(m.first);
-          for (const auto& in : nd.inputs)
-            for (const Conn& cn : in.connected) visit(cn.node);
-        }
-        if (!ok) continue;
-        updateRateCone(topo);
-        if (!topoRateMods.empty() && rateCone[id]) {
-          kept(id, "on a loop, in front of a modulated rate", id);
-          continue;
-        }
-        if (loopProbeCone.empty()) loopProbeCone.assign(nodes.size(), 0);
-        for (int up : cone) loopProbeCone[up] = 1;
-        loopProbeDelays.push_back(id);
-      }
-    }
-    if (!staleProducers.empty() && !unbreakable && cycleDelaySplit && loopProbeDelays.empty()) {
-      int K = 1 << 30;
-      for (size_t m = 0; m < candidate.size(); m++)
-        if (candidate[m]) K = std::min(K, splittable(*nodes[m]));
-      // second walk, edges OUT of a cut DelayNode carry no ordering: is anything still cyclic?
-      std::vector<int> color2(nodes.size(), 0), order, deferred;
-      std::vector<int> lvl2(nodes.size(), 0), dep2(nodes.size(), 0);
-      bool cyclic = false;
-      std::function<void(int)> dfs2 = [&](int id) {
-        if (color2[id] == 2 || cyclic) return;
-        if (color2[id] == 1) {
-          cyclic = true;
-          return;
-        }
-        color2[id] = 1;
-        NodeS& nd = *nodes[id];
-        int lvl = 0, dep = 0;
-        auto edge = [&](int up) {
-          if (candidate[up]) {   // the reader: a source (planned in front of everything); its writer is walked as a root of its own
-            if (color2[up] == 0) deferred.push_back(up);
-            return;
-          }
-          dfs2(up);
-          lvl = std::max(lvl, lvl2[up] + 1);
-          dep = std::max(dep, dep2[up] + (hasImpulseResponse(*nodes[up]) ? 1 : 0));
-        };
-        for (auto& p : nd.params)
-          for (auto& m : p.modulation) edge(m.first);
-        for (auto& in : nd.inputs)
-          for (const Conn& cn : in.connected) edge(cn.node);
-        lvl2[id] = lvl;
-        dep2[id] = dep;
-        color2[id] = 2;
-        order.push_back(id);
-      };
-      dfs2(0);
-      for (size_t q = 0; q < deferred.size() && !cyclic; q++) dfs2(deferred[q]);
-      if (!cyclic && K >= 2 && order.size() == topo.size()) {
-        topo = order;
-        for (int id : topo) {
-          nodes[id]->level = lvl2[id];
-          nodes[id]->depth = dep2[id];
-          if (nodes[id]->type == GA_NODE_DELAY) rec<DelayS>(*nodes[id]).delaySplit = candidate[id] != 0;
-        }
-        cycleBlocks = K;
-      }
-    }
-  }
-  topoCache = topo;
-  topoVersion = graphVersion;
-  topoHasCycles = !staleProducers.empty();
-  for (auto& np : nodes)
-    if (np->prevReachable && !np->reachable && !np->disposed) staleLeavers.push_back(np->id);
-  }
-  // Feedback: the loop closes through the block a producer put out LAST.  Unless every loop can be cut at a DelayNode (above: chunks
-  // of `cycleBlocks` blocks) nothing can be batched along time -- the chunk is one block, the reference's own granularity (a 10 s
+  const TopologyOptions o{sampleRate, delayFlagExact, cycleDelaySplit};
+  topology.chunkNo = stats.chunks;
+  topology.clearProbes(nodes);
+  if (topology.cached(graphVersion)) r.topo = topology.order;
+  else topology.analyse(nodes, o, graphVersion, r.topo);
+  // Feedback: the loop closes through the block a producer put out LAST.  Unless every loop can be cut at a DelayNode (chunks of
+  // `cycleBlocks` blocks) nothing can be batched along time -- the chunk is one block, the reference's own granularity (a 10 s
   // render = 3,750 chunks: launch bound, ~0.1 - 0.3 ms each)
-  if (topoHasCycles) r.n = std::min<int64_t>(r.n, cycleBlocks);
-  if (topoStatsVersion != graphVersion || topoStatsSize != topo.size()) {   // (cached with the order: a sweep over 28,672 node records is 0.5 ms)
-    topoMaxDepth = topoMaxLevel = 0;
-    topoHasTimeNodes = topoHasConvolvers = topoHasOscillators = topoHasStreams = topoHasSpatial = false;
-    for (int id : topo) {
-      const NodeS& nd = *nodes[id];
-      topoMaxDepth = std::max(topoMaxDepth, nd.depth);
-      topoMaxLevel = std::max(topoMaxLevel, nd.level);
-      if (nd.type == GA_NODE_DELAY || nd.type == GA_NODE_STREAM_SOURCE) topoHasTimeNodes = true;
-      if (nd.type == GA_NODE_STREAM_SOURCE) topoHasStreams = true;
-      if (nd.type == GA_NODE_CONVOLVER) topoHasConvolvers = true;   // (with or without an impulse response: Buffer setters run in drain())
-      if (nd.type == GA_NODE_OSCILLATOR) topoHasOscillators = true;
-      if (nd.type == GA_NODE_SPATIAL_PANNER) topoHasSpatial = true;
-    }
-    topoStatsVersion = graphVersion;
-    topoStatsSize = topo.size();
-  }
-  r.maxDepth = topoMaxDepth;
-  r.maxLevel = topoMaxLevel;
-  // ---- playbackRate modulated by a signal (AudioBufferSourceNode / AudioStreamSourceNode): a two-stage chunk (runTwoStageChunk) ----
-  // The rate decides how many samples each block consumes and where a one-shot source ends, and the planner needs that before it can
-  // plan the rest: the modulation inputs' cone is rendered first.  The cases that cannot be split so are refused here, before any state
-  // moves (the context stays usable).
-  updateRateCone(topo);
-  if (!topoRateMods.empty()) {
-    for (const auto& pm : topoRateMods)
-      if (rateCone[pm.first])
-        fail(GA_ERR_UNSUPPORTED, "a modulated playbackRate depends on a source whose own playbackRate is modulated, or on its own output "
-                                 "(nested modulated rates / feedback through the rate) -- not on the device path");
-    for (int id : topo)
-      if (rateCone[id] && nodes[id]->type == GA_NODE_CONVOLVER)
-        fail(GA_ERR_UNSUPPORTED, "a ConvolverNode in front of a modulated playbackRate is not on the device path");
-    for (const auto& pm : topoRateMods) {
+  if (topology.hasCycles) r.n = std::min<int64_t>(r.n, topology.cycleBlocks);
+  topology.refreshSummary(nodes, graphVersion, r.topo);
+  r.maxDepth = topology.maxDepth;
+  r.maxLevel = topology.maxLevel;
+  // a playbackRate modulated by a signal (AudioBufferSourceNode / AudioStreamSourceNode): a two-stage chunk (runTwoStageChunk)
+  topology.updateRateCone(nodes, graphVersion, r.topo);
+  if (!topology.rateMods.empty()) {
+    topology.refuseRateCone(nodes, r.topo);
+    for (const auto& pm : topology.rateMods) {
       if (nodes[pm.first]->type != GA_NODE_BUFFER_SOURCE) continue;
       BufferSourceS& nd = rec<BufferSourceS>(*nodes[pm.first]);
       if (!nd.loop || nd.bufId < 0 || !buffers[nd.bufId]) continue;
@@ -425,137 +107,54 @@ void Context::chunkTopology(ChunkRun& r) {
       if (g.loopEndFrame <= g.loopStartFrame)   // (the replay's guard would fire inside the device walk: refused while nothing has moved)
         fail(GA_ERR_UNSUPPORTED, "source loop of zero length with resampling never finishes a block in the reference");
     }
-    r.rateMods = topoRateMods;
-    r.stage1 = rateCone;
+    r.rateMods = topology.rateMods;
+    r.stage1 = topology.rateCone;
   }
-  // ---- DelayNodes whose output flag this chunk reads from their samples (option "delay_flag_exact"; runTwoStageChunk) ----
-  // The flag rises at the first output SAMPLE that is != 0f (DelayNode.cs:72,92,96-97), which the host cannot see: it predicts the flag
-  // from the flags of the blocks that went into the ring (Sim::process), never late, sometimes early.  A delay whose cone can be
-  // rendered ahead of the rest is rendered in stage 1 instead, and the block in which its samples raise the flag is read back
-  // (delay_onset_kernel).  Accepted, per chunk, while nothing has moved: a reachable DelayNode whose flag is down, that is on no
-  // feedback loop (not among the nodes of a back edge's loop, DelayS::delayOnLoop, and not reached by its own cone: deciding it would
-  // split the reference's walk inside a block), with no other DelayNode whose flag is down in front
-  // of it (the control state of the nodes in between would be undecided: more than two stages), no source with a modulated
-  // playbackRate in front of it and not in front of one (stage 1 plans both from the state before the chunk), and no ConvolverNode
-  // in front of it (stage 1 plans no convolvers: their fusion groups and scratch planes belong to one pass over the whole graph).
-  // Every other delay keeps the prediction (ga_stats.delay_flags_predicted).
-  if (delayFlagExact && topoHasTimeNodes) {
-    std::vector<int> seen, stack, cone;
-    for (int id : topo) {
-      if (nodes[id]->type != GA_NODE_DELAY) continue;
-      DelayS& d = rec<DelayS>(*nodes[id]);
-      if (std::find(loopProbeDelays.begin(), loopProbeDelays.end(), id) != loopProbeDelays.end()) {   // (a delay on a loop, accepted above: value 2)
-        if (r.stage1.empty()) r.stage1.assign(nodes.size(), 0);
-        r.stage1[id] = 1;
-        d.delayProbe = true;
-        d.delayShadow = false;
-        d.delaySpans.clear();
-        probeDelays.push_back(id);
-        continue;
-      }
-      if (d.delayAudible) continue;
-      if (d.delayOnLoop || d.delaySplit) {
-        kept(id, "on a loop", id);
-        continue;
-      }
-      if (!topoRateMods.empty() && rateCone[id]) {
-        kept(id, "in front of a modulated rate", id);
-        continue;
-      }
-      if (seen.empty()) seen.assign(nodes.size(), -1);
-      bool ok = true;
-      cone.clear();
-      stack.assign(1, id);
-      seen[id] = id;
-      while (!stack.empty() && ok) {
-        const NodeS& nd = *nodes[stack.back()];
-        stack.pop_back();
-        auto visit = [&](int up) {
-          // (the cone reaches D itself: D is on a loop that the walk from the destination closed through a node it had finished
-          // already, so D was never on the stack of a back edge -- a consumer of D would be stage 1's and read a view D does not hand out)
-          if (up == id) {
-            if (ok) kept(id, "on a loop closed through a finished node", up);
-            ok = false;
-          }
-          if (seen[up] == id) return;
-          seen[up] = id;
-          const NodeS& u = *nodes[up];
-          if ((u.type == GA_NODE_DELAY && !rec<DelayS>(u).delayAudible) || u.type == GA_NODE_CONVOLVER ||
-              ((u.type == GA_NODE_BUFFER_SOURCE || u.type == GA_NODE_STREAM_SOURCE) && !u.params.empty() && !u.params[0].modulation.empty())) {
-            if (ok) kept(id, u.type == GA_NODE_DELAY ? "another delay with its flag down in front of it" : u.type == GA_NODE_CONVOLVER ? "a convolver in front of it" : "a modulated rate in front of it", up);
-            ok = false;
-          }
-          cone.push_back(up);
-          stack.push_back(up);
-        };
-        for (const auto& p : nd.params)
-          for (const auto& m : p.modulation) visit(m.first);
-        for (const auto& in : nd.inputs)
-          for (const Conn& cn : in.connected) visit(cn.node);
-      }
-      if (!ok) continue;
-      if (r.stage1.empty()) r.stage1.assign(nodes.size(), 0);
-      r.stage1[id] = 1;
-      for (int up : cone) r.stage1[up] = 1;
-      d.delayProbe = true;
-      d.delayShadow = false;
-      d.delaySpans.clear();
-      probeDelays.push_back(id);
+  r.loopProbe = topology.acceptDelays(nodes, o, r.topo, r.stage1);
+  r.probeDelays = topology.probeDelays;
+  if (!r.stage1.empty() && !r.loopProbe) r.coneRoots = topology.coneRoots(r.stage1);
+  refuseSpatialPanners(r);
+  fetchDeviceState();
+}
+
+// SpatialPannerNode: what the device path does not render is refused here, while nothing has moved
+void Context::refuseSpatialPanners(const ChunkRun& r) {
+  if (!topology.hasSpatial) return;
+  const double increment = (double)kBlock / sampleRate;
+  for (int id : r.topo) {
+    if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
+    SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
+    // (decided here, on the graph as the chunk finds it: a modulator that ends inside the chunk is disconnected by the simulation,
+    // and the blocks before that still read it)
+    nd.spSignals = spatialSignalDriven(nd);
+    const std::string who = "SpatialPannerNode " + std::to_string(id) + ": ";
+    for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) {
+      if (nd.params[p].modulation.empty()) continue;
+      if (!spatialParamSignals)
+        fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to parameter " + std::to_string(p) + " (signals on the node's parameters are not on the device path)");
+      if (p == 13 && !spatialOcclusion)   // (its values exist on the device alone: the host cannot show that occlusion stays at 0)
+        fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to occlusion (Steam Audio's occlusion / three-band transmission filters are not known here, "
+                                       "and a signal's values cannot be shown to stay at 0)");
     }
-    r.probeDelays = probeDelays;
-    if (!loopProbeDelays.empty()) {
-      for (size_t id = 0; id < loopProbeCone.size(); id++)
-        if (loopProbeCone[id]) r.stage1[id] = 1;
-      r.loopProbe = true;
+    const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+    if (!hb) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
+    if ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps)
+      fail(GA_ERR_UNSUPPORTED, who + "the HRIR set does not fit hrirAzimuths (channels must be a multiple of 2 * hrirAzimuths, 1 .. 512 frames)");
+    const ParamS& oc = nd.params[13];
+    bool occluded = oc.events.empty() ? oc.value > 0.0f : false;
+    if (!oc.events.empty()) {
+      double t = currentTime;   // the accumulated block clock (AudioContextBase.cs:78-79), as chunkSimulate builds it
+      for (int64_t b = 0; b < r.n && !occluded; b++, t += increment) occluded = param_value_at(oc.events.data(), (int)oc.events.size(), oc.value, t) > 0.0f;
     }
+    if (occluded && !spatialOcclusion)
+      fail(GA_ERR_UNSUPPORTED, who + "occlusion > 0 (Steam Audio's occlusion / three-band transmission filters are not known here)");
   }
-  if (!r.stage1.empty() && !r.loopProbe) {
-    // A feedback loop lies entirely inside stage 1's set or entirely outside it (the set is closed upstream; a loop through a modulated
-    // source is refused above, a delay on a loop is not accepted): a loop outside is stage 2's alone, the same walk from the destination
-    // as a one-pass chunk.  A loop inside is stage 1's, and stage 1 has to enter the set where the reference's walk does
-    // (Sim::evalProbe): the nodes of the set first reached from a node outside it, in the order the walk reaches them.
-    // (A chunk with an accepted delay on a loop, ChunkRun::loopProbe, has loops that lie partly in each stage: stage 1 walks from the
-    // destination and passes through the nodes outside the set, Sim::passThrough.)
-    bool coneLoop = false;
-    for (int id : staleProducers) coneLoop = coneLoop || r.stage1[id];
-    if (coneLoop)
-      for (const auto& e : topoRefEntry)
-        if (r.stage1[e.first] && (e.second < 0 || !r.stage1[e.second])) r.coneRoots.push_back(e.first);
-  }
-  // ---- SpatialPannerNode: what the device path does not render is refused here, while nothing has moved ----
-  if (topoHasSpatial) {
-    const double increment = (double)kBlock / sampleRate;
-    for (int id : topo) {
-      if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
-      SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
-      // (decided here, on the graph as the chunk finds it: a modulator that ends inside the chunk is disconnected by the simulation,
-      // and the blocks before that still read it)
-      nd.spSignals = spatialSignalDriven(nd);
-      const std::string who = "SpatialPannerNode " + std::to_string(id) + ": ";
-      for (int p = 0; p < GA_SPATIAL_PARAM_COUNT; p++) {
-        if (nd.params[p].modulation.empty()) continue;
-        if (!spatialParamSignals)
-          fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to parameter " + std::to_string(p) + " (signals on the node's parameters are not on the device path)");
-        if (p == 13 && !spatialOcclusion)   // (its values exist on the device alone: the host cannot show that occlusion stays at 0)
-          fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to occlusion (Steam Audio's occlusion / three-band transmission filters are not known here, "
-                                         "and a signal's values cannot be shown to stay at 0)");
-      }
-      const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
-      if (!hb) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
-      if ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps)
-        fail(GA_ERR_UNSUPPORTED, who + "the HRIR set does not fit hrirAzimuths (channels must be a multiple of 2 * hrirAzimuths, 1 .. 512 frames)");
-      const ParamS& oc = nd.params[13];
-      bool occluded = oc.events.empty() ? oc.value > 0.0f : false;
-      if (!oc.events.empty()) {
-        double t = currentTime;   // the accumulated block clock (AudioContextBase.cs:78-79), as chunkSimulate builds it
-        for (int64_t b = 0; b < r.n && !occluded; b++, t += increment) occluded = param_value_at(oc.events.data(), (int)oc.events.size(), oc.value, t) > 0.0f;
-      }
-      if (occluded && !spatialOcclusion)
-        fail(GA_ERR_UNSUPPORTED, who + "occlusion > 0 (Steam Audio's occlusion / three-band transmission filters are not known here)");
-    }
-  }
-  // automated runs that ended hand their state back to the host: only nodes whose state went to the device are looked at
-  // (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp, DynStamp::dynSeq, not a flag to reset)
+}
+
+// automated runs that ended hand their state back to the host (the one step of the pass that touches the device): only nodes whose
+// state went to the device are looked at (Context::deviceStateNodes; "this chunk ran the per-sample kernel" is a stamp,
+// DynStamp::dynSeq, not a flag to reset)
+void Context::fetchDeviceState() {
   for (size_t i = 0; i < deviceStateNodes.size();) {
     const int id = deviceStateNodes[i];
     NodeS* np = id < (int)nodes.size() ? nodes[id].get() : nullptr;
@@ -624,7 +223,6 @@ void Context::chunkTopology(ChunkRun& r) {
       }
     }
   }
-
 }
 
 // pass 2: block clock, source timelines, control-plane simulation -> segments (from here on control state moves)
@@ -737,7 +335,7 @@ void Context::chunkSimulate(ChunkRun& r) {
       // -- its records are taken over, the traversal is skipped
       bool replayed = false;
       if (b == 0 && r.stage == 0 && simReplay && lastSegStable && !lastSegNodes.empty() && lastSegEpoch == apiEpoch && lastSegGraphVersion == graphVersion &&
-          !topoHasStreams && lastSegNodes.size() == topo.size() && g == goneAt.end()) {
+          !topology.hasStreams && lastSegNodes.size() == topo.size() && g == goneAt.end()) {
         bool same = true;
         for (const NodeSeg& ns : lastSegNodes) {   // every source still in the phase (and on the buffer) the records say
           if (ns.type == GA_NODE_DELAY) {
@@ -806,7 +404,7 @@ void Context::chunkSimulate(ChunkRun& r) {
           else sim.evalNode(0);
         } catch (...) {
           inRender = false;
-          topoVersion = 0;   // nodes may be left marked as processing: rebuild (and reset) everything next time
+          topology.version = 0;   // nodes may be left marked as processing: rebuild (and reset) everything next time
           throw;
         }
         inRender = false;
@@ -1321,8 +919,8 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   chunkCommit(r);
   curveListTopoSize = ~(size_t)0;
   r1.ex.reset();
-  for (int id : probeDelays) rec<DelayS>(*nodes[id]).delayProbe = false;
-  probeDelays.clear();
+  for (int id : topology.probeDelays) rec<DelayS>(*nodes[id]).delayProbe = false;
+  topology.probeDelays.clear();
   chunkRetire(r);
   lastSegStable = false;   // (the last segment's records hold stage 2's nodes only: no first-block replay in the next chunk)
 }

@@ -279,7 +279,7 @@ struct Sim {
                        !ns.pinSilent(0) || !ns.pinSilent(1) || !ns.pinSilent(2) ||   // a modulated parameter moves per sample
                        bq.dynSeq == c.chunkSeq ||   // (went dynamic earlier in this chunk: the coefficient state lives on the device until the chunk ends)
                        // the coefficient state is on the device and a signal is still connected to a parameter (silent right now):
-                       // the per-sample kernel serves constants too, and the state is not fetched back per chunk (Context::chunkTopology)
+                       // the per-sample kernel serves constants too, and the state is not fetched back per chunk (Context::fetchDeviceState)
                        (bq.coefOnDevice && (!bq.params[0].modulation.empty() || !bq.params[1].modulation.empty() || !bq.params[2].modulation.empty()));
         if (ns.bqDynamic && !ns.ins[0].silent) bq.dynSeq = c.chunkSeq;
         if (!ns.ins[0].silent && ns.bqDynamic) {
@@ -377,7 +377,7 @@ struct Sim {
         pn.outputs[0].zero = ns.ins[0].zero;
         ns.panMode = ns.ins[0].bufCh == 1 ? 1 : 2;
         if (!ns.ins[0].silent && (!pn.params[0].events.empty() || !ns.pinSilent(0) || pn.dynSeq == c.chunkSeq ||
-                                  (pn.panOnDevice && !pn.params[0].modulation.empty()))) {   // (state on the device, a signal still connected: Context::chunkTopology)
+                                  (pn.panOnDevice && !pn.params[0].modulation.empty()))) {   // (state on the device, a signal still connected: Context::fetchDeviceState)
           pn.dynSeq = c.chunkSeq;
           ns.panDyn = true;   // gains follow the a-rate curve on the device (stereo_panner_dynamic_kernel)
         } else if (!ns.ins[0].silent) {
@@ -504,7 +504,7 @@ struct Sim {
         if (audible && !wasAudible) {
           if (dl.delayProbe) {
             dl.delaySpans.back().rise = brel;
-          } else if (c.delayFlagExact && dl.delayPredChunk != c.stats.chunks) {   // (a node that was not accepted: chunkTopology says why)
+          } else if (c.delayFlagExact && dl.delayPredChunk != c.stats.chunks) {   // (a node that was not accepted: Topology::acceptDelays says why)
             dl.delayPredChunk = c.stats.chunks;
             c.stats.delay_flags_predicted++;
           }

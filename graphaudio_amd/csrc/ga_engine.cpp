@@ -768,10 +768,10 @@ void Context::refOrderSensitivity(const std::vector<int>& topo) {
   }
   // (a graph with feedback: the sweep follows the reference's processing order of the WHOLE graph -- the planning order may have cut
   // loops at DelayNodes, and the second stage of a two-stage chunk plans only the nodes outside the modulator cone)
-  const std::vector<int>& order = (topoHasCycles && topoRefOrder.size() == topoCache.size()) ? topoRefOrder : topo;
+  const std::vector<int>& order = (topology.hasCycles && topology.refOrder.size() == topology.order.size()) ? topology.refOrder : topo;
   // A loop multiplies what enters it by 1 / (1 - gain): only where the estimated loop gain (Context::chunkTopology: constant gains,
   // filter boosts) comes near 1 does a last-bit difference grow -- a master echo at 0.5 doubles it and is left alone.
-  const bool wildLoops = topoHasCycles && loopGainBound >= 0.7;
+  const bool wildLoops = topology.hasCycles && topology.loopGainBound >= 0.7;
   std::vector<char>& sens = refSensScratch;
   sens.assign(nodes.size(), 0);
   for (auto it = order.rbegin(); it != order.rend(); ++it) {   // consumers before producers

@@ -31,6 +31,7 @@
 #include "../../include/graphaudio_hip.h"
 #include "ga_kernels.hpp"
 #include "ga_gsr.hpp"
+#include "ga_topology.hpp"
 
 namespace ga {
 
@@ -159,7 +160,7 @@ struct NodeS {
   bool disposed = false;
   bool isProcessing = false;
   bool reachable = false;
-  bool prevReachable = false;   // reachable in the topology the PREVIOUS chunk ran on (= it was evaluated there; chunkTopology)
+  bool prevReachable = false;   // reachable in the topology the PREVIOUS chunk ran on (= it was evaluated there; Topology::analyse)
   int level = 0, depth = 0;
   int64_t lastProcessedBlock = -1;
   std::vector<InputS> inputs;
@@ -254,11 +255,11 @@ struct DelayS : NodeS {   // DelayNode.cs:13-15
   int delayCh = 0;                 // channels of `_outputBuffer` (re-rented, i.e. silent again, when the count changes)
   int delayRings = 0;              // CircularBuffers allocated so far (2 at construction, grown on demand)
   bool delayAudible = false;       // the output buffer's non-silent flag (sticky, :96-97)
-  // option "delay_flag_exact": the flag of this chunk is read from the node's output samples (Context::chunkTopology accepts the node
+  // option "delay_flag_exact": the flag of this chunk is read from the node's output samples (Topology::acceptDelays accepts the node
   // per chunk; delay_onset_kernel).  While accepted the simulation's PREDICTED flag lives in delayShadow, not in delayAudible.
   bool delayProbe = false;
   bool delayShadow = false;
-  bool delayOnLoop = false;        // (chunkTopology) among the stack nodes of a back edge (a loop closed through a finished node is found by the acceptance walk)
+  bool delayOnLoop = false;        // (DestinationWalk, ga_topology.cpp) among the stack nodes of a back edge (a loop closed through a finished node is found by the acceptance walk)
   struct DelaySpan {               // the blocks between two re-rents of `_outputBuffer` inside the chunk (:50-56: the flag starts down)
     int64_t b0;                    // first block (chunk-relative)
     int64_t rise;                  // block in which the prediction raises the flag, -1 = not in this span
@@ -399,12 +400,12 @@ struct SpatialPannerS : NodeS, FedState, IrRef {
   int spHistCur = 0;
   // Parameters driven by signals (option "spatial_param_signals"): spatial_desc_kernel makes the descriptors, and the VALUES of
   // spPrev (idx, w, g, beta) live on the device while spOnDevice is set -- double buffered, one job reads spCarry[spCarryCur] and
-  // writes the other.  spPrev.valid stays the host's.  Context::chunkTopology fetches the values back once when the last signal
+  // writes the other.  spPrev.valid stays the host's.  Context::fetchDeviceState fetches the values back once when the last signal
   // is disconnected (deviceStateNodes).
   SpatialCarry* spCarry[2] = {nullptr, nullptr};
   int spCarryCur = 0;
   bool spOnDevice = false;
-  bool spSignals = false;                  // per chunk (Context::chunkTopology): this chunk's descriptors are made on the device
+  bool spSignals = false;                  // per chunk (Context::refuseSpatialPanners): this chunk's descriptors are made on the device
   // Occlusion and transmission (option "spatial_occlusion"): the EQ triple of the previous processed block (valid as spPrev.valid) and,
   // per input channel (bit ch), whether that block was active -- its run of the band filters continues.  The filters' states live in
   // spDirect on the device; while spEqOnDevice is set (a signal-driven node) the triple and the run flags live there as well and
@@ -930,13 +931,6 @@ struct Context {
   bool spBandsMade = false;
   int delayFlagExact = 0;        // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology);
                                  // 1 = delays on no feedback loop, 2 = also delays on a loop, in chunks of one block
-  std::vector<int> probeDelays;  // the DelayNodes accepted for the current chunk (DelayS::delayProbe)
-  // delay_flag_exact = 2, a graph with feedback (walked every chunk, chunkTopology): the edges of the reference's walk that read their
-  // producer's previous block, as (consumer << 32 | producer), sorted; the DelayNodes on a loop accepted for this chunk and the union of
-  // their cones over the other edges
-  std::vector<uint64_t> topoStaleEdges;
-  std::vector<int> loopProbeDelays;
-  std::vector<char> loopProbeCone;
   bool rateModWalk = true;     // option "rate_mod_walk": a modulated playbackRate is replayed on the device (gsr_walk_kernel); 0 = on the host
   bool resampleFast = true;   // option "resample_fast": one lane per output sample from the trajectory's per-sample table
   void assignConvPaths(const std::vector<int>& topo, int64_t chunkBlocks);
@@ -1037,6 +1031,8 @@ struct Context {
   void runChunkImpl(int64_t nblocks, float* const* bus);
   // the passes of one chunk (ga_chunk.cpp, ga_plan_nodes.cpp, ga_plan_conv.cpp; ChunkRun holds what they share)
   void chunkTopology(ChunkRun& r);
+  void refuseSpatialPanners(const ChunkRun& r);   // (chunkTopology: what is no graph analysis)
+  void fetchDeviceState();
   void chunkSimulate(ChunkRun& r);
   void chunkResources(ChunkRun& r);
   void chunkParamCurves(ChunkRun& r);
@@ -1054,7 +1050,6 @@ struct Context {
   float spatialParamAt(const NodeS& nd, int p, double t) const;   // the k-rate value of a block: sample 0 of the timeline (event values are clamped when they are scheduled)
   // the listener transform (SteamAudioContext.cs:45-54, options listener_*): origin, right, up, ahead
   float listener[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1};
-  bool topoHasSpatial = false;
   void planBufferSource(NodePlanCtx& k);
   void planStreamSource(NodePlanCtx& k);
   void planGain(NodePlanCtx& k);
@@ -1070,11 +1065,6 @@ struct Context {
   void chunkRetire(ChunkRun& r);
   void runTwoStageChunk(ChunkRun& r);
   void chunkRateProbe(ChunkRun& r);
-  // sources whose k-rate playbackRate is modulated by a signal (chunkTopology): (node, param), cached with the graph version, and the
-  // cone of nodes their modulation inputs depend on (rendered by the first stage of a two-stage chunk)
-  std::vector<std::pair<int, int>> topoRateMods;
-  std::vector<char> rateCone;
-  uint64_t rateModsVersion = ~0ull;
   // the first stage's results: rates [mods][blocks] and walk summaries on the device (then the walks' descriptors), and their
   // page-locked copy on the host
   void* rateModDev = nullptr;
@@ -1135,9 +1125,8 @@ struct Context {
   std::vector<const NodeSeg*> fuseSeg;
   std::vector<int> fuseAbs, fuseLen;
   uint32_t fuseEpoch = 0;
-  uint64_t graphVersion = 1, topoVersion = 0;   // connections / disposals / IR changes bump graphVersion
-  std::vector<int> topoCache;
-  int topoMaxDepth = 0, topoMaxLevel = 0;
+  uint64_t graphVersion = 1;   // connections / disposals / IR changes bump graphVersion
+  Topology topology;           // what the graph analysis found (ga_topology.hpp): every cached result of chunkTopology
   std::deque<int> endedQueue;  // sources whose Ended was raised and not yet reported through ga_poll_ended
   uint64_t lastHash = 0;       // control-state hash of the last block of the previous chunk
   // Steady renders: the control-plane records of the previous chunk's LAST segment (kept instead of being recycled).  When nothing
@@ -1151,15 +1140,6 @@ struct Context {
   uint64_t apiEpoch = 0;       // bumped by every API call that can change what a render computes (ga_api.cpp guard) and by drained commands
   bool simReplay = true;       // option "sim_replay"
   bool twinChannels = true;    // option "twin_channels": channels that carry the same signal from the same state are evaluated once
-  bool topoHasTimeNodes = false, topoHasConvolvers = false, topoHasOscillators = false, topoHasStreams = false;
-  bool topoHasCycles = false;   // (chunkTopology) some node is pulled while it is being processed: chunks of ONE block (the reference's own granularity)
-  std::vector<int> staleProducers;
-  std::vector<int> staleLeavers;   // nodes that were evaluated in the previous chunk and are not in this one (an edit took them out of
-                                   // the graph): their output buffers keep the last block, which a later loop through them would read
-  double loopGainBound = 0.0;   // (chunkTopology) the largest estimated gain of a feedback loop: differences that enter it grow by 1 / (1 - gain)
-  std::vector<int> topoRefOrder;   // the reference-order walk of a graph with feedback (the planning order may cut loops at DelayNodes)
-  std::vector<std::pair<int, int>> topoRefEntry;   // ... the same walk's (node, the node it was first reached from, -1 = none) in entry order
-  int cycleBlocks = 1;          // blocks per chunk of a graph with feedback (1 unless every loop is cut at a DelayNode)
   bool cycleDelaySplit = true;  // option "cycle_delay_split"
   // the output views of the previous chunk's last segment (and the gains folded into them): when an edit closes a cycle, the block
   // the new stale producer put out LAST is still in those slabs (Context::chunkStaleSeed)
@@ -1168,12 +1148,10 @@ struct Context {
   std::vector<const float*> lastViewCurve;   // (a GainNode folded into its consumer with a gain CURVE: its output is view x curve)
   int64_t lastViewFrames = 0;
   uint64_t slabGen = 0, lastViewSlabGen = ~0ull;   // (slabGen: bumped when the slab pool is reallocated -- old views dangle)
-  uint64_t topoStatsVersion = ~0ull;
-  size_t topoStatsSize = 0;
   std::vector<std::pair<int, int>> curveList;   // (node, parameter) pairs with a timeline among the reachable nodes (chunkParamCurves)
   uint64_t curveListEpoch = ~0ull, curveListGraphVersion = ~0ull;
   size_t curveListTopoSize = 0;
-  std::vector<int> deviceStateNodes;   // nodes whose pan gains / biquad coefficients live on the device (panOnDevice / coefOnDevice)   // (chunkTopology) delay / stream-source nodes ; convolvers with an impulse response
+  std::vector<int> deviceStateNodes;   // nodes whose pan gains / biquad coefficients live on the device (panOnDevice / coefOnDevice): Context::fetchDeviceState
   int chunkMinDestCh = 0;      // smallest destination channel count over the blocks of the last chunk
   int64_t chunkBlocksDone = 0; // blocks actually executed by the last runChunk
 };

@@ -1026,7 +1026,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
 
   // ---- convolver scratch planes are shared by all groups: size them for the largest group BEFORE any recorded
   //      launch captures their address ----
-  if (topoHasConvolvers && r.stage != 1) {   // (no convolver in the first stage of a two-stage chunk: chunkTopology) (a graph without convolvers -- tens of thousands of nodes of config 4 -- skips these sweeps)
+  if (topology.hasConvolvers && r.stage != 1) {   // (no convolver in the first stage of a two-stage chunk: chunkTopology) (a graph without convolvers -- tens of thousands of nodes of config 4 -- skips these sweeps)
     refOrderSensitivity(topo);
     migrateConvolvers(topo);   // (option "conv_migrate": before the paths, the fusion groups and the scratch sizes are decided)
     assignConvPaths(topo, n);
@@ -1046,7 +1046,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
     aliasBusToLeader(r);
   }
   bHistMax = 0;
-  if (topoHasConvolvers) {
+  if (topology.hasConvolvers) {
     size_t xMax = 0, yMax = 0;
     size_t bx = 0, by = 0;
     for (int id : topo) {
@@ -1134,7 +1134,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
     }
   }
 
-  if (topoHasOscillators)
+  if (topology.hasOscillators)
   for (int id : topo) {  // OscillatorNode._phase lives on the device (one double, zero at Start)
     if (nodes[id]->type != GA_NODE_OSCILLATOR) continue;
     OscillatorS& nd = rec<OscillatorS>(*nodes[id]);

@@ -951,7 +951,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
       fuseLen[b_.id] = la_ + 1;
     }
     int curLevel = -1, levelBqHeads = 0;
-    if (d == 0 && topoHasCycles && cycleBlocks > 1) {   // the readers of the DelayNodes at which this chunk's loops are cut: sources
+    if (d == 0 && topology.hasCycles && topology.cycleBlocks > 1) {   // the readers of the DelayNodes at which this chunk's loops are cut: sources
       for (const NodeSeg& ns : sg.nodes) {
         NodeS& nd = *nodes[ns.id];
         if (nd.type != GA_NODE_DELAY || !rec<DelayS>(nd).delaySplit) continue;
@@ -981,7 +981,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
         }
       }
       auto& ov = ex.outViews[si][ns.id];
-      const bool cutDelay = nd.type == GA_NODE_DELAY && rec<DelayS>(nd).delaySplit && topoHasCycles && cycleBlocks > 1;   // (its reader set the views)
+      const bool cutDelay = nd.type == GA_NODE_DELAY && rec<DelayS>(nd).delaySplit && topology.hasCycles && topology.cycleBlocks > 1;   // (its reader set the views)
       if (!cutDelay) ov.assign(nd.type == GA_NODE_CHANNEL_SPLITTER ? (int)nd.outputs.size() : std::max(ns.outCh, 1), nullptr);
       NodePlanCtx k{r, ex, si, sg, f0, nf, nb, ns, nd, ov, segNode, absorbedBy, levelBqHeads};
       if (cutDelay) k.delayPhase = 2;
@@ -1055,7 +1055,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
 // overwritten yet when this chunk's first launch runs -- copied from there (only from memory the context knows to be alive: slabs
 // and other producers' kept blocks; a zero-copy view of a sample buffer, which may have been released since, is not chased).
 void Context::chunkStaleSeed(ChunkRun& r) {
-  if (staleProducers.empty() && staleLeavers.empty()) return;
+  if (topology.staleProducers.empty() && topology.staleLeavers.empty()) return;
   Exec& ex = *r.ex;
   std::vector<StaleJob> jobs;
   auto alive = [&](const float* p) {
@@ -1104,13 +1104,13 @@ void Context::chunkStaleSeed(ChunkRun& r) {
   //   it was evaluated in the chunk before, in no loop
   //     or in a loop that was entered somewhere else      its last block is in the previous chunk's views (fuzz sessions 60001, 61173)
   //   it was out of the graph (unplugged) for a while     the block it had when it LEFT: kept at that moment (staleLeavers, below)
-  for (int id : staleProducers) {
+  for (int id : topology.staleProducers) {
     NodeS& nd = *nodes[id];
     if (nd.staleBuf && nd.staleSeq + 1 == chunkSeq) continue;
     if (nd.prevReachable || !nd.staleBuf) keepLastBlock(nd);
   }
   // nodes an edit has just taken out of the graph: what their output buffers hold stays there until they are evaluated again
-  for (int id : staleLeavers) {
+  for (int id : topology.staleLeavers) {
     NodeS& nd = *nodes[id];
     if (nd.staleBuf && nd.staleSeq + 1 == chunkSeq) continue;   // (a stale producer of the previous chunk: kept already)
     if (!haveLast || id >= (int)lastViews.size()) continue;
@@ -1118,7 +1118,7 @@ void Context::chunkStaleSeed(ChunkRun& r) {
     for (const float* v : lastViews[id]) any = any || v != nullptr;
     if (any || nd.staleBuf) keepLastBlock(nd);   // (silent and never kept: nothing to remember -- a later seed reads zeros)
   }
-  staleLeavers.clear();
+  topology.staleLeavers.clear();
   hipStream_t st = stream;
   ex.flush(jobs, LK_OTHER, nullptr, [=](const StaleJob* t, int nj, int64_t, uint8_t*) { launch_stale_copy(st, t, nj); });
 }
@@ -1127,11 +1127,11 @@ void Context::chunkStaleSeed(ChunkRun& r) {
 // it is being processed will mix in the next block (TermS::stale).  Written to the OTHER copy: a pass-through node may hand on a
 // view of another producer's current copy, and the jobs of one launch are not ordered.
 void Context::chunkStaleCommit(ChunkRun& r) {
-  if (staleProducers.empty()) return;
+  if (topology.staleProducers.empty()) return;
   Exec& ex = *r.ex;
   std::vector<StaleJob> jobs;
   const int si = (int)r.segs.size() - 1;
-  for (int id : staleProducers) {
+  for (int id : topology.staleProducers) {
     NodeS& nd = *nodes[id];
     const int rows = nd.type == GA_NODE_CHANNEL_SPLITTER ? std::max<int>(1, (int)nd.outputs.size()) : 32;
     if (!nd.staleBuf || nd.staleRows < rows) {
