@@ -141,6 +141,35 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _spatialBuiltinHrir;
+    /// <summary>Option "spatial_builtin_hrir" (default off): a SpatialPannerNode that has no HRIR set of its own renders on the
+    /// library's built-in set -- an analytic spherical-head model (Brown and Duda) on a grid of 72 azimuths x 25 elevations, made on the
+    /// device at the context's sample rate -- instead of being refused.  A node that has a set keeps it.  The set is this library's own
+    /// definition, not Steam Audio's default HRTF (DESIGN.md section 2e, "The built-in set").</summary>
+    public bool SpatialBuiltinHrir
+    {
+        get => _spatialBuiltinHrir;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "spatial_builtin_hrir", value ? 1 : 0));
+            _spatialBuiltinHrir = value;
+        }
+    }
+
+    private double _spatialHeadRadius = 0.0875;
+    /// <summary>Option "spatial_head_radius": the head radius of the built-in HRIR set in metres, 0.04 .. 0.20 (default 0.0875; outside
+    /// the range: ArgumentOutOfRangeException).  A change remakes the set in front of the next block that needs it; nodes on the set
+    /// take it up without a crossfade, as after any change of their HRIR set.</summary>
+    public double SpatialHeadRadius
+    {
+        get => _spatialHeadRadius;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "spatial_head_radius", value));
+            _spatialHeadRadius = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

@@ -139,6 +139,60 @@ class HrirSet(PlayableAudioBuffer):
             raise ArgumentException("hrir must have shape [directions][2][taps]")
         return HrirSet(list(a.reshape(a.shape[0] * 2, a.shape[2])), sampleRate)
 
+    # the built-in set's grid ("The built-in set"): 72 azimuths x 25 elevation rings
+    SPHERICAL_HEAD_AZIMUTHS = 72
+    SPHERICAL_HEAD_ELEVATIONS = 25
+    Azimuths = 1   # of a set made by SphericalHead: its azimuth count, what SpatialPannerNode.HrirAzimuths has to be for it
+
+    @staticmethod
+    def SphericalHead(sampleRate: int, headRadius: float = 0.0875) -> "HrirSet":
+        """The set the native library makes for itself under option "spatial_builtin_hrir" (Brown & Duda's spherical-head model, DESIGN.md
+        section 2e "The built-in set"), tap for tap, as a set of the host's: to look at, to edit, or to assign explicitly
+        (`p.HrirAzimuths = s.Azimuths; p.Hrir = s`).  Evaluated in float64, every tap rounded to float32 once."""
+        fs, a = float(sampleRate), float(headRadius)
+        if not fs > 0:
+            raise ArgumentOutOfRangeException("sampleRate")
+        if not 0.04 <= a <= 0.20:
+            raise ArgumentOutOfRangeException("headRadius is 0.04 .. 0.20 (metres)")
+        A, E, c, half = HrirSet.SPHERICAL_HEAD_AZIMUTHS, HrirSet.SPHERICAL_HEAD_ELEVATIONS, 343.0, 8
+        beta = 2.0 * c / a
+        a1 = (beta - 2.0 * fs) / (beta + 2.0 * fs)
+        # length: the longest delay, the interpolation kernel's 16 taps, the shadow filter's tail down to 2^-14; at most 512
+        tail, q = 0, 1.0
+        while q > 2.0 ** -14:
+            q *= abs(a1)
+            tail += 1
+        longest = math.ceil(fs * (a / c) * (1.0 + 0.5 * math.pi))
+        T = min(512, 8 * int(math.ceil((longest + 2 * half + tail) / 8.0)))
+        channel = np.arange(2 * A * E)
+        direction = channel // 2
+        az = np.radians(360.0 * (direction % A) / A)
+        el = np.radians(-90.0 + 180.0 * (direction // A) / (E - 1))
+        ux = np.sin(az) * np.cos(el)                       # u . e_R ; the left ear sees -ux
+        theta = np.arccos(np.clip(np.where(channel % 2 == 1, ux, -ux), -1.0, 1.0))
+        tau = np.where(theta < 0.5 * np.pi, (a / c) * (1.0 - np.cos(theta)), (a / c) * (1.0 + theta - 0.5 * np.pi))
+        alpha = 1.05 + 0.95 * np.cos(theta * (180.0 / 150.0))
+        b0 = (beta + 2.0 * fs * alpha) / (beta + 2.0 * fs)
+        b1 = (beta - 2.0 * fs * alpha) / (beta + 2.0 * fs)
+        c1 = b1 - a1 * b0
+        centre = half + fs * tau
+        first = np.floor(centre) - half
+        k = np.arange(T, dtype=np.float64)
+        h = np.zeros((channel.size, T))
+        for j in range(2 * half + 1):                      # ascending n: h[k] += p[n] g[k - n]
+            n = first + j
+            x = n - centre
+            px = np.pi * x
+            with np.errstate(invalid="ignore", divide="ignore"):
+                sinc = np.where(x == 0.0, 1.0, np.sin(px) / px)
+            p = np.where(np.abs(x) < half, sinc * 0.5 * (1.0 + np.cos(px / half)), 0.0)
+            m = (k[None, :] - n[:, None]).astype(np.int64)
+            g = np.where(m == 0, b0[:, None], np.where(m > 0, c1[:, None] * np.power(-a1, np.maximum(m - 1, 0)), 0.0))
+            h += p[:, None] * g
+        s = HrirSet(list(h.astype(np.float32)), int(sampleRate))
+        s.Azimuths = A
+        return s
+
 
 class AudioParam:
     """AudioParam (AudioParam.cs:11-392): value + automation timeline, evaluated natively."""
@@ -484,7 +538,9 @@ class DistanceModelType(enum.IntEnum):  # SpatialPannerNode.cs:42-47
 class SpatialPannerNode(AudioNode):
     """SpatialPannerNode (GraphAudio.SteamAudio/Nodes/SpatialPannerNode.cs:10-305): the reference's parameter surface and
     geometry; the binaural stage runs on a caller-supplied HRIR set (``Hrir`` / ``HrirAzimuths``, or the context's
-    ``SetHrir``) instead of Steam Audio's built-in HRTF -- DESIGN.md "SpatialPannerNode"."""
+    ``SetHrir``) instead of Steam Audio's built-in HRTF -- DESIGN.md "SpatialPannerNode".  A node without a set renders on the
+    library's built-in spherical-head set once the context has ``SetOption("spatial_builtin_hrir", 1)`` (``HrirSet.SphericalHead``
+    is the same set on the host); without the option it is refused at render time."""
     _node_type = _capi.NODE_SPATIAL_PANNER
     _FMAX = float(np.finfo(np.float32).max)
     # (name, default, min, max), all k-rate: SpatialPannerNode.cs:94-110 (float.MinValue is -float.MaxValue)

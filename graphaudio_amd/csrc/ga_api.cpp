@@ -172,6 +172,7 @@ void Context::processBlocks(float* const* outPlanar, float* outInterleaved, int 
     GA_HIP(hipStreamSynchronize(stream));
     doneBlocks += done;
   }
+  if (blockCount > 0) freeRetired();   // (the stream is idle)
   stats.device_bytes_in_use = devBytes;
 }
 
@@ -292,6 +293,7 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
   if (!pipelined.callerAsync) {
     GA_HIP(hipStreamSynchronize(stream));
     harvestProfile(true);
+    freeRetired();   // (the stream is idle: what this call replaced -- a built-in HRIR set of another head radius, a sample table that doubled -- goes now)
   }
   stats.device_bytes_in_use = devBytes;
 }
@@ -381,6 +383,15 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "libm_exact") {
       if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "libm_exact is 0 or 1");
       c.libmExact = value != 0;
+    }
+    else if (k == "spatial_builtin_hrir") {
+      if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "spatial_builtin_hrir is 0 or 1");
+      if (c.spatialBuiltinHrir != (value != 0)) c.spHeadEpoch++;   // (a node that was on the built-in set finds its set changed)
+      c.spatialBuiltinHrir = value != 0;
+    }
+    else if (k == "spatial_head_radius") {
+      if (!(value >= kSpatialHeadRadiusMin && value <= kSpatialHeadRadiusMax)) fail(GA_ERR_OUT_OF_RANGE, "spatial_head_radius is 0.04 .. 0.20 (metres)");
+      c.spatialHeadRadius = value;   // (the set is remade in front of the next chunk that needs it)
     }
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);

@@ -121,6 +121,7 @@ void Context::chunkTopology(ChunkRun& r) {
 void Context::refuseSpatialPanners(const ChunkRun& r) {
   if (!topology.hasSpatial) return;
   const double increment = (double)kBlock / sampleRate;
+  bool builtin = false;   // some node has no set of its own
   for (int id : r.topo) {
     if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
     SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
@@ -137,9 +138,10 @@ void Context::refuseSpatialPanners(const ChunkRun& r) {
                                        "and a signal's values cannot be shown to stay at 0)");
     }
     const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
-    if (!hb) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
-    if ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps)
+    if (!hb && !spatialBuiltinHrir) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
+    if (hb && ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps))
       fail(GA_ERR_UNSUPPORTED, who + "the HRIR set does not fit hrirAzimuths (channels must be a multiple of 2 * hrirAzimuths, 1 .. 512 frames)");
+    builtin = builtin || !hb;
     const ParamS& oc = nd.params[13];
     bool occluded = oc.events.empty() ? oc.value > 0.0f : false;
     if (!oc.events.empty()) {
@@ -149,6 +151,67 @@ void Context::refuseSpatialPanners(const ChunkRun& r) {
     if (occluded && !spatialOcclusion)
       fail(GA_ERR_UNSUPPORTED, who + "occlusion > 0 (Steam Audio's occlusion / three-band transmission filters are not known here)");
   }
+  // Nothing is refused: which set every node renders this chunk with.  A node without a set of its own is on the built-in one (option
+  // "spatial_builtin_hrir"), with that set's azimuth count whatever its own hrirAzimuths.  A node that was on another set in its last
+  // chunk -- its own, or the built-in one before the radius changed or the option was switched -- had its HRIR set changed (DESIGN.md
+  // section 2e): the next processed block uses its own filters alone, the input history carries over.
+  if (builtin) ensureSpatialHeadSet();
+  for (int id : r.topo) {
+    if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
+    SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
+    const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+    nd.spSet = hb ? hb : &spHeadSet;
+    nd.spAzimuths = hb ? nd.hrirAzimuths : kSpatialHeadAzimuths;
+    const uint64_t epoch = hb ? 0 : spHeadEpoch;
+    if (nd.spSetEpoch != epoch) nd.spPrev.valid = false;
+    nd.spSetEpoch = epoch;
+  }
+}
+
+// The built-in set for the context's rate and the current head radius, made on the context's stream in front of the chunk that needs
+// it.  A copy made for another radius is retired: launches of the chunk in flight may still read it, it is freed when the stream is
+// next known to be idle (Context::freeRetired), so the memory held does not grow with the number of radius changes.
+void Context::ensureSpatialHeadSet() {
+  if (spHeadSet.dev && spHeadSetRadius == spatialHeadRadius) return;
+  const int T = spatial_head_taps((double)sampleRate, spatialHeadRadius);
+  if (spHeadSet.devBase) {
+    retired.push_back({spHeadSet.devBase, spHeadSet.devBytes});
+    spHeadSet.dev = nullptr;
+    spHeadSet.devBase = nullptr;
+    spHeadEpoch++;
+  }
+  spHeadSet.channels = 2 * kSpatialHeadDirs;
+  spHeadSet.length = T;
+  spHeadSet.stride = (T + 63) / 64 * 64;
+  spHeadSet.sampleRate = sampleRate;
+  spHeadSet.dev = dallocSkewed((size_t)spHeadSet.channels * (size_t)spHeadSet.stride * sizeof(float), &spHeadSet.devBase, &spHeadSet.devBytes);
+  launch_spatial_head(stream, spHeadSet.dev, spHeadSet.stride, T, (double)sampleRate, spatialHeadRadius);
+  GA_HIP(hipGetLastError());
+  stats.kernel_launches++;
+  spHeadSetRadius = spatialHeadRadius;
+}
+
+// SpatialPannerS::spGainBound of the nodes on the built-in set (the loop-gain estimate of the graph analysis reads it): max(1, the
+// largest sum |p| sum |g| over the set's channels).  Only when the graph, the radius or the option moved since the nodes last got it.
+void Context::spatialHeadBounds() {
+  if (!spatialBuiltinHrir || (spHeadBoundVersion == graphVersion && spHeadBoundEpoch == spHeadEpoch && spHeadBoundRadius == spatialHeadRadius)) return;
+  if (spHeadBoundRadius != spatialHeadRadius) {
+    double mx = 1.0;
+    for (int ch = 0; ch < 2 * kSpatialHeadDirs; ch++) mx = std::max(mx, spatial_head_abs_sum_bound(spatial_head_ear((double)sampleRate, spatialHeadRadius, ch)));
+    spHeadGainBound = (float)(mx * (1.0 + 1e-6));
+    spHeadBoundRadius = spatialHeadRadius;
+  }
+  bool moved = false;
+  for (auto& np : nodes) {
+    if (!np || np->disposed || np->type != GA_NODE_SPATIAL_PANNER) continue;
+    SpatialPannerS& nd = rec<SpatialPannerS>(*np);
+    if (nd.irBuf >= 0 || nd.spGainBound == spHeadGainBound) continue;
+    nd.spGainBound = spHeadGainBound;
+    moved = true;
+  }
+  if (moved) graphVersion++;   // (the analysis is cached per graph version)
+  spHeadBoundVersion = graphVersion;
+  spHeadBoundEpoch = spHeadEpoch;
 }
 
 // automated runs that ended hand their state back to the host (the one step of the pass that touches the device): only nodes whose
@@ -704,6 +767,7 @@ void Context::runChunkImpl(int64_t nblocks, float* const* /*unused*/) {
   if (!releasedPending.empty() || ++chunksSinceGc >= 64) collectGarbage();
   latched = true;
   profileNow = profile && (profileSeq++ % std::max(profileEvery, 1)) == 0;
+  spatialHeadBounds();
   chunkTopology(r);
   if (!r.rateMods.empty() || !r.probeDelays.empty()) {   // a playbackRate modulated by a signal, a DelayNode's flag read from its samples: their cones first (runTwoStageChunk)
     runTwoStageChunk(r);

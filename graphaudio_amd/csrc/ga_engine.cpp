@@ -284,6 +284,7 @@ Context::~Context() {
   if (coarseM.p) (void)hipFree(coarseM.p);
   if (deferStage) (void)hipFree(deferStage);
   for (auto& r : retired) (void)hipFree(r.first);
+  if (spHeadSet.devBase) (void)hipFree(spHeadSet.devBase);
   for (auto& kv : resamplers)
     if (kv.second->devSamples) (void)hipFree(kv.second->devSamples);
   for (auto& np : nodes)

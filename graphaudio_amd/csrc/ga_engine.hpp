@@ -406,6 +406,12 @@ struct SpatialPannerS : NodeS, FedState, IrRef {
   int spCarryCur = 0;
   bool spOnDevice = false;
   bool spSignals = false;                  // per chunk (Context::refuseSpatialPanners): this chunk's descriptors are made on the device
+  // per chunk (Context::refuseSpatialPanners): the set the node renders with and its azimuth count -- buffer `irBuf` with hrirAzimuths,
+  // or (option "spatial_builtin_hrir", no set of its own) the context's built-in set with its 72.  spSetEpoch is carried: 0 while the
+  // last chunk used a set of the node's own, else Context::spHeadEpoch as that chunk found it.
+  const PlayBuf* spSet = nullptr;
+  int spAzimuths = 1;
+  uint64_t spSetEpoch = 0;
   // Occlusion and transmission (option "spatial_occlusion"): the EQ triple of the previous processed block (valid as spPrev.valid) and,
   // per input channel (bit ch), whether that block was active -- its run of the band filters continues.  The filters' states live in
   // spDirect on the device; while spEqOnDevice is set (a signal-driven node) the triple and the run flags live there as well and
@@ -927,6 +933,22 @@ struct Context {
     return false;
   }
   bool spatialOcclusion = false;      // option "spatial_occlusion": occlusion > 0 and the three-band transmission are rendered (spatial_direct_kernel); 0 = refused
+  // Options "spatial_builtin_hrir" / "spatial_head_radius": a SpatialPannerNode without a set of its own renders on the built-in
+  // spherical-head set (ga_spatial_head.hpp; 0 = refused).  The set is a buffer of the context's own that no caller id refers to:
+  // spatial_head_kernel fills it on the context's stream in front of the first chunk that needs it (Context::ensureSpatialHeadSet),
+  // and again after the radius changed -- the copy it replaces goes to `retired`.  spHeadEpoch names "the built-in set as a node
+  // found it": it moves when the set is remade and when the option is switched, and a node whose last processed block saw another
+  // value (SpatialPannerS::spSetEpoch) had its HRIR set changed.
+  bool spatialBuiltinHrir = false;
+  double spatialHeadRadius = kSpatialHeadRadiusDefault;
+  PlayBuf spHeadSet;
+  double spHeadSetRadius = 0.0;       // the radius spHeadSet was made for (0: not made)
+  float spHeadGainBound = 1.f;        // SpatialPannerS::spGainBound of a node on it
+  uint64_t spHeadEpoch = 1;
+  double spHeadBoundRadius = 0.0;     // the radius spHeadGainBound was worked out for, and the graph / epoch the nodes last received it at
+  uint64_t spHeadBoundVersion = ~0ull, spHeadBoundEpoch = 0;
+  void spatialHeadBounds();           // in front of the graph analysis, which reads spGainBound
+  void ensureSpatialHeadSet();
   SpatialBands spBands{};             // the band filters of that stage: fixed per context (made when the first job is planned)
   bool spBandsMade = false;
   int delayFlagExact = 0;        // option "delay_flag_exact": a DelayNode's output flag is read from its samples where the chunk can be split in two (chunkTopology);

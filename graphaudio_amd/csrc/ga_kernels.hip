@@ -2597,6 +2597,21 @@ void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nwor
 }
 
 // ======================================================================================================
+//  The built-in HRIR set (ga_spatial_head.hpp): workgroup = channel (one wavefront), lane = tap k, k + 64, ...  Every lane works out
+//  its channel's delay and shadow filter for itself and sums its tap's (at most 16) products in double: no lane reads what another
+//  wrote, no LDS.  Runs once per set and sample rate / head radius, so nothing here is tuned: 3600 x T taps of ~16 terms each.
+// ======================================================================================================
+__global__ __launch_bounds__(64) void spatial_head_kernel(float* __restrict out, int64_t stride, int taps, double fs, double a) {
+  const int ch = blockIdx.x;   // (the grid is 2 * kSpatialHeadDirs workgroups: launch_spatial_head)
+  const SpatialHeadEar e = spatial_head_ear(fs, a, ch);
+  for (int k = threadIdx.x; k < taps; k += 64) gptr(out)[(int64_t)ch * stride + k] = spatial_head_tap(e, k);
+}
+void launch_spatial_head(hipStream_t s, float* out, int64_t stride, int taps, double fs, double a) {
+  if (taps < 1 || taps > kSpatialMaxTaps || stride < taps) launch_fail("spatial_head_kernel: taps / stride");
+  hipLaunchKernelGGL(spatial_head_kernel, dim3(2 * kSpatialHeadDirs), dim3(64), 0, s, out, stride, taps, fs, a);
+}
+
+// ======================================================================================================
 //  SpatialPannerNode descriptors of signal-driven nodes (ga_kernels.hpp, SpatialDescJob): one lane per (node, block), wave64.
 //  A lane depends on no other lane of the launch: the previous block's geometry, which decides the fade, is recomputed from that
 //  block's inputs (blocks b0 + 1 ..), or read from the carried descriptor an earlier launch or the host left (block b0).

@@ -8,6 +8,7 @@
 
 #include "ga_spatial_geom.hpp"
 #include "ga_spatial_direct.hpp"
+#include "ga_spatial_head.hpp"
 #include "ga_conv_rebuild.hpp"
 
 namespace ga {
@@ -709,6 +710,12 @@ struct SpatialWork {      // one workgroup
   int tail;               // != 0: also writes hist_out
 };
 void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nworks, const SpatialJob* jobs_dev, const uint8_t* tables_dev);
+
+// The built-in HRIR set (option "spatial_builtin_hrir"; ga_spatial_head.hpp, DESIGN.md section 2e "The built-in set"):
+// spatial_head_kernel writes taps [0, taps) of the 2 * kSpatialHeadDirs channels of the spherical-head set for sample rate `fs` and
+// head radius `a` to out[channel * stride + k].  One workgroup of one wavefront per channel, a lane per tap; once per set.
+static_assert(kSpatialHeadMaxTaps == kSpatialMaxTaps, "ga_spatial_head.hpp restates the tap limit");
+void launch_spatial_head(hipStream_t s, float* out, int64_t stride, int taps, double fs, double a);
 
 // Descriptors made on the device (option "spatial_param_signals"; DESIGN.md "SpatialPannerNode", "Parameters driven by signals"):
 // a node with a signal connected to one of its parameters gets its SpatialDesc entries from spatial_desc_kernel -- one lane per

@@ -283,7 +283,7 @@ static_assert(GA_DISTANCE_LINEAR == kSpatialLinear && GA_DISTANCE_INVERSE == kSp
               GA_SPATIAL_PARAM_COUNT == kSpatialParams, "ga_spatial_geom.hpp restates the interface's constants");
 void Context::spatialGeometry(const SpatialPannerS& nd, const float* pv, int D, SpatialPannerS::SpatialPrev& o) const {
   SpatialGeom gm;
-  spatial_geometry<SpatialMathLibm>(pv, listener, nd.distanceModel, nd.hrirAzimuths, D, gm);
+  spatial_geometry<SpatialMathLibm>(pv, listener, nd.distanceModel, nd.spAzimuths, D, gm);
   for (int q = 0; q < 4; q++) {
     o.idx[q] = gm.idx[q];
     o.w[q] = gm.w[q];
@@ -336,8 +336,8 @@ void Context::spatialEqTable(Exec& ex, SpatialPannerS& nd, int64_t n) {
 void Context::planSpatialPanner(NodePlanCtx& k) {
   Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; SpatialPannerS& nd = rec<SpatialPannerS>(k.nd); Views& ov = k.ov;
   const int64_t n = k.r.n;
-  PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
-  if (!hb || hb->length < 1 || hb->length > kSpatialMaxTaps || (hb->channels & 1)) fail(GA_ERR_DEVICE, "internal: spatial panner without a valid HRIR set");
+  const PlayBuf* hb = nd.spSet;   // (the node's own set or the built-in one: Context::refuseSpatialPanners)
+  if (!hb || !hb->dev || hb->length < 1 || hb->length > kSpatialMaxTaps || (hb->channels & 1)) fail(GA_ERR_DEVICE, "internal: spatial panner without a valid HRIR set");
   const int D = hb->channels / 2;
   if (nd.spSeq != chunkSeq || nd.spExec != &ex) {   // the node's first segment in this chunk: its tables and its job
     nd.spSeq = chunkSeq;
@@ -420,7 +420,7 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
       dj.desc_off = nd.spDescOff;
       dj.b0 = (int)sg.b0;
       dj.nb = (int)(sg.b1 - sg.b0);
-      dj.azimuths = nd.hrirAzimuths;
+      dj.azimuths = nd.spAzimuths;
       dj.dirs = D;
       dj.model = nd.distanceModel;
       dj.prev_valid = nd.spPrev.valid ? 1 : 0;

@@ -189,7 +189,12 @@ GA_EXPORT int64_t GA_FN(current_block)(ga_context* ctx);       /* AudioContextBa
 GA_EXPORT int GA_FN(set_option)(ga_context* ctx, const char* key, double value); /* tuning knobs, see DESIGN.md ("coarse_long", default 1: impulse responses of 131,073 .. 1,048,576 taps take the coarse-partition formulation D as well -- segmented partition sum; 0: the direct formulations, as for longer ones;
    "libm_exact", default 0: 1 makes an automated BiQuadFilterNode and an automated StereoPannerNode compute their per-sample coefficients
    with cosf / sinf / powf as glibc >= 2.28 computes them, bit for bit, instead of the double-precision functions rounded once -- for a
-   host whose MathF.Cos / Sin / Pow are glibc's; any other value is GA_ERR_OUT_OF_RANGE; DESIGN.md section 8 "libm class") */
+   host whose MathF.Cos / Sin / Pow are glibc's; any other value is GA_ERR_OUT_OF_RANGE; DESIGN.md section 8 "libm class";
+   "spatial_builtin_hrir", default 0: 1 lets a GA_NODE_SPATIAL_PANNER without an HRIR set of its own render on the library's built-in set
+   -- an analytic spherical-head model on 72 azimuths x 25 elevations, made on the device at the context's rate -- instead of being
+   refused with GA_ERR_UNSUPPORTED; a node that has a set keeps it; any other value is GA_ERR_OUT_OF_RANGE;
+   "spatial_head_radius", default 0.0875: the head radius of that set in metres, 0.04 .. 0.20, outside GA_ERR_OUT_OF_RANGE; a change
+   remakes the set and counts as a change of the HRIR set of the nodes on it; DESIGN.md section 2e "The built-in set") */
 GA_EXPORT int GA_FN(get_stats)(ga_context* ctx, ga_stats* out);
 
 /* ---- PlayableAudioBuffer.FromChannelArrays (PlayableAudioBuffer.cs:122-145): immutable sample storage ----

@@ -60,14 +60,17 @@ elif which == "osc":   # oscillators + panners (8(f) rank 1 nodes at scale)
         o.Connect(p).Connect(g).Connect(ctx.Destination)
         o.Start()
     ch = 2
-elif which in ("spatial", "spatial_occlusion"):   # SpatialPannerNode at scale: every voice through its own node, moving, so that every block crossfades
+elif which in ("spatial", "spatial_occlusion", "spatial_builtin"):   # SpatialPannerNode at scale: every voice through its own node, moving, so that every block crossfades
     import math                                    # spatial_occlusion: every node behind a wall as well (option spatial_occlusion: spatial_direct_kernel)
     from graphaudio_amd import AudioBufferSourceNode, HrirSet, PlayableAudioBuffer, SpatialPannerNode
     n_voices = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
     T, A, E = 256, 24, 7
     k = np.arange(T)
     hrir = (np.random.default_rng(5).standard_normal((A * E, 2, T)) * np.exp(-6.9 * k / T) * 0.1).astype(np.float32)
-    ctx.SetHrir(HrirSet.FromArray(hrir, SR), A)
+    if which == "spatial_builtin":   # no set assigned: every node on the built-in spherical-head set (T = 112 at 48 kHz, 72 x 25 directions)
+        ctx.SetOption("spatial_builtin_hrir", 1)
+    else:
+        ctx.SetHrir(HrirSet.FromArray(hrir, SR), A)
     if which == "spatial_occlusion":
         ctx.SetOption("spatial_occlusion", 1)
     corners, period = 32, 5.0   # a circle as a 32-gon of linear ramps, one revolution per 5 s
@@ -88,6 +91,30 @@ elif which in ("spatial", "spatial_occlusion"):   # SpatialPannerNode at scale: 
         s.Connect(p).Connect(ctx.Destination)
         s.Start()
     ch = 2
+elif which == "spatial_head":   # what remaking the built-in set costs: one voice, one-block renders with and without a radius change in front
+    import statistics
+    from graphaudio_amd import AudioBufferSourceNode, PlayableAudioBuffer, SpatialPannerNode
+    ctx.SetOption("spatial_builtin_hrir", 1)
+    s = AudioBufferSourceNode(ctx)
+    s.Buffer = PlayableAudioBuffer.FromMonoArray(G.voice(0, 128 * 64), SR)
+    p = SpatialPannerNode(ctx)
+    p.PositionX.Value = 1.0
+    s.Connect(p).Connect(ctx.Destination)
+    s.Start()
+    out = np.zeros((2, 128 * 64), np.float32)
+    for b in range(4):
+        ctx.Render(out, 128, b * 128)
+    remake, plain = [], []
+    for i in range(12):
+        ctx.SetOption("spatial_head_radius", 0.08 if i % 2 == 0 else 0.0875)   # (sets of the same stored size)
+        for times in (remake, plain):
+            t0 = time.perf_counter()
+            ctx.Render(out, 128, (4 + 2 * i + (times is plain)) * 128)
+            times.append((time.perf_counter() - t0) * 1e3)
+    print(f"one-block render behind a radius change: median {statistics.median(remake):.3f} ms (min {min(remake):.3f}); without: median "
+          f"{statistics.median(plain):.3f} ms (min {min(plain):.3f}); a remake of the set (allocation, launch, spatial_head_kernel over 3600 x 112 "
+          f"taps, release of the old copy) costs the difference, {statistics.median(remake) - statistics.median(plain):.3f} ms")
+    raise SystemExit(0)
 elif which == "spatial_signals":   # the scene above with every orbit driven by two oscillators (option spatial_param_signals): descriptors made on the device
     import math
     from graphaudio_amd import AudioBufferSourceNode, GainNode, HrirSet, OscillatorNode, PlayableAudioBuffer, SpatialPannerNode
@@ -130,7 +157,7 @@ for rep in range(4):   # the first pieces carry one-time costs (formulation assi
 st = ctx.GetStats()
 print(json.dumps({k: st[k] for k in ("chunks", "segments", "kernel_launches", "device_ms_total", "mac_ms_total", "fft_ms_total", "other_ms_total", "device_bytes_in_use")}))
 print("rms", G.rms(out))
-if which in ("spatial", "spatial_signals", "spatial_occlusion"):   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
+if which in ("spatial", "spatial_signals", "spatial_occlusion", "spatial_builtin"):   # spatial_panner_kernel is accounted under stage "other"; 157.3 TFLOPS fp32 vector peak = 78.65e12 fma/s
     ms, flops = st["stage_ms"][0], st["stage_flops"][0]
     print(f"stage other ({st['stage_kernel'][0]}): {ms:.2f} ms over {st['profiled_chunks']} chunks, {flops / 2 / 1e9:.1f} G fma, "
           f"{flops / 2 / max(ms, 1e-9) / 1e9:.2f} T fma/s = {flops / 2 / max(ms, 1e-9) / 1e9 / 78.65 * 100:.1f} % of the fp32 vector peak (all 'other' kernels in the time)")
