@@ -56,7 +56,10 @@ int guardRO(ga_context* h, F&& f) {   // renders and queries: calls that do not 
 template <class F>
 int guard(ga_context* h, F&& f) {   // everything else: the next chunk simulates its first block from scratch (Context::apiEpoch)
   if (h) h->c.apiEpoch++;
-  return guardRO(h, std::forward<F>(f));
+  return guardRO(h, [&](Context& c) {
+    c.joinTail();   // (whatever the call changes or frees, a chunk's tail on stream2 comes first)
+    f(c);
+  });
 }
 float clampf(float v, float mn, float mx) {  // Math.Clamp(float, float, float)
   if (v < mn) return mn;
@@ -144,7 +147,7 @@ void Context::processBlocks(float* const* outPlanar, float* outInterleaved, int 
         size_t need = (size_t)done * kBlock * channels * sizeof(float);
         if (ilvBytes < need) {
           if (ilvDev) {
-            GA_HIP(hipStreamSynchronize(stream));
+            syncStream();
             dfree(ilvDev, ilvBytes);
           }
           ilvBytes = need + need / 4;
@@ -169,7 +172,7 @@ void Context::processBlocks(float* const* outPlanar, float* outInterleaved, int 
                                   sizeof(float) * (size_t)(sg.b1 - sg.b0) * kBlock, kind, stream));
       }
     }
-    GA_HIP(hipStreamSynchronize(stream));
+    syncStream();
     doneBlocks += done;
   }
   if (blockCount > 0) freeRetired();   // (the stream is idle)
@@ -198,18 +201,19 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
     Context& c;
     const bool blocking;
     ~Drain() {
-      if (blocking && c.stream) (void)hipStreamSynchronize(c.stream);
+      if (blocking) c.syncStreamQuiet();
       if (blocking && c.copyStream) (void)hipStreamSynchronize(c.copyStream);
     }
   } drain{*this, !pipelined.callerAsync};
   int64_t written = 0;
   if (cachedFrames > 0) {  // leftover frames of the previous call's last block (:55-75)
     if (channels > cachedCh) fail(GA_ERR_OUT_OF_RANGE, "channelIndex");
+    joinTail();
     int toCopy = (int)std::min<int64_t>(cachedFrames, frameCount);
     for (int ch = 0; ch < channels; ch++)
       GA_HIP(hipMemcpyAsync(out[ch] + startIndex, cacheDev + (size_t)ch * kBlock + (kBlock - cachedFrames), sizeof(float) * toCopy,
                             kind, stream));
-    if (!asyncMode) GA_HIP(hipStreamSynchronize(stream));
+    if (!asyncMode) syncStream();
     written = toCopy;
     cachedFrames -= toCopy;
   }
@@ -239,7 +243,10 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
     }
     struct Target {   // (cleared on every way out of the chunk)
       Context& c;
-      ~Target() { std::memset(c.busTarget, 0, sizeof(c.busTarget)); }
+      ~Target() {
+        std::memset(c.busTarget, 0, sizeof(c.busTarget));
+        c.tailWanted = false;
+      }
     } target{*this};
     // an asynchronous render into page-locked rows: the bus stays on the device and crosses PCIe under the next chunk's kernels
     // (only on the context's OWN stream: a caller who supplied the stream (ga_context_set_stream) may wait on that stream or on an
@@ -250,7 +257,7 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
       if (deferStageBytes < rowBytes * 32) {
         flushHandOver();
         if (deferStage) {
-          GA_HIP(hipStreamSynchronize(stream));
+          syncStream();
           dfree(deferStage, deferStageBytes);
         }
         deferStageBytes = rowBytes * 32;
@@ -260,7 +267,9 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
     } else if (direct) {
       for (int ch = 0; ch < channels; ch++) busTarget[ch] = tgt[ch];
     }
-    runChunk(nblk, nullptr);   // (takes a pending hand-over with it: in its pre-mix launch, or as copies in front of everything else)
+    tailWanted = defer && coarseTailStream && !comm;   // (option "coarse_tail_stream", ga_engine.hpp)
+    runChunk(nblk, nullptr);   // (takes a pending hand-over with it: in its pre-mix or forward launch, or as copies in front of everything else)
+    tailWanted = false;
     if (defer)
       for (int ch = 0; ch < channels; ch++)
         pendingHandOver.push_back(HandOver{busTarget[ch], tgt[ch], out[ch] + startIndex + written, chunkBlocksDone * kBlock});
@@ -287,11 +296,11 @@ void Context::render(float* const* out, int channels, int64_t frameCount, int64_
                               hipMemcpyDeviceToDevice, stream));
       cachedFrames = (int)excess;
     }
-    if (!asyncMode) GA_HIP(hipStreamSynchronize(stream));
+    if (!asyncMode) syncStream();
     written += toCopy;
   }
   if (!pipelined.callerAsync) {
-    GA_HIP(hipStreamSynchronize(stream));
+    syncStream();
     harvestProfile(true);
     freeRetired();   // (the stream is idle: what this call replaced -- a built-in HRIR set of another head radius, a sample table that doubled -- goes now)
   }
@@ -396,6 +405,11 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
     else if (k == "conv_reference_order") c.convRefOrder = (int)std::min(2.0, std::max(0.0, value));
     else if (k == "conv_ref_min_deviation") c.convRefMinDeviation = std::max(0.0, value);
     else if (k == "coarse_premix") c.coarsePremix = value != 0;
+    else if (k == "coarse_tail_stream") c.coarseTailStream = value != 0;
+    else if (k == "coarse_premix_wgs_per_cu") {
+      if (!(value >= 1 && value <= 8) || value != (int)value) fail(GA_ERR_OUT_OF_RANGE, "coarse_premix_wgs_per_cu is 1 .. 8");
+      c.coarsePremixWgsPerCu = (int)value;
+    }
     else if (k == "coarse_long") c.coarseLong = value != 0;
     else if (k == "coarse_ext_history") c.coarseExtHist = value != 0;
     else if (k == "coarse_wide") c.coarseWide = value != 0;
@@ -443,7 +457,7 @@ int ga_synchronize(ga_context* ctx) {
 int ga_context_set_stream(ga_context* ctx, void* hip_stream) {
   return guard(ctx, [&](Context& c) {
     c.flushHandOver();
-    GA_HIP(hipStreamSynchronize(c.stream));
+    c.syncStream();
     c.waitHostCopies();
     if (c.ownStream && c.stream) (void)hipStreamDestroy(c.stream);
     c.stream = (hipStream_t)hip_stream;
@@ -474,7 +488,7 @@ int ga_buffer_create(ga_context* ctx, const float* const* planar, int channels, 
       if (frames)
         GA_HIP(hipMemcpyAsync(b->dev + (size_t)i * b->stride, planar[i], sizeof(float) * frames, hipMemcpyHostToDevice, c.stream));
     }
-    GA_HIP(hipStreamSynchronize(c.stream));
+    c.syncStream();
     c.buffers.push_back(std::move(b));
     c.bufVersion++;
     *out_id = (int)c.buffers.size() - 1;

@@ -32,7 +32,7 @@ float* getSlab(Context& c) {
 void resetSlabs(Context& c, int64_t frames) {
   int64_t need = roundup(frames, 256);
   if (need > c.slabFrames) {
-    GA_HIP(hipStreamSynchronize(c.stream));
+    c.syncStream();
     size_t oldBytes = (size_t)c.slabFrames * sizeof(float);
     for (void* p : c.slabBlocks) c.dfree(p, oldBytes * slabsPerBlock(oldBytes));
     c.slabBlocks.clear();
@@ -238,7 +238,7 @@ void Context::fetchDeviceState() {
       StereoPannerS& nd = rec<StereoPannerS>(*np);
       if (!nd.params[0].events.empty() || !nd.params[0].modulation.empty()) continue;
       PanState tmp;   // back to a constant pan: the gains the automated run left on the device are the node's state
-      GA_HIP(hipStreamSynchronize(stream));   // the state the previous chunk left
+      syncStream();   // the state the previous chunk left
       GA_HIP(hipMemcpy(&tmp, nd.panDev, sizeof(PanState), hipMemcpyDeviceToHost));
       nd.panLast = tmp.last_pan;
       nd.panGL = tmp.gain_l;
@@ -252,7 +252,7 @@ void Context::fetchDeviceState() {
       // first block fades from the descriptor the device made).  `valid` never left the host.
       if (nd.spPrev.valid && nd.spCarry[nd.spCarryCur]) {
         SpatialCarry tmp;
-        GA_HIP(hipStreamSynchronize(stream));
+        syncStream();
         GA_HIP(hipMemcpy(&tmp, nd.spCarry[nd.spCarryCur], sizeof(SpatialCarry), hipMemcpyDeviceToHost));
         for (int q = 0; q < 4; q++) {
           nd.spPrev.idx[q] = tmp.idx[q];
@@ -277,7 +277,7 @@ void Context::fetchDeviceState() {
       for (auto& p : nd.params) automated = automated || !p.events.empty() || !p.modulation.empty();
       if (!automated) {  // back to constant parameters: fetch the coefficients the automated run left on the device
         BiquadDynState tmp;
-        GA_HIP(hipStreamSynchronize(stream));
+        syncStream();
         GA_HIP(hipMemcpy(&tmp, nd.bqDyn, 24, hipMemcpyDeviceToHost));
         nd.b0 = tmp.b0; nd.b1 = tmp.b1; nd.b2 = tmp.b2; nd.a1 = tmp.a1; nd.a2 = tmp.a2;
         nd.coefDirty = tmp.dirty != 0;
@@ -535,7 +535,7 @@ void Context::chunkResources(ChunkRun& r) {
       GA_HIP(hipMemsetAsync(nh, 0, maxD * rings * sizeof(float), stream));
       if (nd.delayHist) {
         GA_HIP(hipMemcpyAsync(nh, nd.delayHist, maxD * nd.delayHistRings * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        GA_HIP(hipStreamSynchronize(stream));
+        syncStream();
         dfree(nd.delayHist, maxD * nd.delayHistRings * sizeof(float));
       }
       nd.delayHist = nh;
@@ -544,7 +544,7 @@ void Context::chunkResources(ChunkRun& r) {
     const int64_t cap = roundup(frames, 4096);
     if (nd.delayCap < cap || nd.delayLineRings < rings) {
       if (nd.delayLine) {
-        GA_HIP(hipStreamSynchronize(stream));
+        syncStream();
         dfree(nd.delayLine, (maxD + (size_t)nd.delayCap) * nd.delayLineRings * sizeof(float));
       }
       nd.delayCap = std::max(nd.delayCap, cap);
@@ -559,7 +559,7 @@ void Context::chunkResources(ChunkRun& r) {
   if (r.stage != 2) resetSlabs(*this, frames);   // (the second stage reads the first stage's slabs: none is handed out again)
   if (zerosLen < frames) {
     if (zeros) {
-      GA_HIP(hipStreamSynchronize(stream));
+      syncStream();
       dfree(zeros, (size_t)zerosLen * 4);
     }
     zerosLen = roundup(frames, 4096);
@@ -567,7 +567,7 @@ void Context::chunkResources(ChunkRun& r) {
     GA_HIP(hipMemsetAsync(zeros, 0, (size_t)zerosLen * 4, stream));
   }
   if (busCapFrames < frames) {
-    GA_HIP(hipStreamSynchronize(stream));
+    syncStream();
     for (float* p : busSlabs) dfree(p, (size_t)busCapFrames * 4);
     busSlabs.clear();
     busCapFrames = roundup(frames, 4096);
@@ -605,17 +605,31 @@ void Context::chunkExecute(ChunkRun& r) {
   if (asyncMode && chunkDone[slot]) GA_HIP(hipEventSynchronize(chunkDone[slot]));   // chunk k - 2 is done: its staging is free
   if (thostBytes < tbytes) {
     if (thost) {
-      GA_HIP(hipStreamSynchronize(stream));
+      syncStream();
       (void)hipHostFree(thost);
     }
     thostBytes = (tbytes + tbytes / 4 + 4096 + 15) & ~(size_t)15;
     GA_HIP(hipHostMalloc(&thost, thostBytes, hipHostMallocDefault));
   }
-  ensure(tables, std::max(tablesHostBytes, tablesHostBBytes));
+  // option "coarse_tail_stream" (ga_engine.hpp): upload + pre-mix on `stream`, the coarse stage behind them on stream2.  Every other
+  // chunk waits for the tail its predecessor may have left there before it enqueues anything.
+  const bool tailChunk = tailWanted && tailCandidate && ex.plan.launches.size() == 2 && ex.plan.launches[0].kind == GA_STAGE_COARSE_SECTION &&
+                         ex.plan.launches[1].kind == LK_CINV;
+  tailCandidate = false;
+  if (tailChunk) ensureOverlapStream();
+  else joinTail();
+  // (the previous chunk's tail may still read the other arena; renders that never leave a tail keep to the one)
+  DevArena& tdev = (tailWanted && slot) ? tablesB : tables;
+  ensure(tdev, std::max(tablesHostBytes, tablesHostBBytes));
   std::memcpy(thost, ex.plan.host.data(), tbytes);
-  if (tableUploadKernel) launch_table_upload(stream, tables.p, thost, tbytes);   // (staging and arena sizes are multiples of 16)
-  else GA_HIP(hipMemcpyAsync(tables.p, thost, tbytes, hipMemcpyHostToDevice, stream));
-  uint8_t* base = (uint8_t*)tables.p;
+  if (tableUploadKernel) launch_table_upload(stream, tdev.p, thost, tbytes);   // (staging and arena sizes are multiples of 16)
+  else GA_HIP(hipMemcpyAsync(tdev.p, thost, tbytes, hipMemcpyHostToDevice, stream));
+  uint8_t* base = (uint8_t*)tdev.p;
+  struct TailActive {   // (cleared on every way out)
+    Context& c;
+    ~TailActive() { c.tailActive = false; }
+  } tailGuard{*this};
+  tailActive = tailChunk;
 
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   std::vector<int> evKind;
@@ -629,14 +643,15 @@ void Context::chunkExecute(ChunkRun& r) {
   }
   for (auto& l : ex.plan.launches) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    const hipStream_t ls = l.kind == LK_CINV ? tailStreamNow() : stream;   // (the stream the launch goes to)
     if (profile) {
       GA_HIP(hipEventCreate(&e0));
       GA_HIP(hipEventCreate(&e1));
-      GA_HIP(hipEventRecord(e0, stream));
+      GA_HIP(hipEventRecord(e0, ls));
     }
     l.fn(base);
     if (profile) {
-      GA_HIP(hipEventRecord(e1, stream));
+      GA_HIP(hipEventRecord(e1, ls));
       evs.push_back({e0, e1});
       evKind.push_back(l.kind);
       evBytes.push_back(l.bytes);
@@ -655,25 +670,30 @@ void Context::chunkExecute(ChunkRun& r) {
     evBytes.push_back(x.bytes);
   }
   extraProf.clear();
-  if (profile) GA_HIP(hipEventRecord(evEnd, stream));
+  if (profile) GA_HIP(hipEventRecord(evEnd, tailStreamNow()));
   GA_HIP(hipGetLastError());
   r.tmLaunch = nowMs();
   if (profileNow) pendingProf.push_back(ProfBatch{evBegin, evEnd, std::move(evs), std::move(evKind), std::move(evBytes)});
   if (asyncMode) {
     if (!chunkDone[slot]) GA_HIP(hipEventCreateWithFlags(&chunkDone[slot], hipEventDisableTiming));
-    GA_HIP(hipEventRecord(chunkDone[slot], stream));
+    GA_HIP(hipEventRecord(chunkDone[slot], tailStreamNow()));
+    if (tailChunk) {
+      GA_HIP(hipEventRecord(tailEv, stream2));
+      tailPending = true;
+    }
     harvestProfile(false);
   } else {
-    GA_HIP(hipStreamSynchronize(stream));
+    syncStream();
     harvestProfile(true);
   }
+  tailActive = false;
   chunkSeq++;
   if (gaTiming)
     fprintf(stderr, "[ga]   host detail: topo %.2f, sources %.2f, sim %.2f | resources %.2f, params %.2f, exec %.2f ms\n", r.tmTopo - r.tm0,
             r.tmSrc - r.tmTopo, r.tmSim - r.tmSrc, r.tmRes - r.tmSim, r.tmPre - r.tmRes, r.tmPlan - r.tmPre);
   if (gaTiming)
-    fprintf(stderr, "[ga] chunk %lld blocks: sim %.2f ms, plan %.2f ms, enqueue %.2f ms, wait %.2f ms\n", (long long)n, r.tmSim - r.tm0,
-            r.tmPlan - r.tmSim, r.tmLaunch - r.tmPlan, nowMs() - r.tmLaunch);
+    fprintf(stderr, "[ga] chunk %lld blocks: sim %.2f ms, plan %.2f ms, enqueue %.2f ms, wait %.2f ms%s\n", (long long)n, r.tmSim - r.tm0,
+            r.tmPlan - r.tmSim, r.tmLaunch - r.tmPlan, nowMs() - r.tmLaunch, tailChunk ? ", coarse stage on the second stream" : "");
 
 }
 
@@ -904,7 +924,7 @@ void Context::runTwoStageChunk(ChunkRun& r) {
   chunkExecute(r1);
   if (r1.waited) {   // (no modulated rate, and no accepted delay whose flag can rise in this chunk: nothing to read back)
     const double tw0 = nowMs();
-    GA_HIP(hipStreamSynchronize(stream));   // the rates, walk summaries and onset blocks (chunkRateProbe)
+    syncStream();   // the rates, walk summaries and onset blocks (chunkRateProbe)
     if (gaTiming) fprintf(stderr, "[ga]   two-stage chunk: stage 1 wait %.3f ms\n", nowMs() - tw0);
   }
   // the accepted delays: the block in which each span's samples raised the flag; the flag the node leaves the chunk with is its last span's
@@ -1064,7 +1084,7 @@ void Context::chunkRateProbe(ChunkRun& r) {
   const size_t devBytes = readBytes + descCount * sizeof(GsrBlock);
   if (rateModDevBytes < devBytes) {
     if (rateModDev) {
-      GA_HIP(hipStreamSynchronize(stream));   // (the previous chunk's gsr_kernel may still read its descriptors)
+      syncStream();   // (the previous chunk's gsr_kernel may still read its descriptors)
       dfree(rateModDev, rateModDevBytes);
     }
     rateModDevBytes = devBytes + devBytes / 2 + 4096;

@@ -1444,15 +1444,20 @@ __global__ __launch_bounds__(256) void coarse_hist_kernel(const CoarseHistJob* _
   }
 }
 // =====================================================================================================================
-//  pre-mix: out[f] = sum over the terms of in_t[f].  Workgroup = 256 consecutive frames (one 16-byte word = 4 frames per lane) x
-//  all terms of the job; its four waves take a quarter of the terms each (four times the waves to keep words in flight, also
-//  for short chunks), stream them from global memory kPremixAhead words at a time per lane, and wave 0 adds the four partial
-//  sums.  Term descriptors come 64 at a time, one per lane, and are handed out with v_readlane: the addresses are scalar base +
-//  32-bit lane offset.  All sums are Kahan-compensated -- four VALU operations per word in a kernel that waits for HBM -- so
-//  the result is the correctly rounded sum to within an ulp whatever the number of terms.  While a wave holds a member's
-//  samples it writes the member's input history of the next chunk (`carry`).
+//  pre-mix: out[f] = sum over the terms of in_t[f].  The grid is sized to the chip, not to the chunk: a summing job gets
+//  `wgs_per_job` workgroups (launch_coarse_premix: option coarse_premix_wgs_per_cu x compute units / summing jobs), all resident
+//  from the first cycle to the last, and workgroup i owns an equal, contiguous share of the job's 16-byte words (shares start on
+//  128-byte lines).  It walks its share in steps of 64 words (one word = 4 frames per lane; the last step is masked) x all terms
+//  of the job; its four waves take a quarter of the terms each (four times the waves to keep words in flight, also for short
+//  chunks), stream them from global memory kPremixAhead words at a time per lane, and wave 0 adds the four partial sums while
+//  the other waves start on the next step (the partial sums are double-buffered in LDS: one barrier per step).  Term descriptors
+//  come 64 at a time, one per lane, and are handed out with v_readlane: the addresses are scalar base + 32-bit lane offset.  All
+//  sums are Kahan-compensated -- four VALU operations per word in a kernel that waits for HBM -- so the result is the correctly
+//  rounded sum to within an ulp whatever the number of terms; the order of the additions of a frame depends on the number of
+//  terms alone, never on the grid.  While a wave holds a member's samples it writes the member's input history of the next chunk
+//  (`carry`).
 //  Job flags (planner): bit 0 = every `in` is 16-byte aligned, bit 1 = some term has a carry, bit 2 = hand-over of a finished bus
-//  to page-locked host rows (one term, plain copy; Context::pendingHandOver).
+//  to page-locked host rows (one term, plain copy; Context::pendingHandOver).  Hand-over jobs stand at the head of the job list.
 // =====================================================================================================================
 #ifndef GA_PREMIX_AHEAD
 #define GA_PREMIX_AHEAD 8
@@ -1464,14 +1469,11 @@ __global__ __launch_bounds__(256) void coarse_hist_kernel(const CoarseHistJob* _
 #define GA_PREMIX_NT 0      // 1: non-temporal loads of the members' samples ; 2: and non-temporal stores of their histories
 #endif
 constexpr int kPremixAhead = GA_PREMIX_AHEAD, kPremixWaves = GA_PREMIX_WAVES;
-#ifndef GA_PREMIX_WORDS
-#define GA_PREMIX_WORDS 1   // 16-byte words per lane and term: a wave reads GA_PREMIX_WORDS KB in a row from a member before it moves on
-#endif
 #ifndef GA_PREMIX_COPY_WGS
 #define GA_PREMIX_COPY_WGS 8
 #endif
 constexpr int kPremixCopyWgs = GA_PREMIX_COPY_WGS;   // workgroups that carry one row of a hand-over across PCIe
-constexpr int kPremixWords = GA_PREMIX_WORDS, kPremixTile = 256 * kPremixWords;   // frames per workgroup
+constexpr int kPremixStep = 64;                      // 16-byte words per step of a workgroup: one per lane
 struct Kahan4 {
   v4f s, c;
   __device__ __forceinline__ void add(v4f x) {
@@ -1485,12 +1487,11 @@ struct Kahan4 {
   }
 };
 template <bool ALIGNED, bool CARRY>
-__device__ __forceinline__ void premix_stream(const PremixJob& J, const PremixTerm* __restrict terms, int t0, int t1, int lane,
-                                              const uint32_t (&off)[kPremixWords], const bool (&keep)[kPremixWords],
-                                              const uint32_t (&coff)[kPremixWords], Kahan4 (&acc)[kPremixWords]) {
+__device__ __forceinline__ void premix_stream(const PremixJob& J, const PremixTerm* __restrict terms, int t0, int t1, int lane, uint32_t off, bool keep,
+                                              uint32_t coff, Kahan4& acc) {
   typedef const GA_GLOBAL char* gcp;
   typedef GA_GLOBAL char* gp;
-  auto fetch = [&](gcp in, uint32_t o) -> v4f {       // `in` is wave-uniform; words behind the end re-read word 0 and are dropped
+  auto fetch = [&](gcp in, uint32_t o) -> v4f {       // `in` is wave-uniform; lanes behind the end re-read the step's first word and are dropped
     if (ALIGNED) return GA_PREMIX_NT ? __builtin_nontemporal_load((const GA_GLOBAL v4f*)(in + o)) : *(const GA_GLOBAL v4f*)(in + o);
     const GA_GLOBAL float* p = (const GA_GLOBAL float*)(in + o);
     return v4f{p[0], p[1], p[2], p[3]};
@@ -1516,49 +1517,41 @@ __device__ __forceinline__ void premix_stream(const PremixJob& J, const PremixTe
     };
     int j = 0;
     for (; j + kPremixAhead <= nb; j += kPremixAhead) {
-      v4f x[kPremixAhead][kPremixWords];
+      v4f x[kPremixAhead];
 #pragma unroll
-      for (int u = 0; u < kPremixAhead; u++) {
-        gcp in = in_of(j + u);
-#pragma unroll
-        for (int w = 0; w < kPremixWords; w++) x[u][w] = fetch(in, off[w]);
-      }
+      for (int u = 0; u < kPremixAhead; u++) x[u] = fetch(in_of(j + u), off);
 #pragma unroll
       for (int u = 0; u < kPremixAhead; u++) {
         if (CARRY) {
           gp car = carry_of(j + u);
-#pragma unroll
-          for (int w = 0; w < kPremixWords; w++)
-            if (car && keep[w]) put(car, coff[w], x[u][w]);
+          if (car && keep) put(car, coff, x[u]);
         }
-#pragma unroll
-        for (int w = 0; w < kPremixWords; w++) acc[w].add(x[u][w]);
+        acc.add(x[u]);
       }
     }
     for (; j < nb; j++) {
       gcp in = in_of(j);
       gp car = CARRY ? carry_of(j) : nullptr;
-#pragma unroll
-      for (int w = 0; w < kPremixWords; w++) {
-        const v4f x = fetch(in, off[w]);
-        if (CARRY && car && keep[w]) put(car, coff[w], x);
-        acc[w].add(x);
-      }
+      const v4f x = fetch(in, off);
+      if (CARRY && car && keep) put(car, coff, x);
+      acc.add(x);
     }
   }
 }
-__global__ __launch_bounds__(64 * kPremixWaves) void coarse_premix_kernel(const PremixJob* __restrict jobs, const PremixTerm* __restrict terms) {
-  __shared__ v4f part[kPremixWaves - 1][2][kPremixWords][64];
-  const PremixJob J = jobs[blockIdx.y];
-  if (J.flags & 4) {
+__global__ __launch_bounds__(64 * kPremixWaves) void coarse_premix_kernel(const PremixJob* __restrict jobs, const PremixTerm* __restrict terms,
+                                                                          int n_handover, int wgs_per_job) {
+  __shared__ v4f part[2][kPremixWaves - 1][2][kPremixStep];
+  const unsigned copy_wgs = (unsigned)n_handover * kPremixCopyWgs;
+  if (blockIdx.x < copy_wgs) {
     // hand-over job: out is page-locked HOST memory.  A few workgroups walk the whole row -- they sit on a handful of wave slots
     // for as long as PCIe needs (~ 70 us for a 10 s stereo bus) while every other workgroup of the launch streams HBM.  (As
     // ordinary jobs -- one short-lived workgroup per 256 frames -- the copies filled the whole chip until PCIe had drained them.)
-    if (blockIdx.x >= (unsigned)kPremixCopyWgs) return;
+    const PremixJob J = jobs[blockIdx.x / kPremixCopyWgs];
+    const unsigned wg = blockIdx.x % kPremixCopyWgs;
     const GA_GLOBAL v4f* src = (const GA_GLOBAL v4f*)terms[J.term0].in;
     GA_GLOBAL v4f* dst = (GA_GLOBAL v4f*)J.out;
     const int64_t nw = J.n / 4, step = (int64_t)kPremixCopyWgs * blockDim.x * 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x * 2 + threadIdx.x; i < nw; i += step) {
+    for (int64_t i = (int64_t)wg * blockDim.x * 2 + threadIdx.x; i < nw; i += step) {
       const int64_t i2 = i + blockDim.x;
       const v4f a = src[i], b = i2 < nw ? src[i2] : a;
       dst[i] = a;
@@ -1566,59 +1559,71 @@ __global__ __launch_bounds__(64 * kPremixWaves) void coarse_premix_kernel(const 
     }
     return;
   }
-  const int64_t tile0 = (int64_t)blockIdx.x * kPremixTile;
-  if (tile0 >= J.n) return;   // (uniform)
+  const unsigned sb = blockIdx.x - copy_wgs;
+  const PremixJob J = jobs[n_handover + sb / (unsigned)wgs_per_job];
+  // this workgroup's share of the job's words: [w0, w1), cut on 128-byte lines (8 words)
+  const int64_t nw = J.n / 4, lines = (nw + 7) / 8, wg = sb % (unsigned)wgs_per_job;
+  const int64_t w0 = lines * wg / wgs_per_job * 8, w1 = min(nw, lines * (wg + 1) / wgs_per_job * 8);
+  if (w0 >= w1) return;   // (uniform: fewer lines than workgroups)
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int64_t f[kPremixWords];
-  bool live[kPremixWords], keep[kPremixWords];
-  uint32_t off[kPremixWords], coff[kPremixWords];   // byte offsets (chunks and histories are far below 4 GB)
-  Kahan4 acc[kPremixWords];
-#pragma unroll
-  for (int w = 0; w < kPremixWords; w++) {
-    f[w] = tile0 + (int64_t)(w * 64 + lane) * 4;
-    live[w] = f[w] < J.n;
-    keep[w] = live[w] && f[w] >= J.carry_from;
-    off[w] = live[w] ? (uint32_t)(f[w] * 4) : 0u;
-    coff[w] = (uint32_t)((f[w] - J.carry_from) * 4);
-    acc[w] = Kahan4{v4f{0.f, 0.f, 0.f, 0.f}, v4f{0.f, 0.f, 0.f, 0.f}};
-  }
   // this wave's share of the terms: a multiple of kPremixAhead each
   const int per = ((J.nterms + kPremixWaves - 1) / kPremixWaves + kPremixAhead - 1) / kPremixAhead * kPremixAhead;
   const int t0 = min(J.nterms, wv * per), t1 = min(J.nterms, t0 + per);
-  const bool carry_here = (J.flags & 2) && tile0 + kPremixTile > J.carry_from;   // (uniform)
-  if (J.flags & 1) {
-    if (carry_here) premix_stream<true, true>(J, terms, t0, t1, lane, off, keep, coff, acc);
-    else premix_stream<true, false>(J, terms, t0, t1, lane, off, keep, coff, acc);
-  } else {
-    if (carry_here) premix_stream<false, true>(J, terms, t0, t1, lane, off, keep, coff, acc);
-    else premix_stream<false, false>(J, terms, t0, t1, lane, off, keep, coff, acc);
-  }
-  if (wv > 0) {
-#pragma unroll
-    for (int w = 0; w < kPremixWords; w++) {
-      part[wv - 1][0][w][lane] = acc[w].s;
-      part[wv - 1][1][w][lane] = acc[w].c;
+  int buf = 0;
+  for (int64_t ws = w0; ws < w1; ws += kPremixStep, buf ^= 1) {   // (uniform)
+    const int64_t f = (ws + lane) * 4;   // first frame of this lane's word
+    const bool live = ws + lane < w1, keep = live && f >= J.carry_from;
+    const uint32_t off = (uint32_t)((live ? f : ws * 4) * 4);   // byte offsets (chunks and histories are far below 4 GB)
+    const uint32_t coff = (uint32_t)((f - J.carry_from) * 4);
+    Kahan4 acc{v4f{0.f, 0.f, 0.f, 0.f}, v4f{0.f, 0.f, 0.f, 0.f}};
+    const bool carry_here = (J.flags & 2) && (ws + kPremixStep) * 4 > J.carry_from;   // (uniform)
+    if (J.flags & 1) {
+      if (carry_here) premix_stream<true, true>(J, terms, t0, t1, lane, off, keep, coff, acc);
+      else premix_stream<true, false>(J, terms, t0, t1, lane, off, keep, coff, acc);
+    } else {
+      if (carry_here) premix_stream<false, true>(J, terms, t0, t1, lane, off, keep, coff, acc);
+      else premix_stream<false, false>(J, terms, t0, t1, lane, off, keep, coff, acc);
     }
-  }
-  __syncthreads();
-  if (wv == 0) {
-#pragma unroll
-    for (int w = 0; w < kPremixWords; w++) {
+    if (wv > 0) {
+      part[buf][wv - 1][0][lane] = acc.s;
+      part[buf][wv - 1][1][lane] = acc.c;
+    }
+    // one barrier per step: wave 0 reads part[buf] in front of the next step's barrier, and the other waves write part[buf] again
+    // only behind it
+    __syncthreads();
+    if (wv == 0) {
 #pragma unroll
       for (int q = 0; q < kPremixWaves - 1; q++) {   // (a partial sum is s - c: add both parts)
-        acc[w].add(part[q][0][w][lane]);
-        acc[w].add(-part[q][1][w][lane]);
+        acc.add(part[buf][q][0][lane]);
+        acc.add(-part[buf][q][1][lane]);
       }
-      if (live[w]) stg4(J.out + f[w], acc[w].s);
+      if (live) stg4(J.out + f, acc.s);
     }
   }
 }
-const char* launch_coarse_premix(hipStream_t s, const PremixJob* jobs_dev, int njobs, const PremixTerm* terms_dev, int64_t max_n) {
+static int premix_compute_units() {   // of the current device (asked once per device)
+  static int cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) launch_fail("coarse pre-mix: no current device");
+  if (!cached[dev]) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) launch_fail("coarse pre-mix: no device properties");
+    cached[dev] = std::max(1, prop.multiProcessorCount);
+  }
+  return cached[dev];
+}
+const char* launch_coarse_premix(hipStream_t s, const PremixJob* jobs_dev, int njobs, int n_handover, const PremixTerm* terms_dev, int64_t max_n,
+                                 int wgs_per_cu) {
   if (njobs <= 0 || max_n <= 0) return "";
-  const int64_t gx = (max_n + kPremixTile - 1) / kPremixTile;
-  if (gx > 0x7fffffff || max_n >= ((int64_t)1 << 29)) launch_fail("coarse pre-mix: chunk too long");
-  for (int j0 = 0; j0 < njobs; j0 += 32768)
-    hipLaunchKernelGGL(coarse_premix_kernel, dim3((unsigned)gx, std::min(32768, njobs - j0)), dim3(64 * kPremixWaves), 0, s, jobs_dev + j0, terms_dev);
+  if (max_n >= ((int64_t)1 << 29)) launch_fail("coarse pre-mix: chunk too long");
+  if (n_handover < 0 || n_handover > njobs || wgs_per_cu < 1) launch_fail("coarse pre-mix: bad launch parameters");
+  // the summing jobs share wgs_per_cu resident workgroups per compute unit; no more of them than a job has 64-word steps
+  const int nsum = njobs - n_handover;
+  const int64_t steps = (max_n / 4 + kPremixStep - 1) / kPremixStep;
+  const int per_job = nsum ? (int)std::max<int64_t>(1, std::min<int64_t>(steps, (int64_t)wgs_per_cu * premix_compute_units() / nsum)) : 1;
+  const int64_t grid = (int64_t)n_handover * kPremixCopyWgs + (int64_t)nsum * per_job;
+  if (grid > 0x7fffffff) launch_fail("coarse pre-mix: too many jobs");
+  hipLaunchKernelGGL(coarse_premix_kernel, dim3((unsigned)grid), dim3(64 * kPremixWaves), 0, s, jobs_dev, terms_dev, n_handover, per_job);
   return "coarse_premix_kernel";
 }
 

@@ -129,6 +129,7 @@ void Context::commAbort() {
 // Wait for the stream of a context that has collectives in flight: a peer that died or aborted shows up as an asynchronous
 // error of the communicator (or, at worst, as the time limit of option "comm_timeout_s"), not as a wait that never ends.
 void Context::commWait() {
+  joinTail();
   if (!comm) {
     GA_HIP(hipStreamSynchronize(stream));
     return;
@@ -193,11 +194,12 @@ void Context::renderReduce(float* const* out, int channels, int64_t frames, int6
       if (!out[ch]) fail(GA_ERR_INVALID_ARGUMENT, "Channel buffer is null.");
   }
   GA_HIP(hipSetDevice(device));
+  joinTail();   // (a sharded render never leaves a tail on stream2; an earlier plain render may have)
   const size_t need_ = (size_t)channels * (size_t)frames * sizeof(float);
   if (reduceBytes < need_) {
     flushHandOver();   // (a pending hand-over reads the buffer that is about to go)
     if (reduceBuf) {
-      GA_HIP(hipStreamSynchronize(stream));
+      syncStream();
       dfree(reduceBuf, reduceBytes);
     }
     reduceBytes = need_ + need_ / 8;

@@ -173,7 +173,7 @@ void Context::dfree(void* p, size_t bytes) {
 void Context::ensure(DevArena& a, size_t bytes) {
   if (a.bytes >= bytes) return;
   if (a.p) {
-    GA_HIP(hipStreamSynchronize(stream));
+    syncStream();
     dfree(a.p, a.bytes);
     a.p = nullptr;
     a.bytes = 0;
@@ -207,6 +207,7 @@ void Context::init_device(int dev) {
 
 Context::~Context() {
   if (stream) (void)hipStreamSynchronize(stream);
+  if (stream2) (void)hipStreamSynchronize(stream2);   // (a chunk's tail may still run there: option "coarse_tail_stream")
   try {
     commDestroy();
   } catch (...) {
@@ -277,6 +278,8 @@ Context::~Context() {
     for (auto& e : dGroupEv)
       if (e) (void)hipEventDestroy(e);
     if (dJoinEv) (void)hipEventDestroy(dJoinEv);
+    if (tailEv) (void)hipEventDestroy(tailEv);
+    if (premixEv) (void)hipEventDestroy(premixEv);
   }
   for (auto& x : extraProf) { (void)hipEventDestroy(x.e0); (void)hipEventDestroy(x.e1); }
   if (coarseX.p) (void)hipFree(coarseX.p);
@@ -295,6 +298,7 @@ Context::~Context() {
   for (float* p : bqSplitBlocks) (void)hipFree(p);
   if (ilvDev) (void)hipFree(ilvDev);
   if (tables.p) (void)hipFree(tables.p);
+  if (tablesB.p) (void)hipFree(tablesB.p);
   if (tablesHost) (void)hipHostFree(tablesHost);
   if (tablesHostB) (void)hipHostFree(tablesHostB);
   for (auto& e : chunkDone)
@@ -392,7 +396,7 @@ void Context::collectGarbage() {
         continue;
       }
       if (!synced && stream) {
-        (void)hipStreamSynchronize(stream);
+        syncStreamQuiet();
         synced = true;
       }
       PlayBuf& b = *buffers[id];
@@ -407,7 +411,7 @@ void Context::collectGarbage() {
   // impulse-response spectra that only the cache still holds (their convolvers are gone or use another buffer)
   for (auto it = irCache.begin(); it != irCache.end();) {
     if (it->second.use_count() == 1) {
-      if (stream) (void)hipStreamSynchronize(stream);
+      syncStreamQuiet();
       it = irCache.erase(it);
     } else {
       ++it;
@@ -445,7 +449,23 @@ void Context::harvestProfile(bool wait) {
     pendingProf.pop_front();
   }
 }
+void Context::joinTail() {
+  if (!tailPending) return;
+  GA_HIP(hipStreamWaitEvent(stream, tailEv, 0));
+  tailPending = false;
+}
+void Context::syncStream() {
+  joinTail();
+  GA_HIP(hipStreamSynchronize(stream));
+}
+void Context::syncStreamQuiet() {   // (on the ways out that must not throw)
+  if (!stream) return;
+  if (tailPending) (void)hipStreamWaitEvent(stream, tailEv, 0);
+  tailPending = false;
+  (void)hipStreamSynchronize(stream);
+}
 void Context::flushHandOver() {
+  joinTail();   // (the rows are written on stream2 when the chunk's tail ran there)
   for (const HandOver& h : pendingHandOver)
     GA_HIP(hipMemcpyAsync(h.dst_host, h.src, sizeof(float) * (size_t)h.n, hipMemcpyDeviceToHost, stream));
   pendingHandOver.clear();
@@ -483,7 +503,7 @@ void Context::handOverToHost(const float* const* src, float* const* out, int cha
     if (outPending[k]) GA_HIP(hipEventSynchronize(outCopied[k]));
     outPending[k] = false;
     if (outStage[k]) {
-      GA_HIP(hipStreamSynchronize(stream));   // (a device-to-device copy into it may still be queued)
+      syncStream();   // (a device-to-device copy into it may still be queued)
       dfree(outStage[k], outStageBytes[k]);
       outStage[k] = nullptr;
       outStageBytes[k] = 0;
@@ -578,7 +598,7 @@ void Context::doDispose(int id) {
   // OnDispose
   if (n.type == GA_NODE_DELAY) {   // the delay lines go with the node
     DelayS& d = rec<DelayS>(n);
-    if (stream) (void)hipStreamSynchronize(stream);
+    syncStreamQuiet();
     if (d.delayHist) dfree(d.delayHist, (size_t)d.maxDelaySamples * d.delayHistRings * sizeof(float));
     if (d.delayLine) dfree(d.delayLine, ((size_t)d.maxDelaySamples + (size_t)d.delayCap) * d.delayLineRings * sizeof(float));
     d.delayHist = d.delayLine = nullptr;
@@ -586,7 +606,7 @@ void Context::doDispose(int id) {
     d.delayCap = 0;
   }
   if (n.staleBuf) {   // (feedback cycles: the kept output block goes with the node)
-    if (stream) (void)hipStreamSynchronize(stream);
+    syncStreamQuiet();
     dfree(n.staleBuf, (size_t)n.staleRows * kBlock * sizeof(float));
     dfree(n.staleNext, (size_t)n.staleRows * kBlock * sizeof(float));
     n.staleBuf = n.staleNext = nullptr;
@@ -595,21 +615,21 @@ void Context::doDispose(int id) {
   if (n.type == GA_NODE_SPATIAL_PANNER) {   // the carried input history goes with the node, the HRIR set is let go
     SpatialPannerS& sp = rec<SpatialPannerS>(n);
     if (sp.spHist[0]) {
-      if (stream) (void)hipStreamSynchronize(stream);
+      syncStreamQuiet();
       for (float*& h : sp.spHist) {
         dfree(h, kSpatialMaxTaps * sizeof(float));
         h = nullptr;
       }
     }
     if (sp.spCarry[0]) {
-      if (stream) (void)hipStreamSynchronize(stream);
+      syncStreamQuiet();
       for (SpatialCarry*& h : sp.spCarry) {
         dfree(h, sizeof(SpatialCarry));
         h = nullptr;
       }
     }
     if (sp.spDirect) {
-      if (stream) (void)hipStreamSynchronize(stream);
+      syncStreamQuiet();
       dfree(sp.spDirect, sizeof(SpatialDirectState));
       sp.spDirect = nullptr;
     }
@@ -640,7 +660,7 @@ void Context::releaseConvState(ConvolverS& n) {
     if (r.group) r.group->rows[r.idx] = {-1, 0};
   n.convRows.clear();
   if (n.bHistR || n.bOverlap) {
-    if (stream) (void)hipStreamSynchronize(stream);
+    syncStreamQuiet();
     if (n.ir) {
       size_t hb = (size_t)n.bInCh * kBins * std::max(n.ir->P - 1, 1) * sizeof(float);
       dfree(n.bHistR, hb);
@@ -652,13 +672,13 @@ void Context::releaseConvState(ConvolverS& n) {
     dfree(n.bOverlap, (size_t)n.bSlots * 2 * kBlock * sizeof(float));
   }
   if (n.dHist[0]) {
-    if (stream) (void)hipStreamSynchronize(stream);
+    syncStreamQuiet();
     dfree(n.dHistBase[0], n.dHistBytes);
     dfree(n.dHistBase[1], n.dHistBytes);
     n.dHistBase[0] = n.dHistBase[1] = nullptr;
   }
   if (n.dTail[0]) {
-    if (stream) (void)hipStreamSynchronize(stream);
+    syncStreamQuiet();
     for (int b = 0; b < 2; b++) dfree(n.dTail[b], (size_t)n.dTailLen * n.dTailCh * sizeof(float));
   }
   n.dTail[0] = n.dTail[1] = nullptr;
@@ -709,7 +729,7 @@ void Context::flushPlaneHistories(int pair) {
   memcpy(tab, jobs.data(), jobs.size() * sizeof(HistJobB));
   launch_hist_copy_b(stream, tab, (int)jobs.size(), maxh);
   GA_HIP(hipGetLastError());
-  GA_HIP(hipStreamSynchronize(stream));
+  syncStream();
   GA_HIP(hipHostFree(tab));
 }
 
@@ -1062,13 +1082,13 @@ std::shared_ptr<IrSpectra> Context::irSpectra(int bufId, bool normalize) {
     std::vector<ConvRowIO> r2(nch);
     for (int c = 0; c < nch; c++) r2[c] = ConvRowIO{dIn + (size_t)c * padded + (size_t)t0 * kBlock, nullptr};
     if (t0 > 0) {
-      GA_HIP(hipStreamSynchronize(stream));
+      syncStream();
       GA_HIP(hipMemcpy(rowsDev, r2.data(), sizeof(ConvRowIO) * nch, hipMemcpyHostToDevice));
     }
     launch_rfft_fwd(stream, rowsDev, nch, nb, t0, pl, Twiddles{w128, w256});
   }
   launch_extract_ir(stream, sp->hr, sp->hi, xr, xi, P, rp, P, nch);
-  GA_HIP(hipStreamSynchronize(stream));
+  syncStream();
   GA_HIP(hipGetLastError());
   sp->taps = dIn;   // kept: formulation D transforms the scaled taps with its own partition size (ensureCoarseSpectra)
   sp->tapsStride = padded;
@@ -1119,6 +1139,8 @@ void Context::ensureOverlapStream() {
   GA_HIP(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
   for (auto& e : dGroupEv) GA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   GA_HIP(hipEventCreateWithFlags(&dJoinEv, hipEventDisableTiming));
+  GA_HIP(hipEventCreateWithFlags(&tailEv, hipEventDisableTiming));
+  GA_HIP(hipEventCreateWithFlags(&premixEv, hipEventDisableTiming));
 }
 const float2* Context::coarseTwab() {
   if (coarseTw) return coarseTw;
@@ -1166,7 +1188,7 @@ void Context::ensureCoarseSpectra(IrSpectra& ir) {
   GA_HIP(hipMemcpy(rd, rows.data(), sizeof(CoarseXRow) * rows.size(), hipMemcpyHostToDevice));
   launch_coarse_fwd(stream, rd, ir.nch, P, P, ir.coarse, twiddles16pw(), coarseTwab());
   GA_HIP(hipGetLastError());
-  GA_HIP(hipStreamSynchronize(stream));
+  syncStream();
   dfree(rd, sizeof(CoarseXRow) * rows.size());
 }
 

@@ -978,6 +978,25 @@ struct Context {
   void handOverToHost(const float* const* src, float* const* out, int channels, int64_t offset, int64_t frames);
   void waitHostCopies();
   hipStream_t stream2 = nullptr;
+  // option "coarse_tail_stream": a chunk whose plan is table upload + ONE pre-mix launch + one coarse stage (forward, sum, inverse)
+  // runs the three latency-bound kernels behind the pre-mix on stream2, so that the next chunk's upload and pre-mix -- which do
+  // not depend on them -- start on `stream` while they run.  Only for asynchronous renders into page-locked rows on the context's
+  // own stream, without a communicator (Context::render sets tailWanted).  The bus of chunk k is handed over inside the forward
+  // launch of chunk k + 1, on stream2, behind the inverse transforms that write it.  Chunk k + 2 is not enqueued before chunk k
+  // has finished (chunkDone, recorded on stream2), so only neighbouring chunks overlap; their job tables and pre-mix arenas
+  // alternate.  INVARIANT: joinTail() makes `stream` wait for the last tail before anything else than that upload + pre-mix
+  // pair is enqueued on `stream` and before the host waits for `stream` (syncStream).
+  bool coarseTailStream = true;
+  bool tailWanted = false;     // this render's chunks may run their tail on stream2
+  bool tailCandidate = false;  // planner: the chunk's coarse stage is laid out for it (the hand-over rides in the forward launch)
+  bool tailActive = false;     // chunkExecute: the chunk being enqueued does
+  bool tailPending = false;    // a tail has been enqueued on stream2 that `stream` has not waited for
+  hipEvent_t tailEv = nullptr, premixEv = nullptr;
+  DevArena tablesB;            // the job tables of odd chunks of renders that may leave a tail (tailWanted)
+  void joinTail();
+  void syncStream();           // joinTail + wait for `stream`
+  void syncStreamQuiet();
+  hipStream_t tailStreamNow() const { return tailActive ? stream2 : stream; }
   hipEvent_t dGroupEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t dJoinEv = nullptr;
   bool coarseOverlap = false;
@@ -1009,6 +1028,8 @@ struct Context {
   bool coarseLong = true;    // option "coarse_long": impulse responses of 131,073 .. 1,048,576 taps take formulation D (segmented partition sum); 0: A / B
   bool coarsePremix = true;  // option "coarse_premix": fused groups on ONE impulse response are summed in the time domain, in front of
                              // one set of transforms (0: every member is transformed, the spectra are summed -- coarse_sum_kernel)
+  int coarsePremixWgsPerCu = 2;   // option "coarse_premix_wgs_per_cu" (1 .. 8): resident workgroups of coarse_premix_kernel per compute unit; the
+                                  // launch's summing jobs share them (ga_coarse.hip).  The sum of a frame does not depend on it.
   void ensureOverlapStream();
   // event pairs recorded by launches that time their own pieces (several kernels, two streams); folded into the chunk's profile batch
   void noteKernel(int kind, const char* name) {   // ga_stats.stage_kernel: the kernel instance a stage's latest launch ran

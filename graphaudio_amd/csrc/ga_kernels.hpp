@@ -234,7 +234,9 @@ struct PremixJob {
   int flags;               // bit 0: every `in` is 16-byte aligned ; bit 1: some term has a carry ; bit 2: hand-over copy to host rows
   int pad_;
 };
-const char* launch_coarse_premix(hipStream_t s, const PremixJob* jobs_dev, int njobs, const PremixTerm* terms_dev, int64_t max_n);
+// jobs_dev: the n_handover hand-over jobs first, then the summing jobs, which share wgs_per_cu resident workgroups per compute unit
+const char* launch_coarse_premix(hipStream_t s, const PremixJob* jobs_dev, int njobs, int n_handover, const PremixTerm* terms_dev, int64_t max_n,
+                                 int wgs_per_cu);
 // (the coarse launchers return the name of the kernel instance they ran: ga_stats.stage_kernel)
 // forward: tw16 = Context::twiddles16pw() ; inverse: tw16 = Context::twiddles16(4096) ; twab = [2][2049]: W_8192^k, W_16384^k
 const char* launch_coarse_fwd(hipStream_t s, const CoarseXRow* rows_dev, int nrows, int max_frames, int run, float2* X, const float2* tw16,

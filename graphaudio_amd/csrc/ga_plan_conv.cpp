@@ -31,7 +31,7 @@ void Context::ensureGroupState(ConvGroup& g) {
                               hipMemcpyDeviceToDevice, c.stream));
     }
     GA_HIP(hipMemcpyAsync(o0, g.overlap[g.ovCur], (size_t)g.rp * kBlock * 4, hipMemcpyDeviceToDevice, c.stream));
-    GA_HIP(hipStreamSynchronize(c.stream));
+    c.syncStream();
     size_t oldH = (size_t)kBins * std::max(hist, 1) * g.rp * sizeof(float);
     c.dfree(g.histR, oldH);
     c.dfree(g.histI, oldH);
@@ -193,6 +193,7 @@ struct CoarseStage {
   std::vector<PremixTerm> pmTerms;
   size_t pmUsed = 0;       // bytes of the pre-mix arena handed out
   int64_t pmMaxN = 0;
+  int pmHandOver = 0;   // hand-over jobs at the head of pmJobs
   double pmBytes = 0;
   std::vector<CoarseXRow> xrows;
   std::vector<CoarseHistJob> hjobs;
@@ -447,8 +448,10 @@ void CoarseStage::buildRows() {
     int xFrame[32], xIndex[32];
     for (int ch = 0; ch < g.nxr; ch++) {
       const size_t bytes = (size_t)(hl + frames) * sizeof(float);
-      if (pmUsed + bytes > c.coarseM.bytes) fail(GA_ERR_INVALID_OPERATION, "internal: the pre-mix arena is too small for the plan");
-      float* mixed = (float*)((char*)c.coarseM.p + pmUsed);
+      // (two halves: the forward transforms of the previous chunk may still read the other one, option "coarse_tail_stream")
+      const size_t half = (c.coarseM.bytes / 2) & ~(size_t)255;
+      if (pmUsed + bytes > half) fail(GA_ERR_INVALID_OPERATION, "internal: the pre-mix arena is too small for the plan");
+      float* mixed = (float*)((char*)c.coarseM.p + ((c.chunkSeq & 1) ? half : 0) + pmUsed);
       pmUsed += (bytes + 255) & ~(size_t)255;
       auto job = [&](float* out, const std::vector<PremixTerm>& tv, int64_t len, int64_t carryFrom) {
         PremixJob j{out, (int)pmTerms.size(), 0, len, carryFrom, 1, 0};
@@ -490,7 +493,14 @@ void CoarseStage::buildRows() {
   }
   // the previous chunk's bus on its way to the caller's page-locked rows (Context::pendingHandOver): one-term jobs at the head of
   // this launch -- their workgroups write over PCIe while the others stream the members' samples from HBM
-  if (!pmJobs.empty() && !c.pendingHandOver.empty()) {
+  // option "coarse_tail_stream": this stage may run behind its pre-mix on stream2 (Context::chunkExecute decides), where the
+  // previous chunk's inverse transforms wrote that bus -- then the hand-over rides in the forward launch, on the same stream
+  c.tailCandidate = c.tailWanted && !pmJobs.empty() && hjobs.empty() && !c.coarseOverlap && ex.plan.launches.empty();
+  if (c.tailCandidate && !c.pendingHandOver.empty() && !xrows.empty()) {
+    for (const Context::HandOver& h : c.pendingHandOver) fwdHandOver.push_back(CoarseHandOver{h.src, h.dst_dev, h.n});
+    c.pendingHandOver.clear();
+    c.stats.deferred_handovers++;
+  } else if (!pmJobs.empty() && !c.pendingHandOver.empty()) {
     std::vector<PremixJob> head;
     for (const Context::HandOver& h : c.pendingHandOver) {
       head.push_back(PremixJob{h.dst_dev, (int)pmTerms.size(), 1, h.n, h.n, 1 | 4, 0});
@@ -499,6 +509,7 @@ void CoarseStage::buildRows() {
       pmBytes += 2.0 * (double)h.n * 4.0;
     }
     pmJobs.insert(pmJobs.begin(), head.begin(), head.end());
+    pmHandOver = (int)head.size();
     c.pendingHandOver.clear();
     c.stats.deferred_handovers++;
   } else if (!c.pendingHandOver.empty() && !xrows.empty()) {   // no pre-mix launch: they ride in the stage's first forward launch
@@ -648,7 +659,7 @@ void CoarseStage::buildOutputs() {
       if (nch == 0) continue;
       if (!ld.dTail[0] || ld.dTailLen != len || ld.dTailCh != nch) {
         if (kv.second.carried) fail(GA_ERR_INVALID_OPERATION, "internal: a carried tail changed its shape");
-        GA_HIP(hipStreamSynchronize(c.stream));
+        c.syncStream();
         for (int b = 0; b < 2; b++) {
           if (ld.dTail[b]) c.dfree(ld.dTail[b], (size_t)ld.dTailLen * ld.dTailCh * sizeof(float));
           ld.dTail[b] = (float*)c.dalloc((size_t)len * nch * sizeof(float));
@@ -702,7 +713,7 @@ void CoarseStage::enqueue() {
   const size_t xo = ex.plan.putv(xrows), ho = ex.plan.putv(hjobs), to = ex.plan.putv(terms), oo = ex.plan.putv(outs), yo = ex.plan.putv(ylist);
   const size_t pjo = ex.plan.putv(pmJobs), pto = ex.plan.putv(pmTerms), fho = ex.plan.putv(fwdHandOver);
   const int nfh = (int)fwdHandOver.size();
-  const int npm = (int)pmJobs.size();
+  const int npm = (int)pmJobs.size(), npmHandOver = this->pmHandOver, pmWgsPerCu = c.coarsePremixWgsPerCu;
   const int64_t pmMaxN = this->pmMaxN;
   const double pmBytes = this->pmBytes, pmFlops = this->pmFlops, invFlops = this->invFlops;
   struct MacLaunch { size_t off; int nj, cw, mt, mp, pb, grp; bool ap; double bytes, flops; };
@@ -763,18 +774,24 @@ void CoarseStage::enqueue() {
       cp->stats.stage_bytes[kind] += bytes;
       cp->stats.stage_flops[kind] += flops;
     };
-    hipStream_t s2 = G > 1 ? cp->stream2 : st;
     if (npm > 0)
-      timed(st, LK_CPREMIX, pmBytes, pmFlops, [&] { return launch_coarse_premix(st, (const PremixJob*)(base + pjo), npm, (const PremixTerm*)(base + pto), pmMaxN); });
+      timed(cp->stream, LK_CPREMIX, pmBytes, pmFlops, [&] { return launch_coarse_premix(st, (const PremixJob*)(base + pjo), npm, npmHandOver, (const PremixTerm*)(base + pto), pmMaxN, pmWgsPerCu); });
+    // (option "coarse_tail_stream": everything behind the pre-mix goes to stream2, G == 1)
+    hipStream_t ts = cp->tailStreamNow();
+    if (cp->tailActive) {
+      GA_HIP(hipEventRecord(cp->premixEv, cp->stream));
+      GA_HIP(hipStreamWaitEvent(ts, cp->premixEv, 0));
+    }
+    hipStream_t s2 = G > 1 ? cp->stream2 : ts;
     for (int g = 0; g < G; g++) {
       const FwdLaunch& f = fwds[g];
       if (f.nx > 0)
-        timed(st, LK_CFWD, f.bytes, f.flops, [&] {
-          return launch_coarse_fwd(st, (const CoarseXRow*)(base + xo) + f.x0, f.nx, f.maxFrames, f.run, X, twFwd, twab,
+        timed(ts, LK_CFWD, f.bytes, f.flops, [&] {
+          return launch_coarse_fwd(ts, (const CoarseXRow*)(base + xo) + f.x0, f.nx, f.maxFrames, f.run, X, twFwd, twab,
                                    (const CoarseHandOver*)(base + fho), g == 0 ? nfh : 0);
         });
       if (G > 1) {
-        GA_HIP(hipEventRecord(cp->dGroupEv[g], st));
+        GA_HIP(hipEventRecord(cp->dGroupEv[g], ts));
         GA_HIP(hipStreamWaitEvent(s2, cp->dGroupEv[g], 0));
       }
       for (const MacLaunch& m : macs)
@@ -786,11 +803,11 @@ void CoarseStage::enqueue() {
     }
     if (G > 1) {   // join: the inverse transforms (and the next chunk's forward transforms, which reuse X) wait for every job
       GA_HIP(hipEventRecord(cp->dJoinEv, s2));
-      GA_HIP(hipStreamWaitEvent(st, cp->dJoinEv, 0));
+      GA_HIP(hipStreamWaitEvent(ts, cp->dJoinEv, 0));
     }
   });
   ex.plan.add(LK_CINV, [=](uint8_t* base) {
-    cp->noteKernel(LK_CINV, launch_coarse_inv(st, (const CoarseOut*)(base + oo), no, invBlocks, (const int*)(base + yo), Y, yFrames, tw16, twab));
+    cp->noteKernel(LK_CINV, launch_coarse_inv(cp->tailStreamNow(), (const CoarseOut*)(base + oo), no, invBlocks, (const int*)(base + yo), Y, yFrames, tw16, twab));
   }, invBytes, invFlops);
   const int64_t mh = maxHist;
   if (nh > 0) ex.plan.add(LK_CHIST, [=](uint8_t* base) { launch_coarse_hist(st, (const CoarseHistJob*)(base + ho), nh, mh); }, histBytes);
@@ -1113,7 +1130,7 @@ void Context::chunkConvScratch(ChunkRun& r) {
         }
         size_t pm = 0;
         for (auto& kv : pmDepth) pm = std::max(pm, kv.second);
-        if (pm) ensure(coarseM, pm);
+        if (pm) ensure(coarseM, 2 * pm + 512);   // (two halves, used in turn)
       }
     }
     bRowX = bRowY = 0;

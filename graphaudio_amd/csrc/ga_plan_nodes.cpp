@@ -794,7 +794,7 @@ void Context::planBiquad(NodePlanCtx& k) {
       init.dirty = nd.coefDirty ? 1 : 0;
       nd.coefDirty = false;   // (while the state is on the device the host flag means: Type written since the state went there)
       GA_HIP(hipMemcpyAsync(nd.bqDyn, &init, 24, hipMemcpyHostToDevice, stream));
-      GA_HIP(hipStreamSynchronize(stream));
+      syncStream();
       nd.coefOnDevice = true;
       deviceStateNodes.push_back(ns.id);
     }
@@ -1136,7 +1136,7 @@ void Context::chunkStaleCommit(ChunkRun& r) {
     const int rows = nd.type == GA_NODE_CHANNEL_SPLITTER ? std::max<int>(1, (int)nd.outputs.size()) : 32;
     if (!nd.staleBuf || nd.staleRows < rows) {
       if (nd.staleBuf) {
-        GA_HIP(hipStreamSynchronize(stream));
+        syncStream();
         dfree(nd.staleBuf, (size_t)nd.staleRows * kBlock * sizeof(float));
         dfree(nd.staleNext, (size_t)nd.staleRows * kBlock * sizeof(float));
       }

@@ -30,7 +30,9 @@ static double timeit(F f, int reps = 7) {
 __global__ void fill(float* p, size_t n, float v) {
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v + (float)(i & 1023) * 1e-3f;
 }
-int main() {
+int main(int argc, char** argv) {   // argument: resident workgroups per compute unit (option coarse_premix_wgs_per_cu), default 7
+  const int wgsPerCu = argc > 1 ? atoi(argv[1]) : 7;
+  printf("coarse_premix_wgs_per_cu %d\n", wgsPerCu);
   const int rows = 1024;
   const int64_t frames = 480000, hl = 65536;
   (void)hipEventCreate(&e0);
@@ -69,7 +71,7 @@ int main() {
       (void)hipMalloc(&djob, sizeof(PremixJob));
       (void)hipMemcpy(dterms, terms.data(), rows * sizeof(PremixTerm), hipMemcpyHostToDevice);
       (void)hipMemcpy(djob, &job, sizeof(job), hipMemcpyHostToDevice);
-      const double ms = timeit([&] { launch_coarse_premix(nullptr, djob, 1, dterms, frames); });
+      const double ms = timeit([&] { launch_coarse_premix(nullptr, djob, 1, 0, dterms, frames, wgsPerCu); });
       const double bytes = (double)rows * frames * 4 + (carry ? (double)rows * hl * 4 : 0.0) + frames * 4.0;
       printf("layout %d (%s), histories %s: %.4f ms  %.2f TB/s\n", layout,
              layout == 0 ? "one arena" : layout == 1 ? "separate allocations" : "separate allocations, 1 KB skew", carry ? "written" : "not written", ms,
