@@ -48,6 +48,7 @@ internal static unsafe partial class GraphAudioHip
         public long twin_rows;
         public long delay_flags_read;
         public long delay_flags_predicted;
+        public long ir_resamples;
         public long conv_migrations;
     }
 

@@ -170,6 +170,24 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
         }
     }
 
+    private bool _irResample;
+    /// <summary>Option "ir_resample" (default off): ConvolverNode.Buffer and a SpatialPannerNode's HRIR set accept a buffer whose
+    /// sample rate is not the context's instead of throwing InvalidOperationException.  The buffer is converted once, when it is
+    /// assigned, on the device, by a band-limited (Kaiser-windowed sinc) filter that keeps the response in Hz and the DC gain; the
+    /// node works on the converted taps, Normalize included, and an HRIR set's 512-frame limit applies to the converted length.
+    /// Rate pairs whose conversion table would exceed 2^22 entries throw NotSupportedException.  The conversion is this library's
+    /// own definition (DESIGN.md section 8); turning the option off leaves buffers already assigned alone
+    /// (Stats.ir_resamples counts the buffers converted).</summary>
+    public bool IrResample
+    {
+        get => _irResample;
+        set
+        {
+            GraphAudioHip.Check(_native, GraphAudioHip.ga_set_option(_native, "ir_resample", value ? 1 : 0));
+            _irResample = value;
+        }
+    }
+
     /// <summary>Same contract as OfflineAudioContext.Render (OfflineAudioContext.cs:30-102).</summary>
     public void Render(float[][] output, int frameCount, int startIndex = 0) => RenderCore(output, frameCount, startIndex, -1);
 

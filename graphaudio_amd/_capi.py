@@ -90,6 +90,7 @@ class Stats(C.Structure):
         ("twin_rows", C.c_int64),
         ("delay_flags_read", C.c_int64),
         ("delay_flags_predicted", C.c_int64),
+        ("ir_resamples", C.c_int64),
         ("conv_migrations", C.c_int64),
     ]
     STAGES = ("other", "mix", "rfft_fwd", "mac", "rfft_inv", "coarse_fwd", "coarse_mac", "coarse_inv", "coarse_hist", "coarse_section",

@@ -398,6 +398,10 @@ int ga_set_option(ga_context* ctx, const char* key, double value) {
       if (c.spatialBuiltinHrir != (value != 0)) c.spHeadEpoch++;   // (a node that was on the built-in set finds its set changed)
       c.spatialBuiltinHrir = value != 0;
     }
+    else if (k == "ir_resample") {
+      if (value != 0 && value != 1) fail(GA_ERR_OUT_OF_RANGE, "ir_resample is 0 or 1");
+      c.irResample = value != 0;   // (buffers converted so far, and the nodes on them, stay as they are)
+    }
     else if (k == "spatial_head_radius") {
       if (!(value >= kSpatialHeadRadiusMin && value <= kSpatialHeadRadiusMax)) fail(GA_ERR_OUT_OF_RANGE, "spatial_head_radius is 0.04 .. 0.20 (metres)");
       c.spatialHeadRadius = value;   // (the set is remade in front of the next chunk that needs it)
@@ -837,11 +841,25 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
         });
         return;
       }
-      PlayBuf* b = c.buffer(buffer_id);
-      if (b->sampleRate != c.sampleRate) fail(GA_ERR_INVALID_OPERATION, "HRIR set sample rate must match the audio context sample rate.");
-      if (b->length < 1 || b->length > kSpatialMaxTaps) fail(GA_ERR_INVALID_OPERATION, "HRIR set length must be between 1 and 512 frames.");
+      const PlayBuf* b = c.buffer(buffer_id);
+      // a set at another rate: its copy at the context's rate takes its place (option "ir_resample").  The frame limit is the
+      // kernel's, so it applies to the converted length.
+      const bool convert = b->sampleRate != c.sampleRate && c.irResample;
+      if (b->sampleRate != c.sampleRate && !convert) fail(GA_ERR_INVALID_OPERATION, "HRIR set sample rate must match the audio context sample rate.");
+      if (convert && b->length >= 1) {
+        ga_irr::Plan p;
+        if (ga_irr::ir_resample_plan(b->sampleRate, c.sampleRate, p)) {   // (a pair without a plan is refused by irConverted)
+          const int64_t M = ga_irr::ir_resample_length(b->length, p.L, p.D);
+          if (M > kSpatialMaxTaps)
+            fail(GA_ERR_INVALID_OPERATION, "HRIR set length must be between 1 and 512 frames: " + std::to_string(b->length) + " frames at " + std::to_string(b->sampleRate) +
+                                               " Hz are " + std::to_string(M) + " frames at " + std::to_string(c.sampleRate) + " Hz.");
+        }
+      }
+      if (b->length < 1 || (!convert && b->length > kSpatialMaxTaps)) fail(GA_ERR_INVALID_OPERATION, "HRIR set length must be between 1 and 512 frames.");
       if ((b->channels & 1) || b->channels % (2 * std::max(sn->hrirAzimuths, 1)) != 0)
         fail(GA_ERR_INVALID_OPERATION, "HRIR set channel count must be even and a multiple of 2 * hrirAzimuths.");
+      if (convert) b = c.irConverted(buffer_id);   // (b is the set the node renders with from here on: its rows bound the gain)
+      if (b->length < 1 || b->length > kSpatialMaxTaps) fail(GA_ERR_INVALID_OPERATION, "HRIR set length must be between 1 and 512 frames.");
       double sumMax = 1.0;   // max(1, max over directions and ears of sum |h|): what sum |F| + |D| cannot exceed
       for (const auto& ch : b->host) {
         double sum = 0.0;
@@ -880,8 +898,13 @@ int ga_convolver_set_buffer(ga_context* ctx, int node, int buffer_id) {
     }
     PlayBuf* b = c.buffer(buffer_id);
     if (b->channels > 32) fail(GA_ERR_OUT_OF_RANGE, "Channel count must be between 1 and 32");
-    if (b->sampleRate != c.sampleRate)
-      fail(GA_ERR_INVALID_OPERATION, "Impulse response buffer sample rate must match the audio context sample rate.");
+    if (b->sampleRate != c.sampleRate) {
+      // option "ir_resample": the spectra are built from the buffer's copy at the context's rate (Context::irSpectra reads it through
+      // irSource), so normalizationScale sees the converted taps -- what the reference would see had the caller converted beforehand
+      if (!c.irResample)
+        fail(GA_ERR_INVALID_OPERATION, "Impulse response buffer sample rate must match the audio context sample rate.");
+      (void)c.irConverted(buffer_id);
+    }
     // spectra are built eagerly with the CURRENT Normalize flag (:51-56); the swap is posted (:58-77)
     std::shared_ptr<IrSpectra> sp = c.irSpectra(buffer_id, n->normalize);
     c.post([cp, node, buffer_id, sp]() {

@@ -137,7 +137,7 @@ void Context::refuseSpatialPanners(const ChunkRun& r) {
         fail(GA_ERR_UNSUPPORTED, who + "a signal is connected to occlusion (Steam Audio's occlusion / three-band transmission filters are not known here, "
                                        "and a signal's values cannot be shown to stay at 0)");
     }
-    const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+    const PlayBuf* hb = hrirSetOf(nd.irBuf);
     if (!hb && !spatialBuiltinHrir) fail(GA_ERR_UNSUPPORTED, who + "no HRIR set assigned (the device path has no built-in set)");
     if (hb && ((hb->channels & 1) || hb->channels % (2 * std::max(nd.hrirAzimuths, 1)) != 0 || hb->length < 1 || hb->length > kSpatialMaxTaps))
       fail(GA_ERR_UNSUPPORTED, who + "the HRIR set does not fit hrirAzimuths (channels must be a multiple of 2 * hrirAzimuths, 1 .. 512 frames)");
@@ -159,7 +159,7 @@ void Context::refuseSpatialPanners(const ChunkRun& r) {
   for (int id : r.topo) {
     if (nodes[id]->type != GA_NODE_SPATIAL_PANNER) continue;
     SpatialPannerS& nd = rec<SpatialPannerS>(*nodes[id]);
-    const PlayBuf* hb = (nd.irBuf >= 0 && nd.irBuf < (int)buffers.size()) ? buffers[nd.irBuf].get() : nullptr;
+    const PlayBuf* hb = hrirSetOf(nd.irBuf);
     nd.spSet = hb ? hb : &spHeadSet;
     nd.spAzimuths = hb ? nd.hrirAzimuths : kSpatialHeadAzimuths;
     const uint64_t epoch = hb ? 0 : spHeadEpoch;

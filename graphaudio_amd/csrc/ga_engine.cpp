@@ -288,6 +288,8 @@ Context::~Context() {
   if (deferStage) (void)hipFree(deferStage);
   for (auto& r : retired) (void)hipFree(r.first);
   if (spHeadSet.devBase) (void)hipFree(spHeadSet.devBase);
+  for (auto& kv : irResampled)
+    if (kv.second->devBase) (void)hipFree(kv.second->devBase);
   for (auto& kv : resamplers)
     if (kv.second->devSamples) (void)hipFree(kv.second->devSamples);
   for (auto& np : nodes)
@@ -404,6 +406,10 @@ void Context::collectGarbage() {
       bufVersion++;
       for (auto it = irCache.begin(); it != irCache.end();)   // spectra built from it stay with the convolvers that hold them
         it = it->first.first == id ? irCache.erase(it) : std::next(it);
+      if (auto rs = irResampled.find(id); rs != irResampled.end()) {   // its copy at the context's rate (option "ir_resample")
+        if (rs->second->devBase) dfree(rs->second->devBase, rs->second->devBytes);
+        irResampled.erase(rs);
+      }
       buffers[id].reset();
     }
     releasedPending.swap(keep);
@@ -1038,11 +1044,70 @@ static float normalizationScale(const float* r, int64_t len) {
   return (1.0f / power) * (float)std::pow(10.0, (double)e);
 }
 
+// Option "ir_resample" (ga_ir_resample.hpp; DESIGN.md section 8 "Impulse responses at another sample rate"): the copy of buffer
+// `bufId` at the context's rate, made once -- the table on the host, the sums by ir_resample_kernel on the context's stream from the
+// buffer's device rows, the result copied back because normalizationScale and spGainBound are worked out on the host.  The copy is
+// a buffer of the context's own that no caller id refers to; it lives as long as the buffer it was made from (collectGarbage).
+const PlayBuf* Context::irSource(int bufId) {
+  auto it = irResampled.find(bufId);
+  return it != irResampled.end() ? it->second.get() : buffer(bufId);
+}
+const PlayBuf* Context::irConverted(int bufId) {
+  auto it = irResampled.find(bufId);
+  if (it != irResampled.end()) return it->second.get();
+  const PlayBuf* b = buffer(bufId);
+  ga_irr::Plan p;
+  const std::string pair = std::to_string(b->sampleRate) + " -> " + std::to_string(sampleRate) + " Hz";
+  if (!ga_irr::ir_resample_plan(b->sampleRate, sampleRate, p))
+    fail(GA_ERR_UNSUPPORTED, "ir_resample: the conversion table for " + pair + " would exceed 2^22 entries (L x 2W)");
+  if (ir_resample_tile(p.L, p.D, p.W) < 1) fail(GA_ERR_UNSUPPORTED, "ir_resample: the filter of " + pair + " (W = " + std::to_string(p.W) + ") does not fit the kernel's window");
+  if (b->length < 1 || b->channels < 1) fail(GA_ERR_INVALID_ARGUMENT, "impulse response buffer is empty");
+  const int64_t M = ga_irr::ir_resample_length(b->length, p.L, p.D);
+  const std::vector<double> tab = ga_irr::ir_resample_table(p);
+  GA_HIP(hipSetDevice(device));
+  auto o = std::make_unique<PlayBuf>();
+  o->channels = b->channels;
+  o->length = M;
+  o->sampleRate = sampleRate;
+  o->stride = (M + 8 + 63) / 64 * 64;
+  o->host.resize(b->channels);
+  const size_t bytes = (size_t)o->stride * (size_t)o->channels * sizeof(float), tabBytes = tab.size() * sizeof(double);
+  double* dTab = (double*)dalloc(tabBytes);
+  try {
+    o->dev = dallocSkewed(bytes, &o->devBase, &o->devBytes);
+    GA_HIP(hipMemsetAsync(o->dev, 0, bytes, stream));
+    GA_HIP(hipMemcpyAsync(dTab, tab.data(), tabBytes, hipMemcpyHostToDevice, stream));
+    launch_ir_resample(stream, b->dev, b->stride, b->length, o->dev, o->stride, M, b->channels, p.L, p.D, p.W, p.gain, dTab, p.entries());
+    GA_HIP(hipGetLastError());
+    stats.kernel_launches++;
+    if ((size_t)o->stride * (size_t)o->channels <= ((size_t)1 << 24)) {   // one copy, then the rows (an HRIR set is thousands of short rows)
+      std::vector<float> all((size_t)o->stride * (size_t)o->channels);
+      GA_HIP(hipMemcpyAsync(all.data(), o->dev, bytes, hipMemcpyDeviceToHost, stream));
+      syncStream();
+      for (int c = 0; c < o->channels; c++) o->host[c].assign(all.begin() + (size_t)c * o->stride, all.begin() + (size_t)c * o->stride + M);
+    } else {
+      for (int c = 0; c < o->channels; c++) {
+        o->host[c].resize((size_t)M);
+        GA_HIP(hipMemcpyAsync(o->host[c].data(), o->dev + (size_t)c * o->stride, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, stream));
+      }
+      syncStream();
+    }
+  } catch (...) {
+    syncStreamQuiet();
+    dfree(dTab, tabBytes);
+    if (o->devBase) dfree(o->devBase, o->devBytes);
+    throw;
+  }
+  dfree(dTab, tabBytes);
+  stats.ir_resamples++;
+  return (irResampled[bufId] = std::move(o)).get();
+}
+
 std::shared_ptr<IrSpectra> Context::irSpectra(int bufId, bool normalize) {
   auto key = std::make_pair(bufId, normalize ? 1 : 0);
   auto it = irCache.find(key);
   if (it != irCache.end()) return it->second;
-  PlayBuf* b = buffer(bufId);
+  const PlayBuf* b = irSource(bufId);   // (the buffer itself, or its copy at the context's rate: option "ir_resample")
   if (b->length <= 0) fail(GA_ERR_INVALID_ARGUMENT, "impulse response buffer is empty");
   const int P = (int)((b->length + kBlock - 1) / kBlock);  // ceil(len / blockSize), :44
   const int nch = b->channels;

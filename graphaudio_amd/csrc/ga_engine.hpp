@@ -922,6 +922,19 @@ struct Context {
   void doDispose(int id);
 
   std::shared_ptr<IrSpectra> irSpectra(int bufId, bool normalize);
+  // Option "ir_resample": 1 lets ga_convolver_set_buffer take an impulse response or an HRIR set whose sample rate is not the
+  // context's -- it is converted once, at assignment (ir_resample_kernel), and the copy at the context's rate takes the buffer's
+  // place wherever the node reads it (the spectra and their normalisation; the spatial kernels' rows and spGainBound).  0 = refused,
+  // as the reference does.  Switching the option off leaves the copies that exist, and the nodes on them, alone.
+  bool irResample = false;
+  std::map<int, std::unique_ptr<PlayBuf>> irResampled;   // buffer id -> its copy at the context's rate (beside irCache; dropped with the buffer)
+  const PlayBuf* irConverted(int bufId);                 // makes the copy, or finds it
+  const PlayBuf* irSource(int bufId);                    // the copy if there is one, else the buffer itself
+  const PlayBuf* hrirSetOf(int bufId) const {            // the same for a SpatialPannerNode's irBuf, per chunk; null: no set (or one that is gone)
+    if (bufId < 0 || bufId >= (int)buffers.size() || !buffers[bufId]) return nullptr;
+    auto it = irResampled.find(bufId);
+    return it != irResampled.end() ? it->second.get() : buffers[bufId].get();
+  }
   void releaseConvState(ConvolverS& n);
   void refOrderSensitivity(const std::vector<int>& topo);
   bool ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto);

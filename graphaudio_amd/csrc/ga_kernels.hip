@@ -2612,6 +2612,64 @@ void launch_spatial_head(hipStream_t s, float* out, int64_t stride, int taps, do
 }
 
 // ======================================================================================================
+//  Sample-rate conversion of an impulse response / HRIR set (ga_ir_resample.hpp): workgroup = (tile of outputs, channel), lane =
+//  output.  The tile's input window x[q_first - W + 1 .. q_last + W], clipped to the row, is staged once in LDS; every lane then walks
+//  its output's 2W terms through ga_irr::ir_resample_sample -- the function the host calls -- so the sums are the same operations on
+//  the same numbers.  Neighbouring lanes read the window D / L frames apart: for a ratio such as 24 (192 -> 8 kHz) that is 8 lanes
+//  on one bank of the 32 a ds_read_b32 sees, so the LDS image skips one dword after every 32 (frame i at i + i / 32), which leaves
+//  at most 2.  The table row of a lane (r = m D mod L) is read from global memory: L x 2W doubles stay cache resident (176 KB at
+//  44.1 -> 48 kHz).  Runs once per buffer: milliseconds for a million taps, nothing here is tuned further.
+// ======================================================================================================
+constexpr int kIrResampleLds = kIrResampleWindow + kIrResampleWindow / 32 + 8;   // 8192 floats
+static_assert(kIrResampleLds * sizeof(float) <= 32 * 1024, "the window's LDS image stays within 32 KB");
+__device__ __forceinline__ int ir_resample_slot(int i) { return i + (i >> 5); }
+__global__ __launch_bounds__(256) void ir_resample_kernel(const float* __restrict x, int64_t xstride, int64_t N, float* __restrict y, int64_t ystride,
+                                                          int64_t M, int64_t L, int64_t D, int W, int tile, double gain, const double* __restrict tab) {
+  __shared__ float win[kIrResampleLds];
+  const int64_t m0 = (int64_t)blockIdx.x * tile;
+  if (m0 >= M) return;
+  const int64_t m1 = m0 + tile < M ? m0 + tile : M;
+  const int64_t qa = m0 * D / L, qb = (m1 - 1) * D / L;
+  const int64_t klo = qa - W + 1 > 0 ? qa - W + 1 : 0;
+  const int64_t khi = qb + W + 1 < N ? qb + W + 1 : N;
+  const int64_t wlen = khi - klo;
+  if (wlen < 0 || wlen > kIrResampleWindow) return;   // (launch_ir_resample sized the tile so that this cannot happen)
+  const GA_GLOBAL float* __restrict row = gptr(x) + (int64_t)blockIdx.y * xstride + klo;
+  for (int i = threadIdx.x; i < (int)wlen; i += 256) win[ir_resample_slot(i)] = row[i];
+  __syncthreads();
+  const int64_t m = m0 + threadIdx.x;
+  if (m >= m1) return;
+  const int64_t q = m * D / L, r = m * D - q * L;
+  const float* w = win;
+  gptr(y)[(int64_t)blockIdx.y * ystride + m] =
+      ga_irr::ir_resample_sample([w, klo](int64_t k) { return w[ir_resample_slot((int)(k - klo))]; }, q, N, W, tab + r * 2 * W, gain);
+}
+int ir_resample_tile(int64_t L, int64_t D, int W) {
+  if (L < 1 || D < 1 || W < 1) return 0;
+  const int64_t room = (int64_t)kIrResampleWindow - 2 * (int64_t)W - 1;   // frames q_last may lie behind q_first
+  if (room < 0) return 0;
+  // q(m0 + T - 1) - q(m0) <= floor((T - 1) D / L) + 1
+  const int64_t t = room > ((int64_t)1 << 40) / L ? 256 : room * L / D + 1;
+  return (int)(t < 256 ? t : 256);
+}
+void launch_ir_resample(hipStream_t s, const float* x, int64_t xstride, int64_t N, float* y, int64_t ystride, int64_t M, int channels,
+                        int64_t L, int64_t D, int W, double gain, const double* tab_dev, int64_t tab_entries) {
+  constexpr int64_t kBig = (int64_t)1 << 61;
+  if (!x || !y || !tab_dev) launch_fail("ir_resample_kernel: null pointer");
+  if (channels < 1 || channels > 65535) launch_fail("ir_resample_kernel: channels");
+  if (L < 1 || D < 1 || W < 1 || L > ga_irr::kMaxTable || D > ((int64_t)1 << 31) || tab_entries != L * 2 * (int64_t)W || tab_entries > ga_irr::kMaxTable)
+    launch_fail("ir_resample_kernel: plan");
+  if (N < 1 || N > kBig / L || N > kBig / D) launch_fail("ir_resample_kernel: input length");
+  if (M != ga_irr::ir_resample_length(N, L, D) || M < 1 || M > kBig / D) launch_fail("ir_resample_kernel: output length");
+  if (xstride < N || ystride < M) launch_fail("ir_resample_kernel: stride");
+  const int tile = ir_resample_tile(L, D, W);
+  if (tile < 1) launch_fail("ir_resample_kernel: the window of one output does not fit");
+  const int64_t tiles = (M + tile - 1) / tile;
+  if (tiles > 0x7fffffff) launch_fail("ir_resample_kernel: too many tiles");
+  hipLaunchKernelGGL(ir_resample_kernel, dim3((unsigned)tiles, (unsigned)channels), dim3(256), 0, s, x, xstride, N, y, ystride, M, L, D, W, tile, gain, tab_dev);
+}
+
+// ======================================================================================================
 //  SpatialPannerNode descriptors of signal-driven nodes (ga_kernels.hpp, SpatialDescJob): one lane per (node, block), wave64.
 //  A lane depends on no other lane of the launch: the previous block's geometry, which decides the fade, is recomputed from that
 //  block's inputs (blocks b0 + 1 ..), or read from the carried descriptor an earlier launch or the host left (block b0).

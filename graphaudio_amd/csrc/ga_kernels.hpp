@@ -10,6 +10,7 @@
 #include "ga_spatial_direct.hpp"
 #include "ga_spatial_head.hpp"
 #include "ga_conv_rebuild.hpp"
+#include "ga_ir_resample.hpp"
 
 namespace ga {
 
@@ -718,6 +719,18 @@ void launch_spatial_panner(hipStream_t s, const SpatialWork* works_dev, int nwor
 // head radius `a` to out[channel * stride + k].  One workgroup of one wavefront per channel, a lane per tap; once per set.
 static_assert(kSpatialHeadMaxTaps == kSpatialMaxTaps, "ga_spatial_head.hpp restates the tap limit");
 void launch_spatial_head(hipStream_t s, float* out, int64_t stride, int taps, double fs, double a);
+
+// Sample-rate conversion of an impulse response or an HRIR set (option "ir_resample"; ga_ir_resample.hpp, DESIGN.md section 8
+// "Impulse responses at another sample rate"): y[c * ystride + m], m < M, from x[c * xstride + k], k < N, for c < channels, with the
+// host-made table tab[L][2W].  One workgroup per (tile of ir_resample_tile(L, D, W) consecutive outputs, channel); the tile's input
+// window is staged in LDS and every lane evaluates ga_irr::ir_resample_sample for its output.  Rows need no alignment.  Runs once per
+// buffer.  The launcher checks on the host everything the kernel's indices follow from (N, M, L, D, W, the strides, the table size)
+// and fails through launch_fail -- an error code of the C ABI -- before anything is launched.
+constexpr int kIrResampleWindow = 7936;   // floats of one tile's window at most (33 / 32 of it is the LDS image: 32 KB)
+// outputs per workgroup: the most (<= 256) whose window x[q_first - W + 1 .. q_last + W] fits; 0: none does (2W + 1 > the window)
+int ir_resample_tile(int64_t L, int64_t D, int W);
+void launch_ir_resample(hipStream_t s, const float* x, int64_t xstride, int64_t N, float* y, int64_t ystride, int64_t M, int channels,
+                        int64_t L, int64_t D, int W, double gain, const double* tab_dev, int64_t tab_entries);
 
 // Descriptors made on the device (option "spatial_param_signals"; DESIGN.md "SpatialPannerNode", "Parameters driven by signals"):
 // a node with a signal connected to one of its parameters gets its SpatialDesc entries from spatial_desc_kernel -- one lane per

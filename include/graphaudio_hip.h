@@ -148,6 +148,9 @@ typedef struct ga_stats {
   int64_t delay_flags_predicted; /* (DelayNode, chunk) pairs whose output flag rose by the host's prediction while the option was on: a
                                     delay behind another undecided delay, a modulated playbackRate or a convolver, and with value 1 a
                                     delay on a feedback loop */
+  int64_t ir_resamples;         /* option "ir_resample" (ga_set_option; 0 = off, the default; 1 = on; any other value is
+                                   GA_ERR_OUT_OF_RANGE): buffers that ga_convolver_set_buffer converted to the context's sample rate
+                                   (once per buffer and context, whatever the number of nodes the buffer is assigned to) */
   int64_t conv_migrations;      /* option "conv_migrate" (ga_set_option; 0 = off, the default; 1 = on; any other value is
                                    GA_ERR_OUT_OF_RANGE): ConvolverNodes that were running on formulation D (coarse partitions) or A
                                    (shared-IR groups) when an edit made them sensitive (a consumer that amplifies or quantises
@@ -194,7 +197,13 @@ GA_EXPORT int GA_FN(set_option)(ga_context* ctx, const char* key, double value);
    -- an analytic spherical-head model on 72 azimuths x 25 elevations, made on the device at the context's rate -- instead of being
    refused with GA_ERR_UNSUPPORTED; a node that has a set keeps it; any other value is GA_ERR_OUT_OF_RANGE;
    "spatial_head_radius", default 0.0875: the head radius of that set in metres, 0.04 .. 0.20, outside GA_ERR_OUT_OF_RANGE; a change
-   remakes the set and counts as a change of the HRIR set of the nodes on it; DESIGN.md section 2e "The built-in set") */
+   remakes the set and counts as a change of the HRIR set of the nodes on it; DESIGN.md section 2e "The built-in set";
+   "ir_resample", default 0: 1 lets ga_convolver_set_buffer take a buffer whose sample rate is not the context's, on a GA_NODE_CONVOLVER
+   and on a GA_NODE_SPATIAL_PANNER, instead of refusing it with GA_ERR_INVALID_OPERATION as the reference does: the buffer is converted
+   once, at assignment, by a band-limited (Kaiser-windowed sinc) filter that keeps the response in Hz and the DC gain, and the node
+   works on the converted taps (normalisation included; an HRIR set's 512-frame limit applies to the converted length); rate pairs
+   whose table L x 2W exceeds 2^22 entries are GA_ERR_UNSUPPORTED; switching it off leaves buffers already assigned alone; any other
+   value is GA_ERR_OUT_OF_RANGE; DESIGN.md section 8 "Impulse responses at another sample rate") */
 GA_EXPORT int GA_FN(get_stats)(ga_context* ctx, ga_stats* out);
 
 /* ---- PlayableAudioBuffer.FromChannelArrays (PlayableAudioBuffer.cs:122-145): immutable sample storage ----
