@@ -591,12 +591,12 @@ __global__ __launch_bounds__(256) void tap_spectra_kernel(float2* __restrict hs,
   const float sc = 1.0f / N2;
   for (int i = tid; i < N2; i += 256) dst[i] = make_float2(buf[PADI(i)].x * sc, buf[PADI(i)].y * sc);
 }
-void launch_tap_spectra(hipStream_t s, float2* hs, const float* hr, const float* hi, int nch, int P, int N2, const float2* tw) {
+const char* launch_tap_spectra(hipStream_t s, float2* hs, const float* hr, const float* hi, int nch, int P, int N2, const float2* tw) {
   dim3 g(kBins, nch), b(256);
-  if (N2 == 1024) hipLaunchKernelGGL(tap_spectra_kernel<1024>, g, b, 0, s, hs, hr, hi, P, tw);
-  else if (N2 == 2048) hipLaunchKernelGGL(tap_spectra_kernel<2048>, g, b, 0, s, hs, hr, hi, P, tw);
-  else if (N2 == 4096) hipLaunchKernelGGL(tap_spectra_kernel<4096>, g, b, 0, s, hs, hr, hi, P, tw);
-  else launch_fail("no taps-spectrum kernel for this block-axis FFT length");
+  if (N2 == 1024) { hipLaunchKernelGGL(tap_spectra_kernel<1024>, g, b, 0, s, hs, hr, hi, P, tw); return "tap_spectra_kernel<1024>"; }
+  if (N2 == 2048) { hipLaunchKernelGGL(tap_spectra_kernel<2048>, g, b, 0, s, hs, hr, hi, P, tw); return "tap_spectra_kernel<2048>"; }
+  if (N2 == 4096) { hipLaunchKernelGGL(tap_spectra_kernel<4096>, g, b, 0, s, hs, hr, hi, P, tw); return "tap_spectra_kernel<4096>"; }
+  launch_fail("no taps-spectrum kernel for this block-axis FFT length");
 }
 
 // ---- register/LDS hybrid FFT for the tconv kernel -------------------------------------------------------------------
@@ -771,9 +771,9 @@ __global__ __launch_bounds__(256) void tconv_kernel(const ConvSetC* __restrict s
     item = next;
   }
 }
-void launch_tconv(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw,
-                  int nseg) {
-  if (nsets <= 0 || nblocks <= 0) return;
+const char* launch_tconv(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw,
+                         int nseg) {
+  if (nsets <= 0 || nblocks <= 0) return "";
   size_t lds = ((size_t)3 * TC_PADDED(N2)) * sizeof(float2);
   // N2 = 4096 needs 104 KB of dynamic LDS (gfx950 has 160 KB per CU); per device, so set on every launch of this legacy path
   if (N2 == 4096) (void)hipFuncSetAttribute((const void*)tconv_kernel<4096>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
@@ -781,10 +781,10 @@ void launch_tconv(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblock
   const long long total = (long long)nsets * nseg;
   const int gx = (int)std::min<long long>(total, TC_GROUPS);
   dim3 grid(gx, kBins), block(256);
-  if (N2 == 1024) hipLaunchKernelGGL(tconv_kernel<1024>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw);
-  else if (N2 == 2048) hipLaunchKernelGGL(tconv_kernel<2048>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw);
-  else if (N2 == 4096) hipLaunchKernelGGL(tconv_kernel<4096>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw);
-  else launch_fail("no block-axis FFT kernel for this length");
+  if (N2 == 1024) { hipLaunchKernelGGL(tconv_kernel<1024>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw); return "tconv_kernel<1024>"; }
+  if (N2 == 2048) { hipLaunchKernelGGL(tconv_kernel<2048>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw); return "tconv_kernel<2048>"; }
+  if (N2 == 4096) { hipLaunchKernelGGL(tconv_kernel<4096>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw); return "tconv_kernel<4096>"; }
+  launch_fail("no block-axis FFT kernel for this length");
 }
 
 // (packed-f32 complex arithmetic and the radix-16 register / LDS transform live in ga_fft16.hpp)
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(256, 3) void tconv16_kernel(const ConvSetC* __restr
     const int seg = live ? item % nseg : 0;
     const int P = S->P;
     const int t0 = tbase + seg * (N2 - (P - 1));
-    // window element e = t + T m is block t0 - (P - 1) + e; plane index hist + block >= 0 because hist >= P - 1
+    // window element e = t + T m is block t0 - (P - 1) + e; plane index hist + block >= 0 because hist >= P - 1 (tconv16_hist_ok)
     const int first = hist + t0 - (P - 1);
     const int lim = (live && t0 < nblocks) ? nblocks - (t0 - (P - 1)) : 0;   // elements at or beyond `lim` are zero padding
     const float* __restrict xr = pl.xr + ((size_t)S->x * kBins + k) * pl.tx + first;
@@ -915,13 +915,13 @@ static void launch_tconv16_n(hipStream_t s, const ConvSetC* sets_dev, int nsets,
   dim3 grid((unsigned)std::min<long long>(steps * kBins, groups)), block(256);
   hipLaunchKernelGGL(tconv16_kernel<N2>, grid, block, lds, s, sets_dev, nsets, nseg, nblocks, hist, pl, tw16, tbase);
 }
-void launch_tconv16(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw16,
-                    int nseg, int tbase) {
-  if (nsets <= 0 || nblocks <= 0 || nseg <= 0) return;
-  if (N2 == 1024) launch_tconv16_n<1024>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase);
-  else if (N2 == 2048) launch_tconv16_n<2048>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase);
-  else if (N2 == 4096) launch_tconv16_n<4096>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase);
-  else launch_fail("no block-axis FFT kernel for this length");
+const char* launch_tconv16(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw16,
+                           int nseg, int tbase) {
+  if (nsets <= 0 || nblocks <= 0 || nseg <= 0) return "";
+  if (N2 == 1024) { launch_tconv16_n<1024>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase); return "tconv16_kernel<1024>"; }
+  if (N2 == 2048) { launch_tconv16_n<2048>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase); return "tconv16_kernel<2048>"; }
+  if (N2 == 4096) { launch_tconv16_n<4096>(s, sets_dev, nsets, nblocks, hist, pl, tw16, nseg, tbase); return "tconv16_kernel<4096>"; }
+  launch_fail("no block-axis FFT kernel for this length");
 }
 
 // ---- plane utilities ----------------------------------------------------------------------------------

@@ -134,14 +134,20 @@ struct ConvSetC {
   int P;
   const float2* hs[16];    // per column: [kBins][N2] spectrum of the taps along the partition axis
 };
-// spectra of the taps: hs[c][k][0..N2) = FFT_N2( H[c][k][0..P) zero padded )
-void launch_tap_spectra(hipStream_t s, float2* hs, const float* hr, const float* hi, int nch, int P, int N2, const float2* tw);
-void launch_tconv(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw,
-                  int nseg);
+// spectra of the taps: hs[c][k][0..N2) = FFT_N2( H[c][k][0..P) zero padded ) / N2  (the 1/N2 of the inverse transform is folded in)
+// (the three launchers return the name of the kernel instance they launched, "" if there was nothing to launch)
+const char* launch_tap_spectra(hipStream_t s, float2* hs, const float* hr, const float* hi, int nch, int P, int N2, const float2* tw);
+// every set of one launch has the same P; the nseg segments of N2 - (P - 1) blocks start at block 0 and cover the chunk; any hist >= 0
+// (blocks in front of -hist read as zero)
+const char* launch_tconv(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw,
+                         int nseg);
 // radix-16 variant; tw16 = [15][16] W_256^(kk m) followed by [N2/256 - 1][256] W_N2^(j m) (Context::twiddles16)
 // the launch covers the nseg segments that start at block `tbase` (a chunk may be covered by launches of different N2)
-void launch_tconv16(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw16,
-                    int nseg, int tbase);
+// Precondition: hist >= P - 1 for every set.  The kernel forms the address of window element 0, plane index hist + t0 - (P - 1), without
+// a guard in front of -hist (the radix-8 kernel has one); the planner's hist is roundup(longest history, 4) >= P - 1.
+constexpr bool tconv16_hist_ok(int hist, int P) { return hist >= P - 1; }
+const char* launch_tconv16(hipStream_t s, const ConvSetC* sets_dev, int nsets, int nblocks, int hist, ConvPlanesB pl, int N2, const float2* tw16,
+                           int nseg, int tbase);
 
 // ---- convolver pipeline, formulation D: coarse partitions, consumer sum fused in the frequency domain (ga_coarse.hip) ----
 constexpr int kCoarseBlock = 8192;   // samples per coarse partition / output block
