@@ -1114,9 +1114,6 @@ struct ConvGroupLess {   // ordered by (IR buffer, IR channel) so groups fed by 
 
 struct ConvPlanCtx {
   std::map<ConvGroup*, std::vector<std::pair<int, int>>, ConvGroupLess> active;   // group -> (node, slot)
-  std::vector<const float*> prevIns;
-  int prevP = -1, prevRp = -1, prevRows = -1;
-  std::vector<int> bNodes, dNodes;
   std::unordered_map<int, std::array<float*, 4>> tsTemps;   // true-stereo temp outputs per node
 };
 

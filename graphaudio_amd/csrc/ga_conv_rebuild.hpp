@@ -43,4 +43,24 @@ constexpr int kRebuildTy = 4;
 // which input channel a slot reads: discrete -> slot c reads input c ; true stereo -> (L,h0) (L,h1) (R,h2) (R,h3)
 GA_HD inline int conv_slot_input(bool trueStereo, int slot) { return trueStereo ? (slot >> 1) : slot; }
 
+// The sets of a node on the B / C / R state layout: its slots (columns) grouped by the x-row they read, at most kConvSetCols per set
+// (ConvSetB / ConvSetC).  For x-row xc = 0 .. nxr - 1 in turn, visit(xc, slots, ncol) receives the slots that read it, ascending, in
+// runs of at most kConvSetCols; `shared`: the node's one x-row feeds every slot.  Nothing is allocated: a chunk plans a thousand nodes.
+constexpr int kConvSetCols = 16;
+template <class Visit>
+inline void conv_for_each_set(bool shared, bool trueStereo, int nxr, int bSlots, Visit&& visit) {
+  for (int xc = 0; xc < nxr; xc++) {
+    int run[kConvSetCols], ncol = 0;
+    for (int slot = 0; slot < bSlots; slot++) {
+      if (!shared && conv_slot_input(trueStereo, slot) != xc) continue;
+      run[ncol++] = slot;
+      if (ncol == kConvSetCols) {
+        visit(xc, (const int*)run, ncol);
+        ncol = 0;
+      }
+    }
+    if (ncol > 0) visit(xc, (const int*)run, ncol);
+  }
+}
+
 }  // namespace ga

@@ -1150,7 +1150,7 @@ std::shared_ptr<IrSpectra> Context::irSpectra(int bufId, bool normalize) {
       syncStream();
       GA_HIP(hipMemcpy(rowsDev, r2.data(), sizeof(ConvRowIO) * nch, hipMemcpyHostToDevice));
     }
-    launch_rfft_fwd(stream, rowsDev, nch, nb, t0, pl, Twiddles{w128, w256});
+    launch_rfft_fwd(stream, rowsDev, nch, nb, t0, pl, twiddles());
   }
   launch_extract_ir(stream, sp->hr, sp->hi, xr, xi, P, rp, P, nch);
   syncStream();

@@ -814,6 +814,7 @@ struct Context {
   // device resources
   double2* w128 = nullptr;
   double2* w256 = nullptr;
+  Twiddles twiddles() const { return Twiddles{w128, w256}; }
   std::map<int, float2*> twC;   // float32 twiddles exp(-2 pi i j / N2) for the block-axis FFTs
   float* zeros = nullptr;  // zero page (chunk frames)
   int64_t zerosLen = 0;
@@ -1111,8 +1112,7 @@ struct Context {
   void planGain(NodePlanCtx& k);
   void planBiquad(NodePlanCtx& k);
   void chunkPlanConvolvers(ChunkRun& r, int depth);
-  void planConvolversShared(ChunkRun& r, int depth, ConvPlanCtx& k);    // formulation A groups
-  void planConvolversPrivate(ChunkRun& r, int depth, ConvPlanCtx& k, bool refOrder);   // formulations B / C, and R on their state layout
+  void planConvolversShared(ChunkRun& r, ConvPlanCtx& k);    // formulation A groups (B / C / R: PrivateStage, ga_plan_conv.cpp)
   void chunkDelayCommit(ChunkRun& r);
   void chunkStaleSeed(ChunkRun& r);
   void chunkStaleCommit(ChunkRun& r);   // feedback cycles: the block every stale producer put out becomes what its consumers read next

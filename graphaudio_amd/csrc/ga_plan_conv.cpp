@@ -139,6 +139,28 @@ static const float* convChunkInput(Context& c, Exec& ex, const Exec::ConvInRow& 
   return slab;
 }
 
+// true stereo: the slab that slot `slot` of node `id` renders into; chunkPlanConvolvers sums the four of a node into its two outputs
+static float* trueStereoTemp(Context& c, ConvPlanCtx& k, int id, int slot) {
+  float* tmp = getSlab(c);
+  k.tsTemps.emplace(id, std::array<float*, 4>{}).first->second[slot] = tmp;
+  return tmp;
+}
+
+// one set of the B / R partition sums: x-row `x`, y rows from `y0`, the spectra of the slots' impulse-response channels (slot index ==
+// IR channel index in both slot layouts)
+static ConvSetB makeSetB(const IrSpectra& ir, int x, int y0, const int* slots, int ncol) {
+  ConvSetB st{};
+  st.x = x;
+  st.y0 = y0;
+  st.ncol = ncol;
+  st.P = ir.P;
+  for (int j = 0; j < ncol; j++) {
+    st.hr[j] = ir.hr + (size_t)slots[j] * kBins * ir.P;
+    st.hi[j] = ir.hi + (size_t)slots[j] * kBins * ir.P;
+  }
+  return st;
+}
+
 // the hist_len samples in front of the chunk of input channel `ch`: a span of a PlayableAudioBuffer, the node's own copy, or nothing yet
 static const float* coarseHistory(const ConvolverS& nd, int ch) {
   if (ch < (int)nd.dHistExt.size() && nd.dHistExt[ch].first) return nd.dHistExt[ch].first;
@@ -986,27 +1008,14 @@ void Context::planConvMigration(ChunkRun& r) {
     const int nxr = nd.bShared ? 1 : nd.bInCh;
     const int x0 = (int)jobs.size();
     for (int ch = 0; ch < nxr; ch++) jobs.push_back(ConvRebuildJob{mg->src[ch], nd.bHistR + ch * hstride, nd.bHistI + ch * hstride, P, x0 + ch});
-    for (int xc = 0; xc < nxr; xc++) {   // sets as planConvolversPrivate makes them: columns by the x-row they read, 16 per set
-      std::vector<int> cols;
-      for (int slot = 0; slot < nd.bSlots; slot++)
-        if (nd.bShared || conv_slot_input(nd.isTrueStereo, slot) == xc) cols.push_back(slot);
-      for (size_t c0 = 0; c0 < cols.size(); c0 += 16) {
-        ConvSetB st{};
-        st.x = x0 + xc;
-        st.y0 = (int)yrows.size();
-        st.ncol = (int)std::min<size_t>(16, cols.size() - c0);
-        st.P = P;
-        for (int j = 0; j < st.ncol; j++) {
-          const int slot = cols[c0 + j];
-          st.hr[j] = nd.ir->hr + (size_t)slot * kBins * P;
-          st.hi[j] = nd.ir->hi + (size_t)slot * kBins * P;
-          yrows.push_back(ConvRowIO{nullptr, nullptr});
-          ovIn.push_back(zeros);
-          ovOut.push_back(nd.bOverlap + ((size_t)slot * 2 + nd.bOvCur) * kBlock);
-        }
-        sets.push_back(st);
+    conv_for_each_set(nd.bShared, nd.isTrueStereo, nxr, nd.bSlots, [&](int xc, const int* slots, int ncol) {
+      sets.push_back(makeSetB(*nd.ir, x0 + xc, (int)yrows.size(), slots, ncol));
+      for (int j = 0; j < ncol; j++) {   // no output row, an overlap-in of zeros: what is left is the overlap the chunk's first block reads
+        yrows.push_back(ConvRowIO{nullptr, nullptr});
+        ovIn.push_back(zeros);
+        ovOut.push_back(nd.bOverlap + ((size_t)slots[j] * 2 + nd.bOvCur) * kBlock);
       }
-    }
+    });
     flops += 8.0 * P * kBins * (double)nd.bSlots;
   }
   // scratch planes of this chunk alone: freed with the retire list, after the stream has run the launches below
@@ -1017,7 +1026,7 @@ void Context::planConvMigration(ChunkRun& r) {
   const size_t jo = ex.plan.putv(jobs), so = ex.plan.putv(sets), yo = ex.plan.putv(yrows), oi = ex.plan.putv(ovIn), oo = ex.plan.putv(ovOut);
   const int nj = (int)jobs.size(), ns_ = (int)sets.size(), ny = (int)yrows.size();
   hipStream_t st = stream;
-  Twiddles tw{w128, w256};
+  Twiddles tw = twiddles();
   Context* cp = this;
   ex.plan.add(LK_FFT, [=](uint8_t* base) {
     GA_HIP(hipMemsetAsync(scratch, 0, 2 * xb, st));   // (columns in front of a shorter node's first block)
@@ -1163,12 +1172,12 @@ void Context::chunkConvScratch(ChunkRun& r) {
 
 // formulation A: convolvers that share an impulse-response channel run as one group per (impulse response, channel) -- the
 // banded-Toeplitz matrix-core kernel or the block-axis transforms over all their rows (PartitionedConvolver.cs:104-223)
-void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
-  int64_t& n = r.n;
-  std::vector<Segment>& segs = r.segs;
+void Context::planConvolversShared(ChunkRun& r, ConvPlanCtx& k) {
+  const int64_t n = r.n;
   Exec& ex = *r.ex;
-  auto& active = k.active; auto& tsTemps = k.tsTemps; auto& prevIns = k.prevIns; int& prevP = k.prevP; int& prevRp = k.prevRp; int& prevRows = k.prevRows;
-  for (auto& kv : active) {
+  std::vector<const float*> prevIns;   // the inputs of the group planned before this one (forward spectra still in the scratch planes)
+  int prevP = -1, prevRp = -1, prevRows = -1;
+  for (auto& kv : k.active) {
     ConvGroup& g = *kv.first;
     const int P = g.P, hist = P - 1;
     const int nrows = (int)g.rows.size();
@@ -1176,47 +1185,11 @@ void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
     for (auto& ns_ : kv.second) {
       ConvolverS& nd = rec<ConvolverS>(*nodes[ns_.first]);
       const int slot = ns_.second;
-      const int idx = nd.convRows[slot].idx;
       // which input channel feeds this row: discrete -> slot ; true stereo -> L,L,R,R for h0,h1,h2,h3 (ConvolverNode.cs:127-151)
-      const int inCh = nd.isTrueStereo ? (slot >> 1) : slot;
-      const Exec::ConvInRow ci = ex.convIn[ns_.first];
-      const float* stable = nullptr;
-      bool same = true, first = true;
-      for (size_t si = 0; si < segs.size(); si++) {
-        const float* v = (ci[si].empty() || inCh >= (int)ci[si].size()) ? nullptr : ci[si][inCh];
-        if (first) { stable = v; first = false; } else if (v != stable) same = false;
-      }
-      const float* in = stable;
-      if (!same) {  // materialise: per segment copy / zero fill into a row slab
-        float* slab = getSlab(*this);
-        for (size_t si = 0; si < segs.size(); si++) {
-          const float* v = (ci[si].empty() || inCh >= (int)ci[si].size()) ? nullptr : ci[si][inCh];
-          MixJob mj;
-          mj.out = slab;
-          mj.term0 = (int)ex.terms.size();
-          mj.nterms = v ? 1 : 0;
-          mj.f0 = segs[si].b0 * kBlock;
-          mj.n = (segs[si].b1 - segs[si].b0) * kBlock;
-          if (v) {
-            ex.terms.push_back(v);
-            ex.noteAlign(v, mj.f0);
-          }
-          ex.mixJobs.push_back(mj);
-        }
-        in = slab;
-      }
-      float* out;
-      if (nd.isTrueStereo) {
-        out = getSlab(*this);  // temp1 / temp2, summed below (ConvolverNode.cs:137-143)
-      } else {
-        out = ex.nodeOut(ns_.first, slot);
-      }
-      rio[idx] = ConvRowIO{in, out};
-      if (nd.isTrueStereo) {
-        auto it = tsTemps.find(ns_.first);
-        if (it == tsTemps.end()) it = tsTemps.emplace(ns_.first, std::array<float*, 4>{nullptr, nullptr, nullptr, nullptr}).first;
-        it->second[slot] = out;
-      }
+      const float* in = convChunkInput(*this, ex, ex.convIn[ns_.first], conv_slot_input(nd.isTrueStereo, slot));
+      // (true stereo: temp1 / temp2, summed behind the stage, ConvolverNode.cs:137-143)
+      float* out = nd.isTrueStereo ? trueStereoTemp(*this, k, ns_.first, slot) : ex.nodeOut(ns_.first, slot);
+      rio[nd.convRows[slot].idx] = ConvRowIO{in, out};
     }
     ex.flushLevel();
     const int rp = g.rp;
@@ -1225,7 +1198,7 @@ void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
     ConvPlanes pl{(float*)planes[0].p, (float*)planes[1].p, (float*)planes[2].p, (float*)planes[3].p, tx, ty, rp};
     size_t rioOff = ex.plan.putv(rio);
     hipStream_t st = stream;
-    Twiddles tw{w128, w256};
+    Twiddles tw = twiddles();
     const int nn = (int)n;
     float* hR = g.histR;
     float* hI = g.histI;
@@ -1273,218 +1246,204 @@ void Context::planConvolversShared(ChunkRun& r, int /*d*/, ConvPlanCtx& k) {
   }
 }
 
-// formulations B / C: nodes with an impulse response of their own (per-node planes; block-axis FFT segments or the direct sum)
-void Context::planConvolversPrivate(ChunkRun& r, int /*d*/, ConvPlanCtx& k, bool refOrder) {
-  int64_t& n = r.n;
-  std::vector<Segment>& segs = r.segs;
-  Exec& ex = *r.ex;
-  const std::vector<int>& bNodes = k.bNodes; auto& tsTemps = k.tsTemps;
-  const int hist = (int)roundup(r.bHistMax, 4);   // plane time origin, 16-byte aligned rows
-  const int txb = hist + (int)roundup(n, 16) + 16, tyb = (int)roundup(n, 256);
-  // rows of this depth start after the rows of the depths before it: a node's spectra stay intact for the next chunk
-  const size_t rowX0 = bRowX, rowY0 = bRowY;
-  ConvPlanesB plb{xPlane(bPairWrite, 0) + rowX0 * kBins * txb, xPlane(bPairWrite, 1) + rowX0 * kBins * txb,
-                  (float*)planesB[2].p + rowY0 * kBins * tyb, (float*)planesB[3].p + rowY0 * kBins * tyb, txb, tyb};
+// One private-IR convolver stage of a chunk: nodes with an impulse response of their own on the B / C state layout (per-node planes;
+// the direct partition sum, block-axis FFT segments, or -- refOrder -- formulation R: the reference's own order between
+// double-precision transforms).  Planned node by node in four passes, then enqueued and accounted (planPrivateStage).
+namespace {
+struct PrivateStage {
+  Context& c;
+  Exec& ex;
+  ConvPlanCtx& k;
+  const std::vector<int>& bNodes;
+  const bool refOrder;
+  const int64_t n;
+  const int hist;       // plane time origin, 16-byte aligned rows
+  const int txb, tyb;   // columns of an x row / a y row
+  // rows of this stage start after the rows of the stages before it: a node's spectra stay intact for the next chunk
+  const size_t rowX0, rowY0;
+  const ConvPlanesB plb;
+  struct SetTaps { IrSpectra* ir; int slot[kConvSetCols]; };
+  using TconvLaunch = Context::TconvLaunch;
   std::vector<ConvRowIO> xrows, yrows;
-  std::vector<ConvSetB> sets;
-  std::map<int, std::vector<ConvSetC>> setsC;   // by P: launches per distinct segment length
-  struct SetTaps { IrSpectra* ir; int slot[16]; };
-  std::map<int, std::vector<SetTaps>> setsCTaps;   // which taps spectra each column of a set needs (filled per FFT length)
   std::vector<HistJobB> restore;
+  std::vector<ConvSetB> sets;                        // formulations B and R
+  std::map<int, std::vector<ConvSetC>> setsC;        // formulation C, by P: launches per distinct segment length
+  std::map<int, std::vector<SetTaps>> setsCTaps;     // which taps spectra each column of a set needs (filled per FFT length)
   std::vector<const float*> ovIn;
   std::vector<float*> ovOut;
   double flops = 0;
-  std::vector<const float*> chIn;   // (scratch vectors live outside the node loop: a thousand convolvers per chunk)
-  std::vector<float*> slotOut;
-  std::vector<int> cols;
-  for (int id : bNodes) {
-    ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
-    const int P = nd.ir->P, h = P - 1;
-    const Exec::ConvInRow ci = ex.convIn[id];
-    // chunk-long input pointer of every input channel (stable view, or a materialised copy)
-    chIn.assign(nd.bInCh, nullptr);
-    for (int c = 0; c < nd.bInCh; c++) {
-      const float* stable = nullptr;
-      bool same = true, first = true;
-      for (size_t si = 0; si < segs.size(); si++) {
-        const float* v = (ci[si].empty() || c >= (int)ci[si].size()) ? nullptr : ci[si][c];
-        if (first) { stable = v; first = false; } else if (v != stable) same = false;
-      }
-      if (same) {
-        chIn[c] = stable;
+  Views chIn;   // chunk-long views of the current node's input channels
+
+  PrivateStage(Context& c_, ChunkRun& r, ConvPlanCtx& k_, const std::vector<int>& nodes_, bool refOrder_)
+      : c(c_), ex(*r.ex), k(k_), bNodes(nodes_), refOrder(refOrder_), n(r.n), hist((int)roundup(r.bHistMax, 4)),
+        txb(hist + (int)roundup(r.n, 16) + 16), tyb((int)roundup(r.n, 256)), rowX0(c_.bRowX), rowY0(c_.bRowY),
+        plb{c_.xPlane(c_.bPairWrite, 0) + rowX0 * kBins * txb, c_.xPlane(c_.bPairWrite, 1) + rowX0 * kBins * txb,
+            (float*)c_.planesB[2].p + rowY0 * kBins * tyb, (float*)c_.planesB[3].p + rowY0 * kBins * tyb, txb, tyb} {}
+  void resolveInputs(int id, ConvolverS& nd);          // chunk-long input views; the shared -> private history hand-down
+  int buildRows(ConvolverS& nd);                       // x rows and the jobs that restore their columns around the chunk; -> first row
+  void buildSets(int id, ConvolverS& nd, int x0);      // B / R sets, C sets and their tap lists, y rows, overlaps
+  void keepHistory(int id, ConvolverS& nd, int x0);    // where the next chunk finds this node's last P - 1 spectra
+  void enqueue();                                      // tables into the plan, launches
+  void enqueueTimeFft();                               // formulation C: one launch per P and segment length
+  void account();                                      // flops, streaming-formulation bytes, the stage's launch count
+};
+
+void PrivateStage::resolveInputs(int id, ConvolverS& nd) {
+  chIn.assign(nd.bInCh, nullptr);
+  for (int ch = 0; ch < nd.bInCh; ch++) chIn[ch] = convChunkInput(c, ex, ex.convIn[id], ch);
+  bool allSame = true;
+  for (int ch = 1; ch < nd.bInCh; ch++) allSame = allSame && (chIn[ch] == chIn[0]);
+  if (!nd.bShared || allSame) return;
+  // the channels start to differ: every channel inherits the (so far common) history of channel 0
+  const int h = nd.ir->P - 1;
+  const size_t hstride = (size_t)kBins * std::max(h, 1);
+  if (!nd.bHistZero && h > 0 && nd.bHistPlane < 0)   // (a plane-resident shared row is simply read by every channel)
+    for (int ch = 1; ch < nd.bInCh; ch++) {   // (plan entries: ordered with the chunk's launches)
+      float *dr = nd.bHistR + ch * hstride, *di = nd.bHistI + ch * hstride;
+      const float *sr = nd.bHistR, *sim = nd.bHistI;
+      hipStream_t st = c.stream;
+      ex.plan.add(LK_OTHER, [dr, di, sr, sim, hstride, st](uint8_t*) {
+        GA_HIP(hipMemcpyAsync(dr, sr, hstride * 4, hipMemcpyDeviceToDevice, st));
+        GA_HIP(hipMemcpyAsync(di, sim, hstride * 4, hipMemcpyDeviceToDevice, st));
+      });
+    }
+  nd.bShared = false;
+}
+
+int PrivateStage::buildRows(ConvolverS& nd) {
+  const int h = nd.ir->P - 1;
+  const size_t hstride = (size_t)kBins * std::max(h, 1);
+  const int nxr = nd.bShared ? 1 : nd.bInCh;
+  const int x0 = (int)xrows.size();
+  for (int ch = 0; ch < nxr; ch++) {
+    const int xi = x0 + ch;
+    xrows.push_back(ConvRowIO{chIn[ch], nullptr});
+    float* xr_row = plb.xr + (size_t)xi * kBins * txb;
+    float* xi_row = plb.xi + (size_t)xi * kBins * txb;
+    // [0, hist - h) zeros, [hist - h, hist) this channel's history, rows after the chunk zero (K padding reads them)
+    if (hist - h > 0) {
+      restore.push_back(HistJobB{xr_row, nullptr, txb, 0, hist - h, 0});
+      restore.push_back(HistJobB{xi_row, nullptr, txb, 0, hist - h, 0});
+    }
+    if (h > 0) {
+      const float *srcR = nullptr, *srcI = nullptr;
+      int sstride = h;
+      if (nd.bHistZero) {
+      } else if (nd.bHistPlane >= 0) {   // the previous chunk's x planes (never the pair being written: flushed in chunkConvScratch)
+        const size_t off = (size_t)(nd.bHistRow + (nd.bHistNx == 1 ? 0 : ch)) * kBins * nd.bHistTxb + nd.bHistOff;
+        srcR = c.xPlane(nd.bHistPlane, 0) + off;
+        srcI = c.xPlane(nd.bHistPlane, 1) + off;
+        sstride = nd.bHistTxb;
       } else {
-        float* slab = getSlab(*this);
-        for (size_t si = 0; si < segs.size(); si++) {
-          const float* v = (ci[si].empty() || c >= (int)ci[si].size()) ? nullptr : ci[si][c];
-          MixJob mj;
-          mj.out = slab;
-          mj.term0 = (int)ex.terms.size();
-          mj.nterms = v ? 1 : 0;
-          mj.f0 = segs[si].b0 * kBlock;
-          mj.n = (segs[si].b1 - segs[si].b0) * kBlock;
-          if (v) {
-            ex.terms.push_back(v);
-            ex.noteAlign(v, mj.f0);
-          }
-          ex.mixJobs.push_back(mj);
-        }
-        chIn[c] = slab;
+        srcR = nd.bHistR + ch * hstride;
+        srcI = nd.bHistI + ch * hstride;
       }
+      restore.push_back(HistJobB{xr_row + (hist - h), srcR, txb, sstride, h, 0});
+      restore.push_back(HistJobB{xi_row + (hist - h), srcI, txb, sstride, h, 0});
     }
-    bool allSame = true;
-    for (int c = 1; c < nd.bInCh; c++) allSame = allSame && (chIn[c] == chIn[0]);
-    const size_t hstride = (size_t)kBins * std::max(h, 1);
-    if (nd.bShared && !allSame) {
-      // the channels start to differ: every channel inherits the (so far common) history of channel 0
-      if (!nd.bHistZero && h > 0 && nd.bHistPlane < 0)   // (a plane-resident shared row is simply read by every channel)
-        for (int c = 1; c < nd.bInCh; c++) {   // (plan entries: ordered with the chunk's launches)
-          float *dr = nd.bHistR + c * hstride, *di = nd.bHistI + c * hstride;
-          const float *sr = nd.bHistR, *sim = nd.bHistI;
-          hipStream_t st = stream;
-          ex.plan.add(LK_OTHER, [=](uint8_t*) {
-            GA_HIP(hipMemcpyAsync(dr, sr, hstride * 4, hipMemcpyDeviceToDevice, st));
-            GA_HIP(hipMemcpyAsync(di, sim, hstride * 4, hipMemcpyDeviceToDevice, st));
-          });
-        }
-      nd.bShared = false;
-    }
-    const int nxr = nd.bShared ? 1 : nd.bInCh;
-    const int x0 = (int)xrows.size();
-    for (int c = 0; c < nxr; c++) {
-      const int xi = x0 + c;
-      xrows.push_back(ConvRowIO{chIn[c], nullptr});
-      float* xr_row = plb.xr + (size_t)xi * kBins * txb;
-      float* xi_row = plb.xi + (size_t)xi * kBins * txb;
-      // [0, hist - h) zeros, [hist - h, hist) this channel's history, rows after the chunk zero (K padding reads them)
-      if (hist - h > 0) {
-        restore.push_back(HistJobB{xr_row, nullptr, txb, 0, hist - h, 0});
-        restore.push_back(HistJobB{xi_row, nullptr, txb, 0, hist - h, 0});
-      }
-      if (h > 0) {
-        const float *srcR = nullptr, *srcI = nullptr;
-        int sstride = h;
-        if (nd.bHistZero) {
-        } else if (nd.bHistPlane >= 0) {   // the previous chunk's x planes (never the pair being written: flushed above)
-          const size_t off = (size_t)(nd.bHistRow + (nd.bHistNx == 1 ? 0 : c)) * kBins * nd.bHistTxb + nd.bHistOff;
-          srcR = xPlane(nd.bHistPlane, 0) + off;
-          srcI = xPlane(nd.bHistPlane, 1) + off;
-          sstride = nd.bHistTxb;
-        } else {
-          srcR = nd.bHistR + c * hstride;
-          srcI = nd.bHistI + c * hstride;
-        }
-        restore.push_back(HistJobB{xr_row + (hist - h), srcR, txb, sstride, h, 0});
-        restore.push_back(HistJobB{xi_row + (hist - h), srcI, txb, sstride, h, 0});
-      }
-      const int tailn = txb - (hist + (int)n);
-      restore.push_back(HistJobB{xr_row + hist + (int)n, nullptr, txb, 0, tailn, 0});
-      restore.push_back(HistJobB{xi_row + hist + (int)n, nullptr, txb, 0, tailn, 0});
-    }
-    // slots: discrete -> slot c reads input c, IR channel c ; true stereo -> (L,h0) (L,h1) (R,h2) (R,h3)
-    slotOut.assign(nd.bSlots, nullptr);
-    for (int slot = 0; slot < nd.bSlots; slot++) {
-      if (nd.isTrueStereo) {
-        float* tmp = getSlab(*this);
-        slotOut[slot] = tmp;
-        auto it = tsTemps.find(id);
-        if (it == tsTemps.end()) it = tsTemps.emplace(id, std::array<float*, 4>{nullptr, nullptr, nullptr, nullptr}).first;
-        it->second[slot] = tmp;
-      } else {
-        slotOut[slot] = ex.nodeOut(id, slot);
-      }
-    }
-    // sets: columns grouped by the x-row they read, at most 16 per set, y rows consecutive per set
-    for (int xc = 0; xc < nxr; xc++) {
-      cols.clear();
-      for (int slot = 0; slot < nd.bSlots; slot++) {
-        int inc = nd.isTrueStereo ? (slot >> 1) : slot;
-        if (nd.bShared || inc == xc) cols.push_back(slot);
-      }
-      for (size_t c0 = 0; c0 < cols.size(); c0 += 16) {
-        ConvSetB st{};
-        st.x = x0 + xc;
-        st.y0 = (int)yrows.size();
-        st.ncol = (int)std::min<size_t>(16, cols.size() - c0);
-        st.P = P;
-        ConvSetC sc{};
-        sc.x = st.x;
-        sc.y0 = st.y0;
-        sc.ncol = st.ncol;
-        sc.P = P;
-        for (int j = 0; j < st.ncol; j++) {
-          int slot = cols[c0 + j];
-          st.hr[j] = nd.ir->hr + (size_t)slot * kBins * P;   // slot index == IR channel index in both modes
-          st.hi[j] = nd.ir->hi + (size_t)slot * kBins * P;
-          sc.hs[j] = nullptr;   // per FFT length, below
-          yrows.push_back(ConvRowIO{nullptr, slotOut[slot]});
-          ovIn.push_back(nd.bOverlap + ((size_t)slot * 2 + nd.bOvCur) * kBlock);
-          ovOut.push_back(nd.bOverlap + ((size_t)slot * 2 + (nd.bOvCur ^ 1)) * kBlock);
-        }
-        if (refOrder) {
-          sets.push_back(st);
-          stats.ref_order_rows += st.ncol;
-        } else if (nd.convPath == 3) {
-          SetTaps tp{nd.ir.get(), {}};
-          for (int j = 0; j < st.ncol; j++) tp.slot[j] = cols[c0 + j];
-          setsC[P].push_back(sc);
-          setsCTaps[P].push_back(tp);
-        } else {
-          sets.push_back(st);
-        }
-      }
-    }
-    nd.bOvCur ^= 1;
-    nd.bHistZero = false;
-    if (h > 0) {   // the history of the next chunk: the last h spectra of these rows
-      if (nd.bHistPlane == bPairWrite) fail(GA_ERR_DEVICE, "internal: convolver history lives in the planes being written");
-      nd.bHistPlane = bPairWrite;
-      nd.bHistRow = (int)rowX0 + x0;
-      nd.bHistNx = nxr;
-      nd.bHistOff = hist + (int)n - h;
-      nd.bHistTxb = txb;
-      bResidents[bPairWrite].push_back(id);
-    }
-    flops += 8.0 * P * kBins * (double)nd.bSlots * (double)n;
+    const int tailn = txb - (hist + (int)n);
+    restore.push_back(HistJobB{xr_row + hist + (int)n, nullptr, txb, 0, tailn, 0});
+    restore.push_back(HistJobB{xi_row + hist + (int)n, nullptr, txb, 0, tailn, 0});
   }
-  bRowX += xrows.size();
-  bRowY += yrows.size();
-  bPairCur = bPairWrite;
-  ex.flushLevel();
-  size_t xo = ex.plan.putv(xrows), yo = ex.plan.putv(yrows), so = ex.plan.putv(sets), ro = ex.plan.putv(restore),
-         oi = ex.plan.putv(ovIn), oo = ex.plan.putv(ovOut);
+  return x0;
+}
+
+void PrivateStage::buildSets(int id, ConvolverS& nd, int x0) {
+  // slots: discrete -> slot c reads input c, IR channel c ; true stereo -> (L,h0) (L,h1) (R,h2) (R,h3), into temps summed behind the stage
+  float* slotOut[32];
+  if (nd.bSlots > 32) fail(GA_ERR_INVALID_OPERATION, "internal: more than 32 convolver slots");
+  for (int slot = 0; slot < nd.bSlots; slot++) slotOut[slot] = nd.isTrueStereo ? trueStereoTemp(c, k, id, slot) : ex.nodeOut(id, slot);
+  const int P = nd.ir->P;
+  conv_for_each_set(nd.bShared, nd.isTrueStereo, nd.bShared ? 1 : nd.bInCh, nd.bSlots, [&](int xc, const int* slots, int ncol) {
+    const int y0 = (int)yrows.size();
+    for (int j = 0; j < ncol; j++) {   // y rows consecutive per set
+      yrows.push_back(ConvRowIO{nullptr, slotOut[slots[j]]});
+      ovIn.push_back(nd.bOverlap + ((size_t)slots[j] * 2 + nd.bOvCur) * kBlock);
+      ovOut.push_back(nd.bOverlap + ((size_t)slots[j] * 2 + (nd.bOvCur ^ 1)) * kBlock);
+    }
+    if (refOrder || nd.convPath != 3) {
+      sets.push_back(makeSetB(*nd.ir, x0 + xc, y0, slots, ncol));
+      if (refOrder) c.stats.ref_order_rows += ncol;
+    } else {
+      ConvSetC sc{};   // (hs: per FFT length, enqueueTimeFft)
+      sc.x = x0 + xc;
+      sc.y0 = y0;
+      sc.ncol = ncol;
+      sc.P = P;
+      SetTaps tp{nd.ir.get(), {}};
+      std::copy(slots, slots + ncol, tp.slot);
+      setsC[P].push_back(sc);
+      setsCTaps[P].push_back(tp);
+    }
+  });
+  nd.bOvCur ^= 1;
+  flops += 8.0 * P * kBins * (double)nd.bSlots * (double)n;
+}
+
+void PrivateStage::keepHistory(int id, ConvolverS& nd, int x0) {
+  const int h = nd.ir->P - 1;
+  nd.bHistZero = false;
+  if (h == 0) return;
+  // the history of the next chunk: the last h spectra of this node's rows, read where they lie
+  if (nd.bHistPlane == c.bPairWrite) fail(GA_ERR_DEVICE, "internal: convolver history lives in the planes being written");
+  nd.bHistPlane = c.bPairWrite;
+  nd.bHistRow = (int)rowX0 + x0;
+  nd.bHistNx = nd.bShared ? 1 : nd.bInCh;
+  nd.bHistOff = hist + (int)n - h;
+  nd.bHistTxb = txb;
+  c.bResidents[c.bPairWrite].push_back(id);
+}
+
+void PrivateStage::enqueue() {
+  c.bRowX += xrows.size();   // (the next stage's rows lie behind these)
+  c.bRowY += yrows.size();
+  c.bPairCur = c.bPairWrite;
+  ex.flushLevel();   // (materialised inputs)
+  // (the launches below run after this object is gone: they capture what they name, never members)
+  const size_t xo = ex.plan.putv(xrows), yo = ex.plan.putv(yrows), so = ex.plan.putv(sets), ro = ex.plan.putv(restore),
+               oi = ex.plan.putv(ovIn), oo = ex.plan.putv(ovOut);
   const int nx = (int)xrows.size(), ny = (int)yrows.size(), ns_ = (int)sets.size(), nr = (int)restore.size();
-  hipStream_t st = stream;
-  Twiddles tw{w128, w256};
-  const int nn = (int)n;
+  const int nn = (int)n, hist = this->hist;
   const int maxn = std::max(hist, txb - hist - nn);
-  const bool f64 = fft64 || refOrder;   // (formulation R: the reference's FftFlat precision around its own partition sum)
-  ex.plan.add(LK_FFT, [=](uint8_t* base) {
+  const ConvPlanesB plb = this->plb;
+  const bool ref = refOrder;
+  const bool f64 = c.fft64 || ref;   // (formulation R: the reference's FftFlat precision around its own partition sum)
+  const double flops = this->flops;
+  hipStream_t st = c.stream;
+  const Twiddles tw = c.twiddles();
+  Context* cp = &c;
+  ex.plan.add(LK_FFT, [st, ro, nr, maxn, xo, nx, nn, hist, plb, tw, f64](uint8_t* base) {
     launch_hist_copy_b(st, (const HistJobB*)(base + ro), nr, std::max(maxn, 1));
     launch_rfft_fwd_b(st, (const ConvRowIO*)(base + xo), nx, nn, hist, plb, tw, f64);
   });
-  Context* cp = this;
   // (formulation R: 8 separately rounded operations per complex multiply-add -- the planner's count of what the launch executes)
-  if (ns_ > 0 && refOrder)
-    ex.plan.add(LK_MAC, [=](uint8_t* base) {
-      launch_refmac(st, (const ConvSetB*)(base + so), ns_, nn, hist, plb);
-      cp->noteKernel(LK_MAC, "refmac_kernel");
+  if (ns_ > 0)
+    ex.plan.add(LK_MAC, [st, so, ns_, nn, hist, plb, ref, cp](uint8_t* base) {
+      if (ref) launch_refmac(st, (const ConvSetB*)(base + so), ns_, nn, hist, plb);
+      else launch_spectral_mac_b(st, (const ConvSetB*)(base + so), ns_, nn, hist, plb);
+      cp->noteKernel(LK_MAC, ref ? "refmac_kernel" : "spectral_mac_b_kernel");
     }, 0.0, flops);
-  else if (ns_ > 0)
-    ex.plan.add(LK_MAC, [=](uint8_t* base) {
-      launch_spectral_mac_b(st, (const ConvSetB*)(base + so), ns_, nn, hist, plb);
-      cp->noteKernel(LK_MAC, "spectral_mac_b_kernel");
-    }, 0.0, flops);
+  enqueueTimeFft();
+  ex.plan.add(LK_FFT, [st, yo, ny, nn, plb, oi, oo, tw, f64](uint8_t* base) {
+    launch_irfft_ola_b(st, (const ConvRowIO*)(base + yo), ny, nn, plb, (const float* const*)(base + oi), (float* const*)(base + oo), tw, f64);
+  });
+}
+
+void PrivateStage::enqueueTimeFft() {
+  const int nn = (int)n, hist = this->hist;
+  const ConvPlanesB plb = this->plb;
+  hipStream_t st = c.stream;
   for (auto& kv : setsC) {
     const int Pc = kv.first;
     static const char* r16env = expenv("GA_TCONV_RADIX16");   // A/B switches for measurements
     static const char* planenv = expenv("GA_TCONV_MIXED");
-    const bool r16 = r16env ? atoi(r16env) != 0 : useRadix16;
+    const bool r16 = r16env ? atoi(r16env) != 0 : c.useRadix16;
     std::vector<TconvLaunch> tplan;
-    if (debugTconvN2 > 0) {   // tests: a length no kernel exists for must come back as an error code, not abort the host
-      const int Lc = std::max(1, debugTconvN2 - (Pc - 1));
-      tplan.push_back(TconvLaunch{debugTconvN2, 0, (nn + Lc - 1) / Lc});
+    if (c.debugTconvN2 > 0) {   // tests: a length no kernel exists for must come back as an error code, not abort the host
+      const int Lc = std::max(1, c.debugTconvN2 - (Pc - 1));
+      tplan.push_back(TconvLaunch{c.debugTconvN2, 0, (nn + Lc - 1) / Lc});
     } else if (r16 && !(planenv && atoi(planenv) == 0)) {
-      tplan = tconvPlan(nn, Pc);
+      tplan = c.tconvPlan(nn, Pc);
     } else {   // one FFT length for the whole chunk
       const int N2 = tapFftSize(Pc), Lc = N2 - (Pc - 1);
       tplan.push_back(TconvLaunch{N2, 0, (nn + Lc - 1) / Lc});
@@ -1493,38 +1452,50 @@ void Context::planConvolversPrivate(ChunkRun& r, int /*d*/, ConvPlanCtx& k, bool
     for (const TconvLaunch& tl : tplan) {
       std::vector<ConvSetC> sv = kv.second;
       for (size_t i = 0; i < sv.size(); i++) {
-        const float2* hsp = ensureTapSpectra(*taps[i].ir, tl.N2);
+        const float2* hsp = c.ensureTapSpectra(*taps[i].ir, tl.N2);
         for (int j = 0; j < sv[i].ncol; j++) sv[i].hs[j] = hsp + (size_t)taps[i].slot[j] * kBins * tl.N2;
       }
-      size_t co = ex.plan.putv(sv);
+      const size_t co = ex.plan.putv(sv);
       const int nc = (int)sv.size();
       const int N2 = tl.N2, tbase = tl.tbase, nseg = tl.nseg;
-      const float2* twc = r16 ? twiddles16(N2) : twiddlesC(N2);
-      ex.plan.add(LK_MAC, [=](uint8_t* base) {
+      const float2* twc = r16 ? c.twiddles16(N2) : c.twiddlesC(N2);
+      ex.plan.add(LK_MAC, [st, co, nc, nn, hist, plb, N2, twc, nseg, tbase, r16](uint8_t* base) {
         if (r16) launch_tconv16(st, (const ConvSetC*)(base + co), nc, nn, hist, plb, N2, twc, nseg, tbase);
         else launch_tconv(st, (const ConvSetC*)(base + co), nc, nn, hist, plb, N2, twc, nseg);
       });
     }
   }
-  ex.plan.add(LK_FFT, [=](uint8_t* base) {
-    launch_irfft_ola_b(st, (const ConvRowIO*)(base + yo), ny, nn, plb, (const float* const*)(base + oi), (float* const*)(base + oo), tw, f64);
-  });
-  stats.mac_flops_total += flops;
+}
+
+void PrivateStage::account() {
+  c.stats.mac_flops_total += flops;
   // streaming-formulation bytes: per channel-instance per block FDL read + write + input; every distinct
   // IR channel is counted once per block however many nodes share it
-  {
-    std::map<std::pair<IrSpectra*, int>, int> distinct;
-    double bytes = 0;
-    for (int id : bNodes) {
-      ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
-      const int P = nd.ir->P;
-      bytes += ((double)P * kBins * 8.0 + kBins * 8.0 + 512.0) * nd.bSlots * (double)n;
-      for (int sl = 0; sl < nd.bSlots; sl++) distinct[{nd.ir.get(), sl}] = P;
-    }
-    for (auto& kv : distinct) bytes += (double)kv.second * kBins * 8.0 * (double)n;
-    stats.mac_bytes_total += bytes;
+  std::map<std::pair<IrSpectra*, int>, int> distinct;
+  double bytes = 0;
+  for (int id : bNodes) {
+    ConvolverS& nd = rec<ConvolverS>(*c.nodes[id]);
+    const int P = nd.ir->P;
+    bytes += ((double)P * kBins * 8.0 + kBins * 8.0 + 512.0) * nd.bSlots * (double)n;
+    for (int sl = 0; sl < nd.bSlots; sl++) distinct[{nd.ir.get(), sl}] = P;
   }
-  stats.mac_launches += 1;
+  for (auto& kv : distinct) bytes += (double)kv.second * kBins * 8.0 * (double)n;
+  c.stats.mac_bytes_total += bytes;
+  c.stats.mac_launches += 1;
+}
+}  // namespace
+
+static void planPrivateStage(Context& c, ChunkRun& r, ConvPlanCtx& k, const std::vector<int>& bNodes, bool refOrder) {
+  PrivateStage s(c, r, k, bNodes, refOrder);
+  for (int id : bNodes) {   // node by node: the order of slabs, terms and mix jobs decides the plan tables
+    ConvolverS& nd = rec<ConvolverS>(*c.nodes[id]);
+    s.resolveInputs(id, nd);
+    const int x0 = s.buildRows(nd);
+    s.buildSets(id, nd, x0);
+    s.keepHistory(id, nd, x0);
+  }
+  s.enqueue();
+  s.account();
 }
 
 // pass 7 (per convolver depth d): the convolvers whose inputs are complete, once per chunk over all blocks
@@ -1536,9 +1507,8 @@ void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
   // rebuilt in front of the first convolver stage, for every depth at once)
   if (!convMigrations.empty()) planConvMigration(r);
   ConvPlanCtx k;
-  auto& active = k.active;
-  std::vector<int>& bNodes = k.bNodes;  // formulation B / C nodes of this depth
-  std::vector<int>& dNodes = k.dNodes;  // formulation D nodes of this depth
+  std::vector<int> dNodes;        // formulation D nodes of this depth
+  std::vector<int> plain, ref;    // formulation B / C nodes of this depth; those evaluated in the reference's order (formulation R)
   for (int id : r.topo) {
     if (nodes[id]->type != GA_NODE_CONVOLVER) continue;
     ConvolverS& nd = rec<ConvolverS>(*nodes[id]);
@@ -1549,32 +1519,21 @@ void Context::chunkPlanConvolvers(ChunkRun& r, int d) {
       continue;
     }
     if (nd.convPath >= 2) {
-      bNodes.push_back(id);
+      (nd.refOrder ? ref : plain).push_back(id);
       continue;
     }
-    for (int slot = 0; slot < (int)nd.convRows.size(); slot++) active[nd.convRows[slot].group].push_back({id, slot});
+    for (int slot = 0; slot < (int)nd.convRows.size(); slot++) k.active[nd.convRows[slot].group].push_back({id, slot});
   }
-  if (!active.empty()) planConvolversShared(r, d, k);
+  if (!k.active.empty()) planConvolversShared(r, k);
   // ---- formulation D: coarse partitions, consumer sums fused in the frequency domain ----
   if (!dNodes.empty()) planCoarseStage(*this, ex, dNodes, r.n);
   // ---- formulations B / C: nodes with a private impulse response ----
-  // (those that this chunk evaluates in the reference's own order -- formulation R -- in a pass of their own: double-precision
+  // (those that this chunk evaluates in the reference's own order -- formulation R -- in a stage of their own: double-precision
   // transforms and launch_refmac instead of the matrix-core / block-axis-FFT partition sums)
-  if (!bNodes.empty()) {
-    std::vector<int> plain, ref;
-    for (int id : bNodes) (rec<ConvolverS>(*nodes[id]).refOrder ? ref : plain).push_back(id);
-    if (!plain.empty()) {
-      bNodes = plain;
-      planConvolversPrivate(r, d, k, false);
-    }
-    if (!ref.empty()) {
-      bNodes = ref;
-      planConvolversPrivate(r, d, k, true);
-    }
-  }
-  auto& tsTemps = k.tsTemps;
+  if (!plain.empty()) planPrivateStage(*this, r, k, plain, false);
+  if (!ref.empty()) planPrivateStage(*this, r, k, ref, true);
   // true stereo: outL = conv0(L) + conv2(R) ; outR = conv1(L) + conv3(R)  (ConvolverNode.cs:127-144)
-  for (auto& kv : tsTemps) {
+  for (auto& kv : k.tsTemps) {
     hipStream_t st = stream;
     int64_t fr = r.n * kBlock;
     for (int o = 0; o < 2; o++) {

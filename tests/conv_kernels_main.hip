@@ -261,7 +261,7 @@ static void family_a() {
 }
 
 // =====================================================================================================================
-//  b, r, c: the [row][bin][block] layout.  Planes as planConvolversPrivate allocates them: tx = hist + roundup(n, 16) + 16,
+//  b, r, c: the [row][bin][block] layout.  Planes as the planner's PrivateStage lays them out: tx = hist + roundup(n, 16) + 16,
 //  ty = roundup(n, 256); X holds values in [0, hist + n) and NaN behind; sets with x and y0 out of order.
 // =====================================================================================================================
 struct SetSpec { int x, y0, ncol; };

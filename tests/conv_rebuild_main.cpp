@@ -2,7 +2,8 @@
 // The rebuild kernel's loops are replayed on the host over arrays of exactly the sizes the planner allocates (D's input history of
 // coarseP x 8192 samples per channel, the node's [bInCh][129][P-1] stores, the scratch planes [rows][129][tx]); every element carries
 // a tag (channel, bin, block), so a wrong offset shows as a wrong tag or a missing element, and an offset outside an array is the
-// address sanitizer's (tests/test_conv_migrate_host.py builds this file with -fsanitize=address,undefined).
+// address sanitizer's (tests/test_conv_migrate_host.py builds this file with -fsanitize=address,undefined).  The same program checks
+// the set builder that the private-IR convolver stage and the migration share (conv_for_each_set).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -107,7 +108,41 @@ static void run(const std::vector<Node>& nodes) {
   std::printf("checked %zu nodes, %zu jobs, planes %d columns\n", nodes.size(), jobs.size(), tx);
 }
 
+// conv_for_each_set: the planner's sets of one node.  Every slot exactly once, no run longer than a set, a run's x-row is the input
+// channel of each of its slots (0 when the node's one row is shared), runs in increasing x-row, then increasing slot.
+static void check_sets(bool shared, bool trueStereo, int bInCh, int bSlots) {
+  const int nxr = shared ? 1 : bInCh;
+  std::vector<int> emitted(bSlots, 0);
+  int runs = 0, lastXc = -1, lastSlot = -1;
+  conv_for_each_set(shared, trueStereo, nxr, bSlots, [&](int xc, const int* slots, int ncol) {
+    runs++;
+    CHECK(ncol >= 1 && ncol <= kConvSetCols && kConvSetCols == 16, "run of %d slots", ncol);
+    CHECK(xc >= 0 && xc < nxr && xc >= lastXc, "x-row %d after %d of %d", xc, lastXc, nxr);
+    if (xc != lastXc) lastSlot = -1;
+    lastXc = xc;
+    for (int j = 0; j < ncol; j++) {
+      const int slot = slots[j];
+      CHECK(slot >= 0 && slot < bSlots, "slot %d of %d", slot, bSlots);
+      if (slot < 0 || slot >= bSlots) continue;
+      emitted[slot]++;
+      CHECK(slot > lastSlot, "slot %d after %d on x-row %d", slot, lastSlot, xc);
+      lastSlot = slot;
+      CHECK(xc == (shared ? 0 : conv_slot_input(trueStereo, slot)), "slot %d on x-row %d", slot, xc);
+    }
+  });
+  for (int slot = 0; slot < bSlots; slot++)
+    CHECK(emitted[slot] == 1, "shared %d true stereo %d, %d slots: slot %d emitted %d times", (int)shared, (int)trueStereo, bSlots, slot, emitted[slot]);
+  // as few runs as the rule allows: a shared row is cut every 16 slots, a row of its own holds the slots that read it (1, or 2 in true stereo)
+  const int want = shared ? (bSlots + kConvSetCols - 1) / kConvSetCols : nxr;
+  CHECK(runs == want, "shared %d true stereo %d, %d slots: %d runs, expected %d", (int)shared, (int)trueStereo, bSlots, runs, want);
+}
+
 int main() {
+  for (int shared = 0; shared < 2; shared++) {
+    check_sets(shared != 0, true, 2, 4);
+    for (int ch = 1; ch <= 33; ch++) check_sets(shared != 0, false, ch, ch);
+  }
+  std::printf("checked the sets of %d slot layouts\n", 2 * 34);
   for (int P : {1, 2, 71, 1101}) {
     run({Node{P, 1, 1, true, false}});
     run({Node{P, 2, 2, true, false}});     // a mono signal in both channels of a two-channel response: one row

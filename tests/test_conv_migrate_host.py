@@ -1,5 +1,6 @@
-"""Option "conv_migrate" (DESIGN.md 2b), the parts that need no GPU: the surface, the index arithmetic of the rebuild kernel (a
-stand-alone program under the address and undefined-behaviour sanitizers), and -- on the oracle -- that every edit session of
+"""Option "conv_migrate" (DESIGN.md 2b), the parts that need no GPU: the surface, the index arithmetic of the rebuild kernel and the
+set builder it shares with the private-IR convolver stage (a stand-alone program under the address and undefined-behaviour
+sanitizers), and -- on the oracle -- that every edit session of
 tests/_migrate_scenes.py really exercises its sink after the edit.  A scene whose delay time does not move across sample boundaries
 would pass on the device whatever formulation the convolver is on."""
 import os
