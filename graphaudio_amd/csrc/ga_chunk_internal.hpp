@@ -598,7 +598,7 @@ struct Exec {
   std::vector<BiquadSection> bqSecs;
   // cascades split along time (ga_kernels.hpp, BiquadScanJob): pass A / pass B pieces by cascade length, the scans, A^K matrices
   std::vector<BiquadScanJob> bqScans[kMaxBiquadSections + 1];          // by cascade length; all of one level share G and K
-  std::vector<const std::vector<float>*> bqMats[kMaxBiquadSections + 1];   // their A^K -> m_off once the table exists
+  std::vector<const std::vector<double>*> bqMats[kMaxBiquadSections + 1];   // their A^K -> m_off once the table exists
   int bqG = 0;
   int64_t bqK = 0;
   size_t bqZeroFrom = 0;   // Context::bqSplitUsed up to which the pieces' states are already covered by a zeroing launch

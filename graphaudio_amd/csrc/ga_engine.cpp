@@ -1,6 +1,7 @@
 // ga_engine.cpp -- graph state, command queue, device resources.  See ga_engine.hpp for the design overview and
 // ga_chunk.cpp (+ ga_sources / ga_plan_nodes / ga_plan_conv) for the control-plane simulation + chunk executor.
 #include "ga_engine.hpp"
+#include "ga_biquad_split.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -37,62 +38,12 @@ double Context::biquadDeviation(const float* coefs, int nsec) {
   auto& bucket = bqDeviations[h];
   for (auto& e : bucket)
     if (e.first == key) return e.second;
-  double dev = 1.0;
-  // Rounding-noise model (white input): the rounding of section q's  w = x - a1 w1 - a2 w2  is an error of ~ 2^-24 / sqrt(3) |w|
-  // entering at that section's input; it reaches the output through sections q .. nsec-1.  With g_q = energy of the impulse response
-  // input -> w_q and t_q = energy of (input of section q -> output), the noise-to-signal ratio is eps^2 sum_q g_q t_q / energy of the
-  // whole cascade; two evaluations that round differently differ by sqrt(2) of that.
-  {
-    const int N = 1 << 14;
-    std::vector<double> sig(N, 0.0);
-    sig[0] = 1.0;
-    std::vector<std::vector<double>> wq(nsec);
-    for (int q = 0; q < nsec; q++) {   // impulse response of the first q sections + 1/A_q: the W of section q
-      const double b0 = coefs[5 * q], b1 = coefs[5 * q + 1], b2 = coefs[5 * q + 2], a1 = coefs[5 * q + 3], a2 = coefs[5 * q + 4];
-      wq[q].resize(N);
-      double w1 = 0, w2 = 0;
-      for (int i = 0; i < N; i++) {
-        const double w = sig[i] - a1 * w1 - a2 * w2;
-        wq[q][i] = w;
-        sig[i] = b0 * w + b1 * w1 + b2 * w2;
-        w2 = w1;
-        w1 = w;
-      }
-    }
-    double eOut = 0;
-    for (double v : sig) eOut += v * v;
-    double acc = 0;
-    for (int q = 0; q < nsec; q++) {
-      std::vector<double> tail(N, 0.0);
-      tail[0] = 1.0;
-      for (int r = q; r < nsec; r++) {
-        const double b0 = coefs[5 * r], b1 = coefs[5 * r + 1], b2 = coefs[5 * r + 2], a1 = coefs[5 * r + 3], a2 = coefs[5 * r + 4];
-        double w1 = 0, w2 = 0;
-        for (int i = 0; i < N; i++) {
-          const double w = tail[i] - a1 * w1 - a2 * w2;
-          tail[i] = b0 * w + b1 * w1 + b2 * w2;
-          w2 = w1;
-          w1 = w;
-        }
-      }
-      double g = 0, tt = 0;
-      for (int i = 0; i < N; i++) {
-        g += wq[q][i] * wq[q][i];
-        tt += tail[i] * tail[i];
-      }
-      acc += g * tt;
-    }
-    const double eps = 5.96e-8 / 1.7320508;
-    // absolute, for white input of unit variance; x 3: what the measured deviations are above this model (tests/test_gpu_biquad_split.py)
-    (void)eOut;
-    dev = 3.0 * std::sqrt(2.0 * eps * eps * acc);
-  }
+  const double dev = biquad_split_deviation(coefs, nsec);   // (the model: ga_biquad_split.hpp)
   bucket.push_back({std::move(key), dev});
   return dev;
 }
 // A^K of a cascade's state recursion (state = W1, W2 of every section, direct form II as in BiQuadFilterNode.cs:137-141), float64.
 const Context::BqTransition& Context::biquadTransition(const float* coefs, int nsec, int64_t K) {
-  const int D = 2 * nsec;
   std::vector<float> key(coefs, coefs + 5 * nsec);
   key.push_back((float)K);
   uint64_t h = 1469598103934665603ull;
@@ -104,40 +55,9 @@ const Context::BqTransition& Context::biquadTransition(const float* coefs, int n
   auto& bucket = bqTransitions[h];
   for (auto& t : bucket)
     if (t.key == key) return t;
-  // one step from the unit states with zero input gives the columns of A
-  std::vector<double> A((size_t)D * D, 0.0), R((size_t)D * D, 0.0), T((size_t)D * D);
-  for (int j = 0; j < D; j++) {
-    std::vector<double> st(D, 0.0);
-    st[j] = 1.0;
-    double x = 0.0;
-    for (int q = 0; q < nsec; q++) {
-      const double b0 = coefs[5 * q], b1 = coefs[5 * q + 1], b2 = coefs[5 * q + 2], a1 = coefs[5 * q + 3], a2 = coefs[5 * q + 4];
-      const double w1 = st[2 * q], w2 = st[2 * q + 1];
-      const double w = x - a1 * w1 - a2 * w2;
-      x = b0 * w + b1 * w1 + b2 * w2;
-      st[2 * q + 1] = w1;
-      st[2 * q] = w;
-    }
-    for (int r = 0; r < D; r++) A[(size_t)r * D + j] = st[r];
-  }
-  for (int i = 0; i < D; i++) R[(size_t)i * D + i] = 1.0;
-  auto mul = [&](std::vector<double>& out, const std::vector<double>& a, const std::vector<double>& b) {
-    for (int i = 0; i < D; i++)
-      for (int j = 0; j < D; j++) {
-        double acc = 0.0;
-        for (int k = 0; k < D; k++) acc += a[(size_t)i * D + k] * b[(size_t)k * D + j];
-        T[(size_t)i * D + j] = acc;
-      }
-    out = T;
-  };
-  for (int64_t e = K; e > 0; e >>= 1) {
-    if (e & 1) mul(R, R, A);
-    if (e > 1) mul(A, A, A);
-  }
   BqTransition t;
   t.key = std::move(key);
-  t.M.resize((size_t)D * D);
-  for (size_t i = 0; i < t.M.size(); i++) t.M[i] = (float)R[i];
+  t.M = biquad_split_transition(coefs, nsec, K);   // (unit-state construction of A, repeated squaring: ga_biquad_split.hpp)
   bucket.push_back(std::move(t));
   return bucket.back();
 }

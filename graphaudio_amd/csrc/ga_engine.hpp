@@ -888,7 +888,7 @@ struct Context {
   // biquadDeviation: predicted RMS difference between two float32 evaluations of the cascade that round differently (the one walk
   // and the split): rounding noise injected at every section's W, shaped by the rest of the cascade.  Direct form II at low cut-offs is the hard case (large W, cancelling output taps): e.g. the 100 Hz low shelf of
   // config 4 carries ~1e-4 of such noise IN THE REFERENCE'S OWN ARITHMETIC, so no re-association can stay within 1e-5 of it.
-  struct BqTransition { std::vector<float> key; std::vector<float> M; };
+  struct BqTransition { std::vector<float> key; std::vector<double> M; };
   std::unordered_map<uint64_t, std::vector<std::pair<std::vector<float>, double>>> bqDeviations;
   double biquadDeviation(const float* coefs, int nsec);
   std::unordered_map<uint64_t, std::vector<BqTransition>> bqTransitions;

@@ -333,12 +333,12 @@ void launch_biquad(hipStream_t s, const BiquadJob* jobs_dev, int njobs, const Bi
 //   scan     s_0 = the cascade's state ; s_{l+1} = A^K s_l + z_l                                             (per cascade, G - 1 steps)
 //   pass B   every piece is run from its true initial state s_l and writes its outputs                        (G pieces in parallel)
 // Each pass is the per-sample arithmetic of BiQuadFilterNode.cs:137-138 (the lane-per-cascade kernel, biquad_kernel<NSEC, 64>);
-// A^K comes from the host (float64, repeated squaring).  What differs from the one-walk evaluation is the rounding of the
+// A^K comes from the host (float64, repeated squaring: ga_biquad_split.hpp) and is read as float64.  What differs from the one-walk evaluation is the rounding of the
 // pieces' initial states (not bit-exact; tests/test_gpu_biquad_split.py measures it): twice the arithmetic, G times the lanes.
 struct BiquadScanJob {   // one cascade (node chain x channel) cut into G pieces of K frames (the last one shorter)
   const float* in;
   float* out;
-  uint64_t m_off;     // offset of A^K (row-major [2 nsec][2 nsec], float) in the chunk's table
+  uint64_t m_off;     // offset of A^K (row-major [2 nsec][2 nsec], float64, 8-byte aligned) in the chunk's table
   float* scratch;     // [G - 1][nsec][2]: in: z_l of pass A ; out: s_l, where pass B's piece l starts
   int sec0, nsec;     // the cascade's own sections (their `state` is the persistent state: in s_0, out s_{G-1})
   int64_t f0, n;

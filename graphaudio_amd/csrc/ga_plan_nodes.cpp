@@ -1,6 +1,7 @@
 // ga_plan_nodes.cpp -- per-node planning of a chunk: parameter curves, sources, gains, biquads, panners, delays, oscillators; the kept blocks
 // of feedback loops; delay-line commit (see ga_chunk_internal.hpp).
 #include "ga_chunk_internal.hpp"
+#include "ga_biquad_split.hpp"
 
 namespace ga {
 
@@ -818,26 +819,25 @@ void Context::planBiquad(NodePlanCtx& k) {
   }
   // pieces along time (ga_kernels.hpp, BiquadScanJob): as many as keep every lane of the chip busy, each >= 1024 frames;
   // mode 1: only cascades whose float32 rounding noise is so small that a different rounding stays inside the budget
-  int G = 1;
+  BiquadSplitCut cut{1, nf};
   float coefs[5 * kMaxBiquadSections];
   if (biquadTimeSplit && nf >= biquadSplitMinFrames) {
-    const int64_t lanes = 64 * 1024, heads = std::max(levelBqHeads, 1);
-    G = (int)std::max<int64_t>(1, std::min<int64_t>({(lanes + heads - 1) / heads, nf / 1024, 256}));
+    cut = biquad_split_cut(nf, levelBqHeads);   // (the cut rule: ga_biquad_split.hpp)
     int q = 0;
     for (const NodeSeg* cn : chain) {
       coefs[5 * q] = cn->b0; coefs[5 * q + 1] = cn->b1; coefs[5 * q + 2] = cn->b2; coefs[5 * q + 3] = cn->a1; coefs[5 * q + 4] = cn->a2;
       q++;
     }
-    if (biquadTimeSplit == 1 && biquadDeviation(coefs, (int)chain.size()) > biquadSplitMaxDeviation) G = 1;
+    if (biquadTimeSplit == 1 && biquadDeviation(coefs, (int)chain.size()) > biquadSplitMaxDeviation) cut = BiquadSplitCut{1, nf};
   }
-  int64_t K = G > 1 ? ((nf + G - 1) / G + 31) / 32 * 32 : nf;   // (whole cache lines per piece: biquad1_kernel reads 128 bytes per round)
-  if (G > 1) G = (int)((nf + K - 1) / K);
+  int G = cut.G;
+  const int64_t K = cut.K;   // (whole cache lines per piece: biquad1_kernel reads 128 bytes per round)
   if (G > 1 && ex.bqG == 0) {
     ex.bqG = G;
     ex.bqK = K;
   }
   if (G > 1 && (G != ex.bqG || K != ex.bqK)) G = 1;   // (one cut per level: the pieces of a level are expanded by one launch)
-  const std::vector<float>* AK = G > 1 ? &biquadTransition(coefs, (int)chain.size(), K).M : nullptr;
+  const std::vector<double>* AK = G > 1 ? &biquadTransition(coefs, (int)chain.size(), K).M : nullptr;
   // Twin channels: a mono signal in a stereo node arrives as the SAME view on every channel (AudioNodeInput.cs:182-244 copies the
   // mono mix to all of them), and while every channel's state has been the same so far (BiquadS::bqTwinN) the reference computes
   // the same numbers once per channel (BiQuadFilterNode.cs:117-146).  One job then stands for all of them: every channel's output

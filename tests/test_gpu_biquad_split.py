@@ -3,10 +3,13 @@
 A long segment of a cascade is cut into pieces that run in parallel: pass A finds every piece's zero-state end state, a scan
 chains them with A^K (float64, host), pass B runs every piece from its true initial state.  Every pass is the reference's
 per-sample float arithmetic (BiQuadFilterNode.cs:137-138); what differs from the one-walk evaluation (option 0: bit-exact with the
-oracle) is the rounding of the pieces' initial states.  These tests measure that difference -- against the oracle, and against
-scipy.signal.lfilter in float64 (truth): the split path has to be as close to the truth as the reference's own arithmetic is,
-within north_star's 1e-5 RMS -- for the filters of configs 2 and 4 and for the hard cases of a direct-form-II recursion
-(low cut-off, high Q, high-pass: large internal state, cancelling output taps).
+oracle) is the rounding of the pieces' initial states.  These tests measure that difference against the oracle for the filters of
+configs 2 and 4 and for the hard cases of a direct-form-II recursion (low cut-off, high Q, high-pass: large internal state,
+cancelling output taps); their tolerances (1e-3 of the bus, 1e-5) only show a hand-over error of order one.  How close the split
+is to float64 is measured on the scalar model of the path (tests/biquad_split_main.cpp, which the kernels equal bit for bit,
+tests/test_gpu_biquad_split_kernels.py): over the cascades that mode 1 splits it is within 1.09 x the one walk's distance from
+float64 and within 0.87 x the predicted deviation -- with A^K read as float64; rounded to float, as it was, the figures were 2.05 x
+and 1.22 x.  Outside mode 1's threshold (forced mode 2) the prediction is not a bound and was never meant as one.
 """
 import numpy as np
 import pytest
