@@ -1,4 +1,4 @@
-// ga_fft16.hpp -- device-side FFT building blocks shared by ga_kernels.hip (formulation C, block-axis FFT) and ga_coarse.hip
+// ga_fft16.hpp -- device-side FFT building blocks shared by ga_conv.hip (formulation C, block-axis FFT) and ga_coarse.hip
 // (formulation D, coarse partitions): packed-f32 complex arithmetic and the register / LDS hybrid radix-16 transform.
 // Device code only (inline gfx950 assembly); include from .hip translation units.
 #pragma once

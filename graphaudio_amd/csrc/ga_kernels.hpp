@@ -1,4 +1,4 @@
-// ga_kernels.hpp -- launch wrappers of the hand-written gfx950 kernels (ga_kernels.hip; the 256-point real-FFT kernels: ga_rfft.hip).
+// ga_kernels.hpp -- launch wrappers of the hand-written gfx950 kernels (ga_kernels.hip, ga_conv.hip, ga_biquad.hip, ga_spatial.hip, ga_rfft.hip, ga_coarse.hip).
 // Host code (ga_engine.cpp) builds small job tables in pinned memory, uploads them once per chunk and
 // calls these wrappers; every wrapper only enqueues work on `stream` (no allocation, no sync).
 #pragma once

@@ -1,7 +1,7 @@
 // ga_spatial_geom.hpp -- the geometry of one SpatialPannerNode block (SpatialPannerNode.cs:133-204, ApplyDistanceModel :263-284)
 // and the HRIR selection of DESIGN.md section 2e as one set of __host__ __device__ statements: the host evaluates it per block for
 // nodes whose parameters it knows (Context::spatialGeometry, ga_plan_nodes.cpp), spatial_desc_kernel evaluates it for nodes whose
-// parameters are driven by signals (ga_kernels.hip).  Both builds use -ffp-contract=off.  The two differ only in how acos and pow are
+// parameters are driven by signals (ga_spatial.hip).  Both builds use -ffp-contract=off.  The two differ only in how acos and pow are
 // taken (the `Math` policy): the host keeps the C library's float functions, the device rounds once from double -- the project's
 // rule for device transcendentals.  atan2 / asin are double on both sides.
 // Nothing here needs the HIP headers: a plain host compiler builds it too (tests/test_spatial_geometry_host.py).

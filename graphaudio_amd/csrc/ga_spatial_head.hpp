@@ -2,7 +2,7 @@
 // section 2e, "The built-in set"): Brown & Duda's structural model of a rigid spherical head -- per ear a delay that depends on the angle
 // of incidence and a one-pole one-zero head-shadow filter -- sampled on the 72 x 25 grid of section 2e at the context's rate.  The set
 // is this library's own DEFINITION, not a measurement: tests/_spatial_head_model.py restates it in numpy and is what the tests hold
-// both instantiations to.  One set of __host__ __device__ statements: spatial_head_kernel (ga_kernels.hip) evaluates a tap per lane,
+// both instantiations to.  One set of __host__ __device__ statements: spatial_head_kernel (ga_spatial.hip) evaluates a tap per lane,
 // the host evaluates the length, the gain bound and (tests/spatial_head_main.cpp) single taps.  Everything is double and a tap is
 // rounded to float32 once.  Nothing here needs the HIP headers: a plain host compiler builds it too.
 #pragma once

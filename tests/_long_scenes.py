@@ -3,7 +3,7 @@ numpy models against the oracle, the two oracles against each other) and tests/t
 
 Two lengths.  L1 = 2200 blocks with the default options: 34 full groups of 64 blocks and a ragged one of 24, past the grids capped
 at 1024 and at 2048 blocks.  L2 = 4200 blocks with `max_chunk_blocks` = 8192: past the grids capped at 4096 blocks (524,288 frames).
-Every scene's docstring names the kernel (ga_kernels.hip) and the boundary it crosses.  A scene is a _param_scenes.Scene: it is built
+Every scene's docstring names the kernel (ga_kernels.hip, ga_biquad.hip) and the boundary it crosses.  A scene is a _param_scenes.Scene: it is built
 on any context (HIP product, oracle, double-trig oracle)."""
 import functools
 import math

@@ -1,4 +1,4 @@
-// Stand-alone run of the time-split biquad path of graphaudio_amd/csrc/ga_kernels.hip through its launchers alone, on plain device tables,
+// Stand-alone run of the time-split biquad path of graphaudio_amd/csrc/ga_biquad.hip through its launchers alone, on plain device tables,
 // against tests/biquad_split_ref.hpp.  argv[1] picks a family:
 //   scan    launch_biquad_scan alone on integers: biquad_scan_fixed_kernel<1..4> (nsec = k) and biquad_scan_kernel (nsec = 0, and k >= 5)
 //   expand  launch_biquad_split_expand: the passA / passB job tables field by field

@@ -1,4 +1,4 @@
-// Stand-alone run of the fine-partition convolver kernels of graphaudio_amd/csrc/ga_kernels.hip through their launchers alone, against
+// Stand-alone run of the fine-partition convolver kernels of graphaudio_amd/csrc/ga_conv.hip through their launchers alone, against
 // tests/conv_ref.hpp.  argv[1] picks a family:
 //   a     spectral_mac_shared_kernel (formulation A) on integer spectra: bit for bit
 //   b     spectral_mac_b_kernel (B) on integer spectra: bit for bit

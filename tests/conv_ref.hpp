@@ -1,4 +1,4 @@
-// conv_ref.hpp -- a plain statement of what the fine-partition convolver kernels of graphaudio_amd/csrc/ga_kernels.hip compute
+// conv_ref.hpp -- a plain statement of what the fine-partition convolver kernels of graphaudio_amd/csrc/ga_conv.hip compute
 // (formulations A, B, R and C, the taps' spectra and the five plane utilities), written from the contracts in ga_kernels.hpp, not from
 // the kernels' index arithmetic.  C++17, no HIP, nothing from csrc but the bin count restated below (tests/conv_kernels_main.hip asserts
 // it agrees).  Used by tests/conv_ref_main.cpp (the reference against itself, under the sanitizers) and tests/conv_kernels_main.hip

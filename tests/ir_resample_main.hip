@@ -1,5 +1,5 @@
 // Stand-alone device check of graphaudio_amd/csrc/ga_ir_resample.hpp (option "ir_resample"): ir_resample_kernel, run through the
-// launcher the library uses (launch_ir_resample of ga_kernels.hip), against the host evaluating the same header on the same rows and
+// launcher the library uses (launch_ir_resample of ga_conv.hip), against the host evaluating the same header on the same rows and
 // the same table.  The condition is identical bit patterns (tests/test_gpu_ir_resample_kernel.py).
 //
 // Per rate pair (44.1 -> 48, 48 -> 44.1, 96 -> 48, 8 -> 48, 192 -> 8 kHz): N = 1, 2, 2W-1, 2W, 2W+1; N chosen so that M is tile - 1,

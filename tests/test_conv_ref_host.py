@@ -1,5 +1,5 @@
 """tests/conv_ref.hpp, the reference of the fine-partition convolver kernels (formulations A, B, R and C, the taps' spectra and the plane
-utilities of graphaudio_amd/csrc/ga_kernels.hip), against itself.
+utilities of graphaudio_amd/csrc/ga_conv.hip), against itself.
 
 tests/conv_ref_main.cpp is built with g++ under the address and undefined-behaviour sanitizers, with -ffp-contract=off and no
 fast-math or flush-to-zero flag, and run directly (no GPU, no HIP): the fast float64 transform against a naive O(N^2) DFT, the float64

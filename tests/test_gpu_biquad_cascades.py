@@ -4,7 +4,7 @@ The oracle restates BiQuadFilterNode.cs:137-138 per sample (tests/test_oracle_gr
 scipy.signal.lfilter in float64); the one-walk evaluation on the device is the same float arithmetic operation by operation, so the
 condition is np.array_equal.  Only the time split (case 6) rounds differently and is measured instead.
 
-Launch rules the cases are derived from (ga_kernels.hip; a change there has to be restated here):
+Launch rules the cases are derived from (ga_biquad.hip; a change there has to be restated here):
 
   cascades of 2..8 sections -> biquad_pipe_kernel<NSEC>                                 launch_biquad, `if (pipe && nsec >= 2)`
       GPR  = 16 // NSEC                 cascades per 16-lane row                       biquad_pipe_kernel, `constexpr int GPR`

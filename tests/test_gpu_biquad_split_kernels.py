@@ -1,4 +1,4 @@
-"""The time-split biquad path of graphaudio_amd/csrc/ga_kernels.hip alone -- biquad_split_expand_kernel, the state-only and the full
+"""The time-split biquad path of graphaudio_amd/csrc/ga_biquad.hip alone -- biquad_split_expand_kernel, the state-only and the full
 lane kernels behind launch_biquad_lanes, biquad_scan_fixed_kernel<1..4> and biquad_scan_kernel -- against tests/biquad_split_ref.hpp,
 bit for bit.
 

@@ -1,4 +1,4 @@
-"""The fine-partition convolver kernels of graphaudio_amd/csrc/ga_kernels.hip alone -- formulations A, B, R and C, the taps' spectra
+"""The fine-partition convolver kernels of graphaudio_amd/csrc/ga_conv.hip alone -- formulations A, B, R and C, the taps' spectra
 and the five plane utilities -- against the reference tests/conv_ref.hpp.
 
 tests/conv_kernels_main.hip drives them through their launchers on plain device tables, one family per process run, and prints one

@@ -1,5 +1,5 @@
 """The node kernels at production chunk lengths: every scene of tests/_long_scenes.py rendered on the device as ONE chunk of 2200
-blocks (default options) or 4200 blocks (`max_chunk_blocks` = 8192), so that the launch shapes of ga_kernels.hip cross the boundaries
+blocks (default options) or 4200 blocks (`max_chunk_blocks` = 8192), so that the launch shapes of ga_kernels.hip and ga_biquad.hip cross the boundaries
 short renders never reach: the serial carry across groups of 64 blocks and their ragged last group, workgroups of 64 blocks from
 `bl0`, and the grids capped at 1024, 2048 and 4096 blocks, which stride from there on.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where the cycles of biquad_pipe_kernel go INSIDE the engine (config 4 at full size): a library built with
-`VARIANT_KERNELS=1 tools/build_variant.sh bqprobe -DGA_BQ_PROBE` sums s_memtime ticks per phase (ga_kernels.hip, GA_BQ_PROBE)."""
+`VARIANT_KERNELS=1 tools/build_variant.sh bqprobe -DGA_BQ_PROBE` sums s_memtime ticks per phase (ga_biquad.hip, GA_BQ_PROBE)."""
 import ctypes, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -7,10 +7,13 @@ cd "$(dirname "$0")/../graphaudio_amd/csrc"
 mkdir -p ../../tools/variants /tmp/variant_$name
 F="-DGA_EXPERIMENTS --offload-arch=gfx950 -O3 -g1 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function"
 /opt/rocm/bin/hipcc $F "$@" -c ga_coarse.hip -o /tmp/variant_$name/ga_coarse.o &
-KO=ga_kernels.o
-if [ -n "$VARIANT_KERNELS" ]; then   # (ga_kernels.hip too: its experiment switches, e.g. GA_BQ_JPW; minutes of compile time)
-  KO=/tmp/variant_$name/ga_kernels.o
-  /opt/rocm/bin/hipcc $F "$@" -c ga_kernels.hip -o $KO &
+KO="ga_kernels.o ga_conv.o ga_biquad.o ga_spatial.o"
+if [ -n "$VARIANT_KERNELS" ]; then   # (the four other kernel files too: their experiment switches, e.g. GA_BQ_JPW in ga_biquad.hip)
+  KO=
+  for f in ga_kernels ga_conv ga_biquad ga_spatial; do
+    /opt/rocm/bin/hipcc $F "$@" -c $f.hip -o /tmp/variant_$name/$f.o &
+    KO="$KO /tmp/variant_$name/$f.o"
+  done
 fi
 for f in ga_topology ga_chunk ga_sources ga_plan_nodes ga_plan_conv; do   # (the planner shares the job-size constants and the experiment switches)
   /opt/rocm/bin/hipcc $F "$@" -x hip -c $f.cpp -o /tmp/variant_$name/$f.o &

@@ -1,7 +1,7 @@
 """tools/fuzz_libm_class.py SEED...: is a session's deviation from the oracle the last bit of cosf / sinf / powf?
 
 The reference's MathF.Cos / Sin / Pow are the C runtime's single-precision functions (the oracle: glibc's); the device evaluates the
-coefficients of AUTOMATED biquads and the gains of panners in double and rounds once (ga_kernels.hip, biquad_update_coefficients) --
+coefficients of AUTOMATED biquads and the gains of panners in double and rounds once (ga_biquad.hip, biquad_update_coefficients; ga_kernels.hip, pan_gains) --
 the same float except where the true value lies within ~1e-9 of a rounding boundary.  A graph that quantises such a value (a delay
 time in whole samples, `pan != lastPan`) turns that last bit into a block that sounds different.  This tool renders the session
 three times: oracle, device, and the double-trig oracle (oracle/libga_oracle_dtrig.so, built by `make -C oracle` with

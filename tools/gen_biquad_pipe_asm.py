@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Writes graphaudio_amd/csrc/ga_biquad_pipe_asm.inc: the steady-state walk of biquad_pipe_kernel (ga_kernels.hip) as ONE inline
+"""Writes graphaudio_amd/csrc/ga_biquad_pipe_asm.inc: the steady-state walk of biquad_pipe_kernel (ga_biquad.hip) as ONE inline
 assembly statement -- a run of `nb` batches of 16 pipeline steps, 8 vector instructions per step, fixed registers.
 
 Why assembly: a wave that is alone on its SIMD pays ~5 cycles per instruction whatever the instruction is (measured,

@@ -3,7 +3,7 @@
 // (A bench tool, kernel against kernel.  The suite holds these shapes -- every cascade length, every wave packing, ragged and
 // unaligned rows -- against the CPU oracle: tests/test_gpu_biquad_cascades.py.)
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I graphaudio_amd/csrc tools/micro/bq_pipe_check.hip -o tools/micro/bq_pipe_check
-#include "../../graphaudio_amd/csrc/ga_kernels.hip"
+#include "../../graphaudio_amd/csrc/ga_biquad.hip"
 #include <vector>
 #include <cmath>
 #include <cstring>

@@ -4,7 +4,7 @@
 //   tools/micro/bq_pipe_probe <cascades> <frames> <cascades per wave> [row stride in rows: 3 = the rows of a cascade's input and
 //   output two rows apart, as where the engine's slab allocator interleaves them with other nodes' rows]
 #define GA_BQ_PROBE 1
-#include "../../graphaudio_amd/csrc/ga_kernels.hip"
+#include "../../graphaudio_amd/csrc/ga_biquad.hip"
 #include <vector>
 #include <cmath>
 #include <cstring>
