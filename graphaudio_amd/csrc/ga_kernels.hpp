@@ -55,6 +55,20 @@ struct Twiddles {
   const double2* w256;
 };
 
+// Layout facts of the 256-point transforms (launch_rfft_fwd, launch_irfft_ola here; launch_rfft_fwd_b, launch_conv_rebuild and
+// launch_irfft_ola_b below).  The kernels move spectra in 16-byte pieces and take these for granted; the planner provides them and
+// tests/rfft_ref_kernels_main.hip checks them before every launch:
+//   A   rp is a multiple of 128 and holds whole tiles of 32 rows: roundup(nrows, 32) <= rp.  The forward kernel writes all 32 rows of a
+//       tile (rows from nrows on as silence: zeros) into columns [hist, hist + nblocks) -- any hist >= 0, tx >= hist + nblocks.  The inverse
+//       kernel loads all 32 rows of a tile of blocks [0, nblocks) (what rows from nrows on hold never reaches a stored sample) and reads
+//       overlap_in / writes overlap_out for rows < nrows only.
+//   B   tx, ty and hist are multiples of 4 and the planes' base addresses are 16-byte aligned.  The forward kernel writes whole quads:
+//       columns [hist, hist + roundup(nblocks, 4)), the ones from hist + nblocks on as zeros, so tx >= hist + roundup(nblocks, 4).  The
+//       inverse kernel loads whole quads: columns [0, roundup(nblocks, 4)), so ty >= roundup(nblocks, 4); what the columns from nblocks
+//       on hold never reaches a stored sample.  launch_conv_rebuild stores single floats: column hist - (P - 1) + j for block j < P only.
+//   in  a row's input is exactly nblocks x 128 floats, read as 8-byte pairs at any 4-byte alignment; nothing behind it is read.
+//   out rows are 16-byte aligned (the B inverse kernel stores 16-byte pieces, the A inverse kernel 8-byte pairs); a row without `out`
+//       still gets its overlap_out.
 // forward rfft256 of every (row, block): X planes rows [hist + t] for t in [0, nblocks)
 void launch_rfft_fwd(hipStream_t s, const ConvRowIO* rows_dev, int nrows, int nblocks, int hist, ConvPlanes pl, Twiddles tw);
 // shared-IR spectral multiply-accumulate (PartitionedConvolver.cs:154-223 over all blocks of the chunk at once)
