@@ -19,7 +19,11 @@ internal static unsafe partial class GraphAudioHip
                      GA_ERR_OUT_OF_MEMORY = -8, GA_ERR_NO_DEVICE = -9;
     public const int NodeBufferSource = 1, NodeGain = 2, NodeBiquad = 3, NodeConvolver = 4;
     public const int NodeChannelSplitter = 5, NodeChannelMerger = 6, NodeConstantSource = 7, NodeStereoPanner = 8,
-                     NodeOscillator = 9, NodeDelay = 10, NodeStreamSource = 11, NodeSpatialPanner = 12;
+                     NodeOscillator = 9, NodeDelay = 10, NodeStreamSource = 11, NodeSpatialPanner = 12,
+                     NodeDynamicsCompressor = 13;
+    // GA_NODE_DYNAMICS_COMPRESSOR parameter indices (GA_COMPRESSOR_*)
+    public const int CompressorThreshold = 0, CompressorKnee = 1, CompressorRatio = 2, CompressorAttack = 3, CompressorRelease = 4,
+                     CompressorMakeupGain = 5;
     // GA_NODE_SPATIAL_PANNER pseudo-parameters (ga_param_set_value / ga_param_get_value only)
     public const int SpatialDistanceModel = 17, SpatialHrirAzimuths = 18;
 

@@ -13,7 +13,7 @@
 // Destination (same traversal as GetAllNodes, AudioContextBase.cs:191-218), (3) replays what changed since the last
 // call through the flat C ABI -- O(graph delta) calls -- and (4) makes ONE ga_render call for the whole frame range.
 // Unsupported node types (anything but AudioBufferSourceNode, GainNode, BiQuadFilterNode, ConvolverNode, ChannelSplitterNode,
-// ChannelMergerNode, ConstantSourceNode, StereoPannerNode, OscillatorNode, DelayNode, Hip.SpatialPannerNode and the
+// ChannelMergerNode, ConstantSourceNode, StereoPannerNode, OscillatorNode, DelayNode, Hip.SpatialPannerNode, Hip.DynamicsCompressorNode and the
 // destination) make EnsureSynced throw NotSupportedException; callers fall back to the stock CPU context.
 // NOTE: not compiled in this repository's build image (no .NET); reviewed by reading.  The Python host in
 // graphaudio_amd/core.py drives the very same C ABI calls in the same order and IS tested.
@@ -271,6 +271,7 @@ public sealed unsafe class HipOfflineAudioContext : AudioContextBase
             OscillatorNode => (GraphAudioHip.NodeOscillator, 0.0),
             DelayNode d => (GraphAudioHip.NodeDelay, d.MaxDelayTimeInternal),
             SpatialPannerNode => (GraphAudioHip.NodeSpatialPanner, 0.0),
+            DynamicsCompressorNode => (GraphAudioHip.NodeDynamicsCompressor, 0.0),
             _ => throw new NotSupportedException($"{node.GetType().Name} is not on the HIP render path; use OfflineAudioContext"),
         };
         GraphAudioHip.Check(_native, GraphAudioHip.ga_node_create_ex(_native, type, arg, out int id));
@@ -473,4 +474,34 @@ public sealed class SpatialPannerNode : AudioNode
     }
 
     protected override void Process() => throw new NotSupportedException("SpatialPannerNode (HIP) is rendered by HipOfflineAudioContext only");
+}
+
+/// <summary>
+/// A bus compressor / limiter rendered by HipOfflineAudioContext (native node type 13): the library's own definition
+/// (include/graphaudio_hip.h, DESIGN.md section 2g) -- GraphAudio.Core has no such node, so the stock CPU context cannot render it.
+/// One input (2 channels, clamped-max, speakers), one output with the input's channel count; all parameters k-rate.  Connecting a
+/// signal to a parameter makes the native library answer GA_ERR_UNSUPPORTED (NotSupportedException from EnsureSynced).
+/// </summary>
+public sealed class DynamicsCompressorNode : AudioNode
+{
+    // (name, default, min, max) in the native parameter order
+    private static readonly (string name, float def, float min, float max)[] Table =
+    {
+        ("threshold", -24f, -100f, 0f), ("knee", 30f, 0f, 40f), ("ratio", 12f, 1f, 20f),
+        ("attack", 0.003f, 0f, 1f), ("release", 0.25f, 0f, 1f), ("makeupGain", 0f, -40f, 40f),
+    };
+    private readonly AudioParam[] _p = new AudioParam[Table.Length];
+
+    public AudioParam Threshold => _p[0]; public AudioParam Knee => _p[1]; public AudioParam Ratio => _p[2];
+    public AudioParam Attack => _p[3]; public AudioParam Release => _p[4]; public AudioParam MakeupGain => _p[5];
+
+    public DynamicsCompressorNode(HipOfflineAudioContext context) : base(context, inputCount: 1, outputCount: 1, "DynamicsCompressor")
+    {
+        for (int i = 0; i < Table.Length; i++) _p[i] = CreateAudioParam(Table[i].name, Table[i].def, Table[i].min, Table[i].max, AutomationRate.KRate);
+        Inputs[0].SetChannelCount(2);
+        Inputs[0].SetChannelCountMode(ChannelCountMode.ClampedMax);
+        Inputs[0].SetChannelInterpretation(ChannelInterpretation.Speakers);
+    }
+
+    protected override void Process() => throw new NotSupportedException("DynamicsCompressorNode (HIP) is rendered by HipOfflineAudioContext only");
 }

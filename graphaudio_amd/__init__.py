@@ -10,6 +10,7 @@ from .core import (AudioStreamSourceNode, StreamState, AudioBufferSourceNode, Au
                    AudioParam, AutomationRate, BiQuadFilterNode, ChannelCountMode, ChannelInterpretation,
                    ChannelMergerNode, ChannelSplitterNode, ConstantSourceNode, ConvolverNode, DelayNode, FilterType,
                    FramesPerBlock, GainNode, HipOfflineAudioContext, OfflineAudioContext, OscillatorNode,
-                   OscillatorType, PlayableAudioBuffer, StereoPannerNode, DistanceModelType, HrirSet, SpatialPannerNode)
+                   OscillatorType, PlayableAudioBuffer, StereoPannerNode, DistanceModelType, HrirSet, SpatialPannerNode,
+                   DynamicsCompressorNode)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

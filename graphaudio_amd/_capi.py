@@ -115,6 +115,16 @@ SPATIAL_DISTANCE_MODEL = 17
 SPATIAL_HRIR_AZIMUTHS = 18
 LISTENER_OPTIONS = tuple(f"listener_{v}_{a}" for v in ("origin", "right", "up", "ahead") for a in "xyz")
 
+# GA_NODE_DYNAMICS_COMPRESSOR and its parameter indices (include/graphaudio_hip.h; the node goes through node_create and param_*)
+NODE_DYNAMICS_COMPRESSOR = 13
+COMPRESSOR_THRESHOLD = 0
+COMPRESSOR_KNEE = 1
+COMPRESSOR_RATIO = 2
+COMPRESSOR_ATTACK = 3
+COMPRESSOR_RELEASE = 4
+COMPRESSOR_MAKEUP_GAIN = 5
+COMPRESSOR_PARAM_COUNT = 6
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 

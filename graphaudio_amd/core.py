@@ -529,6 +529,23 @@ class StereoPannerNode(AudioNode):  # Nodes/StereoPannerNode.cs:9-163
         self.Pan = self._param("pan", 0.0, -1.0, 1.0, AutomationRate.ARate)
 
 
+class DynamicsCompressorNode(AudioNode):
+    """A bus compressor / limiter: this library's own definition (include/graphaudio_hip.h) -- the reference
+    has no such node, and the CPU oracle refuses to create one (ArgumentException).  One input (2 channels, clamped-max, speakers),
+    one output with the input's channel count; the channels share one gain (the level is the larger magnitude).  All six parameters
+    are k-rate and take values and timelines; connecting a signal to one raises NotSupportedException.  No look-ahead, no adaptive
+    release, no automatic makeup gain, no ``reduction`` read-back."""
+    _node_type = _capi.NODE_DYNAMICS_COMPRESSOR
+    # (name, default, min, max) in the native parameter order; dB, dB, ratio, s, s, dB
+    PARAMS = (("threshold", -24.0, -100.0, 0.0), ("knee", 30.0, 0.0, 40.0), ("ratio", 12.0, 1.0, 20.0),
+              ("attack", 0.003, 0.0, 1.0), ("release", 0.25, 0.0, 1.0), ("makeupGain", 0.0, -40.0, 40.0))
+
+    def __init__(self, context):
+        super().__init__(context, "DynamicsCompressor")
+        for name, default, mn, mx in self.PARAMS:   # Threshold, Knee, Ratio, Attack, Release, MakeupGain
+            setattr(self, name[0].upper() + name[1:], self._param(name, default, mn, mx, AutomationRate.KRate))
+
+
 class DistanceModelType(enum.IntEnum):  # SpatialPannerNode.cs:42-47
     Linear = 0
     Inverse = 1

@@ -569,6 +569,11 @@ int ga_node_connect_param(ga_context* ctx, int src, int dst_node, int dst_param,
     NodeS* s = c.node(src);
     c.param(dst_node, dst_param);
     if (output_index < 0 || output_index >= (int)s->outputs.size()) fail(GA_ERR_OUT_OF_RANGE, "outputIndex");
+    if (c.node(dst_node)->type == GA_NODE_DYNAMICS_COMPRESSOR) {   // (graphaudio_hip.h: the six parameters take values and timelines only)
+      static const char* const names[GA_COMPRESSOR_PARAM_COUNT] = {"threshold", "knee", "ratio", "attack", "release", "makeupGain"};
+      fail(GA_ERR_UNSUPPORTED, std::string("DynamicsCompressorNode: a signal connected to parameter ") + names[dst_param] +
+                                   " is not on the device path (the node's parameters take values and timelines)");
+    }
     Context* cp = &c;
     c.executeOrPost([cp, src, dst_node, dst_param, output_index]() { cp->connectTo(src, output_index, InRef{dst_node, -1 - dst_param}); });
   });

@@ -406,6 +406,12 @@ struct Sim {
         // node is planned (Context::planSpatialPanner), from the parameters' timelines and the descriptor of the previous block
         break;
       }
+      case GA_NODE_DYNAMICS_COMPRESSOR:  // graphaudio_hip.h: the output is silent exactly when the input is, and zero when it is (0 * g = 0)
+        n_.outputs[0].bufCh = ns.ins[0].bufCh;
+        n_.outputs[0].silent = ns.ins[0].silent;
+        n_.outputs[0].zero = ns.ins[0].zero;
+        // (the per-block parameters do not cut segments: the node's table is made where it is planned, Context::planCompressor)
+        break;
       case GA_NODE_DELAY: {  // DelayNode.cs:43-100
         DelayS& dl = rec<DelayS>(n_);
         const InSeg& in = ns.ins[0];
@@ -623,6 +629,7 @@ struct Exec {
   double spatialFma = 0;                   // fused multiply-adds of the level's workgroups
   std::vector<SpatialDescJob> spatialDescJobs;   // signal-driven spatial nodes of the level being planned (spatial_desc_kernel)
   std::vector<SpatialDirectJob> spatialDirectJobs;   // option "spatial_occlusion": the level's nodes with an active block in the segment (spatial_direct_kernel)
+  std::vector<CompressorJob> compressorJobs;   // the level's DynamicsCompressorNodes over the segment being planned (compressor_kernel)
   std::vector<ParamModJob> pmodJobs;
   std::vector<ResampleBlock> traj;  // per-chunk trajectory table (all rates + custom tail blocks)
   bool mixAligned = true;
@@ -961,6 +968,9 @@ struct Exec {
       launch_spatial_panner(st, t, nw, (const SpatialJob*)(base + spatialJobsOff), base);
     }, 0.0, 2.0 * spatialFma);
     spatialFma = 0;
+    // the level's compressors: one wavefront per node (the segments of a chunk are launched in order, so yL passes from one to the next)
+    if (!compressorJobs.empty()) c.noteKernel(LK_OTHER, "compressor_kernel");
+    flush(compressorJobs, LK_OTHER, nullptr, [=](const CompressorJob* t, int nj, int64_t, uint8_t* base) { launch_compressor(st, t, nj, base); });
     // after the mix jobs of this level, which append the input to the delay lines
     flush(delayJobs, LK_OTHER, &DelayJob::n, [=](const DelayJob* t, int nj, int64_t mx, uint8_t*) { launch_delay(st, t, nj, mx); });
     flush(gainJobs, LK_OTHER, &GainJob::n, [=](const GainJob* t, int nj, int64_t mx, uint8_t*) { launch_gain(st, t, nj, mx); });

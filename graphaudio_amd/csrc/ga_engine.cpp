@@ -175,6 +175,7 @@ Context::~Context() {
         drop({sp.spHist[0], sp.spHist[1], sp.spCarry[0], sp.spCarry[1], sp.spDirect});
         break;
       }
+      case GA_NODE_DYNAMICS_COMPRESSOR: drop({rec<CompressorS>(*np).cmpState}); break;
       default: break;
     }
   }
@@ -562,6 +563,15 @@ void Context::doDispose(int id) {
     sp.spOnDevice = sp.spEqOnDevice = false;
     sp.irBuf = -1;
     sp.hrirRequested = -1;
+  }
+  if (n.type == GA_NODE_DYNAMICS_COMPRESSOR) {   // the level detector's state goes with the node
+    CompressorS& cm = rec<CompressorS>(n);
+    if (cm.cmpState) {
+      syncStreamQuiet();
+      dfree(cm.cmpState, sizeof(double));
+      cm.cmpState = nullptr;
+    }
+    cm.cmpMoved = false;
   }
   if (n.type == GA_NODE_BUFFER_SOURCE) rec<BufferSourceS>(n).bufId = -1;  // AudioBufferSourceNode.cs:412
   if (n.type == GA_NODE_STREAM_SOURCE) {   // AudioStreamSourceNodeBase.cs:315-327

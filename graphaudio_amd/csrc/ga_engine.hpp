@@ -430,6 +430,18 @@ struct SpatialPannerS : NodeS, FedState, IrRef {
   int spJob = -1;
 };
 
+// DynamicsCompressorNode (include/graphaudio_hip.h): the level detector's yL is one double on the device,
+// allocated (as 0) when the node is first planned and freed when it is disposed; it carries across chunks and render calls.
+struct CompressorS : NodeS {
+  static constexpr int kType = GA_NODE_DYNAMICS_COMPRESSOR;
+  double* cmpState = nullptr;        // device: yL
+  bool cmpMoved = false;             // a non-silent block has reached the node: yL may be non-zero (until then silent blocks need no job)
+  // per chunk (valid while cmpSeq == Context::chunkSeq and cmpExec is the chunk's executor): the node's per-block parameter table
+  uint64_t cmpSeq = ~0ull;
+  const void* cmpExec = nullptr;
+  size_t cmpParOff = 0;
+};
+
 // The typed record of a node.  The check is always on: `type` sits in the record's first cache line, and a planner or an API call
 // that reaches for another type's state fails here instead of reading a neighbour's bytes.
 // (the failure is one out-of-line call, so that a check costs its caller a compare and a branch and no string code)
@@ -562,6 +574,17 @@ inline std::unique_ptr<NodeS> makeNode(int type, int id, double arg, int sampleR
       for (int i = 0; i < 4; i++) n->params.push_back(makeParam(0.f, 0.f, 1.f, false));      // occlusion, transmissionLow/Mid/High
       break;
     }
+    case GA_NODE_DYNAMICS_COMPRESSOR:   // this library's own definition (graphaudio_hip.h): all k-rate
+      n = std::make_unique<CompressorS>();
+      shape(1, 1, GA_COMPRESSOR_PARAM_COUNT);
+      clampedStereoInput();
+      n->params.push_back(makeParam(-24.f, -100.f, 0.f, false));   // threshold, dB
+      n->params.push_back(makeParam(30.f, 0.f, 40.f, false));      // knee, dB
+      n->params.push_back(makeParam(12.f, 1.f, 20.f, false));      // ratio
+      n->params.push_back(makeParam(0.003f, 0.f, 1.f, false));     // attack, s
+      n->params.push_back(makeParam(0.25f, 0.f, 1.f, false));      // release, s
+      n->params.push_back(makeParam(0.f, -40.f, 40.f, false));     // makeupGain, dB
+      break;
     default: fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");
   }
   n->id = id;
@@ -1100,6 +1123,7 @@ struct Context {
   void planDelay(NodePlanCtx& k);
   void planStereoPanner(NodePlanCtx& k);
   void planSpatialPanner(NodePlanCtx& k);
+  void planCompressor(NodePlanCtx& k);
   void planSpatialDirect(Exec& ex, size_t si, const Segment& sg, const NodeSeg& ns, SpatialPannerS& nd, const SpatialEq& prev, int open, bool prevValid);
   void spatialEqTable(Exec& ex, SpatialPannerS& nd, int64_t n);
   // SpatialPannerNode: geometry of one block (SpatialPannerNode.cs:133-204,263-284 in float32) -> HRIR indices, weights, g, beta

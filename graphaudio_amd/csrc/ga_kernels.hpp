@@ -3,6 +3,7 @@
 // calls these wrappers; every wrapper only enqueues work on `stream` (no allocation, no sync).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -810,6 +811,48 @@ struct SpatialDirectJob {   // one node over one segment of a chunk (every block
   int b0, nb;             // blocks [b0, b0 + nb) of the chunk
 };
 void launch_spatial_direct(hipStream_t s, const SpatialDirectJob* jobs_dev, int njobs, int max_nb, const uint8_t* tables_dev, const SpatialBands& bands);
+
+// DynamicsCompressorNode (this library's own definition: include/graphaudio_hip.h; ga_dynamics.hip).  The level
+// detector's state yL is one double per node and the time axis is serial, so a job is one node walked by ONE wavefront: per tile of 64
+// frames every lane computes xL of its own frame, the 64-step recurrence is walked wave-uniformly (xL[i] by lane broadcast, every lane
+// keeps the yL of its own frame), then every lane computes g and writes its outputs.  A job covers consecutive segments of a chunk
+// (the input's channel count and views change between segments); the link is the max over the channels present.
+struct CompressorParams {   // one per block of the chunk, float64: the clamped float values widened, and what follows from them
+  double T, W, R, M;        // threshold dB, knee dB, ratio, makeup dB
+  double aA, aR;            // attack > 0 ? exp(-1 / (attack * fs)) : 0 ; the same from release
+  double quiet;             // a level a (linear) with (double)a < quiet has 2 (xG - T) < -W, i.e. xL = +0, whatever log10 rounds to: pow(10, (T - W/2) / 20) (1 - 2^-30)
+  double pad_;
+};
+// the table entry of a block from the six parameter values in GA_COMPRESSOR_* order, already clamped to their ranges (host only)
+inline CompressorParams compressor_params(const float v[6], double fs) {
+  CompressorParams o{};
+  o.T = (double)v[0];
+  o.W = (double)v[1];
+  o.R = (double)v[2];
+  o.M = (double)v[5];
+  const double at = (double)v[3], rl = (double)v[4];
+  o.aA = at > 0.0 ? exp(-1.0 / (at * fs)) : 0.0;
+  o.aR = rl > 0.0 ? exp(-1.0 / (rl * fs)) : 0.0;
+  // below `quiet`, 2 (xG - T) < -W holds by 8e-9 dB, a million times what log10 and the subtraction can be off by: xL is exactly +0
+  // there and the kernel does not take the logarithm (a NaN parameter makes this NaN: no level is below it, nothing is skipped)
+  o.quiet = pow(10.0, (o.T - o.W / 2.0) / 20.0) * (1.0 - 1.0 / 1073741824.0);
+  return o;
+}
+struct CompressorSeg {      // one segment of the job: blocks [b0, b0 + nb) of the chunk
+  const float* in[2];       // chunk-frame indexed input views; nch = 0 (silent input): not read
+  float* out[2];            // chunk-frame indexed outputs; nch = 0: not written
+  int b0, nb;
+  int nch;                  // 0 (silent: only yL moves, xL = 0), 1 or 2
+  int pad_;
+};
+struct CompressorJob {
+  uint64_t seg_off;         // CompressorSeg[nseg] in the chunk's tables
+  uint64_t par_off;         // CompressorParams in the chunk's tables: entry b * par_stride belongs to chunk block b
+  double* state;            // yL: read at the start, written at the end
+  int nseg;
+  int par_stride;           // 1: one entry per block of the chunk ; 0: one entry for all (no parameter on a timeline)
+};
+void launch_compressor(hipStream_t s, const CompressorJob* jobs_dev, int njobs, const uint8_t* tables_dev);
 
 // ProcessBlockInterleaved (AudioContextBase.cs:125-155): dst[(f0 + i) * channels + ch] = ch < used ? src[ch][f0 + i] : 0
 struct InterleaveSrc {

@@ -529,6 +529,62 @@ void Context::planSpatialPanner(NodePlanCtx& k) {
   if (sg.b1 == n && !tailDone) ex.spatialWorks.push_back(SpatialWork{nd.spJob, (int)n, 0, 1});   // the chunk ends on silence: history only
 }
 
+// ---- DynamicsCompressorNode (include/graphaudio_hip.h) ---------------------------------------------------
+// The parameters of one block, per the definition: the timeline's value at the block's start, clamped to the range, widened.
+static CompressorParams compressorParamsAt(const NodeS& nd, double t, int sampleRate) {
+  float v[GA_COMPRESSOR_PARAM_COUNT];
+  for (int p = 0; p < GA_COMPRESSOR_PARAM_COUNT; p++) {
+    const ParamS& ps = nd.params[p];
+    const float raw = ps.events.empty() ? ps.value : param_value_at(ps.events.data(), (int)ps.events.size(), ps.value, t);
+    v[p] = clamp_ref(raw, ps.minv, ps.maxv);
+  }
+  return compressor_params(v, (double)sampleRate);
+}
+static_assert(GA_COMPRESSOR_THRESHOLD == 0 && GA_COMPRESSOR_KNEE == 1 && GA_COMPRESSOR_RATIO == 2 && GA_COMPRESSOR_ATTACK == 3 &&
+              GA_COMPRESSOR_RELEASE == 4 && GA_COMPRESSOR_MAKEUP_GAIN == 5, "compressor_params (ga_kernels.hpp) restates the parameter order");
+
+// One job per segment (a level's launches run segment after segment, so yL passes from job to job in time order) over a per-block
+// parameter table that is made once per chunk -- one entry when no parameter is on a timeline.  The parameters do not cut segments.
+// A silent segment gets a job while yL may be non-zero: the state still moves.
+void Context::planCompressor(NodePlanCtx& k) {
+  Exec& ex = k.ex; const size_t si = k.si; const Segment& sg = k.sg; const NodeSeg& ns = k.ns; CompressorS& nd = rec<CompressorS>(k.nd); Views& ov = k.ov;
+  const bool silent = ns.ins[0].silent;
+  if (silent && !nd.cmpMoved) return;   // yL is 0 and stays 0
+  if (!nd.cmpState) {
+    nd.cmpState = (double*)dalloc(sizeof(double));
+    GA_HIP(hipMemsetAsync(nd.cmpState, 0, sizeof(double), stream));
+  }
+  bool moving = false;
+  for (const ParamS& ps : nd.params) moving = moving || !ps.events.empty();
+  if (nd.cmpSeq != chunkSeq || nd.cmpExec != &ex) {   // the node's first job in this chunk: its parameter table
+    nd.cmpSeq = chunkSeq;
+    nd.cmpExec = &ex;
+    std::vector<CompressorParams> tab((size_t)(moving ? k.r.n : 1));
+    for (size_t b = 0; b < tab.size(); b++) tab[b] = compressorParamsAt(nd, k.r.bt[b], sampleRate);
+    nd.cmpParOff = ex.plan.putv(tab);
+  }
+  CompressorSeg cs{};
+  cs.b0 = (int)sg.b0;
+  cs.nb = (int)(sg.b1 - sg.b0);
+  cs.nch = silent ? 0 : std::min(std::max(ns.ins[0].bufCh, 1), 2);
+  if (!silent) {
+    auto iv = ex.resolveInput((int)si, ns, 0, false, nullptr);
+    for (int ch = 0; ch < cs.nch; ch++) {
+      cs.in[ch] = (ch < (int)iv.size() && iv[ch]) ? iv[ch] : zeros;
+      cs.out[ch] = ex.nodeOut(ns.id, ch);
+      ov[ch] = cs.out[ch];
+    }
+    nd.cmpMoved = true;
+  }
+  CompressorJob j{};
+  j.seg_off = ex.plan.put(&cs, sizeof(cs));
+  j.par_off = nd.cmpParOff;
+  j.state = nd.cmpState;
+  j.nseg = 1;
+  j.par_stride = moving ? 1 : 0;
+  ex.compressorJobs.push_back(j);
+}
+
 // The per-sample table of a resampler trajectory on the device, up to (excluding) block `upto`: what extend() left in `pending` is
 // appended (through the chunk's tables: a plan entry in front of the launches that read it), the buffer doubles when it is full.
 bool Context::ensureResampleSamples(Exec& ex, Resampler& rs, int64_t upto) {
@@ -1006,6 +1062,7 @@ void Context::chunkPlanNodes(ChunkRun& r, int d) {
         case GA_NODE_DELAY: planDelay(k); break;
         case GA_NODE_STEREO_PANNER: planStereoPanner(k); break;
         case GA_NODE_SPATIAL_PANNER: planSpatialPanner(k); break;
+        case GA_NODE_DYNAMICS_COMPRESSOR: planCompressor(k); break;
         case GA_NODE_BUFFER_SOURCE: planBufferSource(k); break;
         case GA_NODE_STREAM_SOURCE: planStreamSource(k); break;
         case GA_NODE_GAIN: planGain(k); break;

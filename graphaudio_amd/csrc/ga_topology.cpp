@@ -73,6 +73,9 @@ double loopGain(const NodeTable& nodes, const int* loop, size_t n) {
       case GA_NODE_CONVOLVER: bound *= rec<ConvolverS>(mn).normalize ? 2.0 : 1e9; break;   // (normalised responses: broadband gain well below 1, peaks unknown)
       case GA_NODE_STEREO_PANNER: bound *= 2.0; break;                    // (oL = inL + inR * gainL)
       case GA_NODE_SPATIAL_PANNER: bound *= (double)rec<SpatialPannerS>(mn).spGainBound; break;   // (sum |F| + |D| <= max(1, sum |h|): g <= 1, the weights sum to 1)
+      case GA_NODE_DYNAMICS_COMPRESSOR:   // (g = 10^((M - yL) / 20) with yL >= 0 to rounding: at most the makeup gain)
+        bound *= moving ? 100.0 : std::max(1.0, std::pow(10.0, (double)std::min(std::max(mn.params[GA_COMPRESSOR_MAKEUP_GAIN].value, -40.f), 40.f) / 20.0));
+        break;
       default: break;
     }
   }

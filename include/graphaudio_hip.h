@@ -85,8 +85,27 @@ enum { /* node types creatable through ga_node_create; the destination is always
      band factor becomes a plain gain, the rest a three-band EQ of the input in front of the binaural stage (one-pole bands at 800 Hz
      and 8 kHz; DESIGN.md "SpatialPannerNode", "Occlusion and transmission").  With 0, ga_render answers GA_ERR_UNSUPPORTED where
      occlusion is above 0 in a block of the chunk.  A signal on occlusion needs "spatial_param_signals" = 1 as well. */
-  GA_NODE_SPATIAL_PANNER = 12
+  GA_NODE_SPATIAL_PANNER = 12,
+  /* DynamicsCompressorNode: this library's own definition (the reference has no such node).  One input
+     (2 channels, clamped-max, speakers), one output with the input's channel count of the block (1 or 2).  Params, all k-rate, the
+     value of a block is the timeline's at the block's start, clamped to the range when used:
+       GA_COMPRESSOR_THRESHOLD   default -24     -100 .. 0   dB        GA_COMPRESSOR_ATTACK       default 0.003   0 .. 1   s
+       GA_COMPRESSOR_KNEE        default  30        0 .. 40  dB        GA_COMPRESSOR_RELEASE      default 0.25    0 .. 1   s
+       GA_COMPRESSOR_RATIO       default  12        1 .. 20            GA_COMPRESSOR_MAKEUP_GAIN  default 0     -40 .. 40  dB
+     Per block, in double: T, W, R, M the clamped float values; aA = attack > 0 ? exp(-1 / (attack * fs)) : 0, aR likewise from release.
+     Per frame n, in double: a = max over channels of |x_c[n]| (exact in float); xG = 20 log10(max(a, 1e-6)); d = xG - T;
+       yG = xG                                       if 2 d < -W
+          = xG + (1/R - 1) (d + W/2)^2 / (2 W)       if W > 0 and |2 d| <= W
+          = T + d / R                                otherwise;
+     xL = xG - yG; yL = xL > yLprev ? aA yLprev + (1 - aA) xL : aR yLprev + (1 - aR) xL (products and sums rounded separately);
+     g = (float)pow(10, (M - yL) / 20) -- the one rounding to float -- and y_c[n] = x_c[n] * g as a float product.  yL is one double
+     per node, 0 at first, carried across chunks and render calls; over silent input it decays by aR per frame.  No look-ahead, no
+     added latency, no adaptive release, no automatic makeup, no `reduction` read-back.  ga_node_connect_param on one of the six
+     parameters returns GA_ERR_UNSUPPORTED (the message names the parameter). */
+  GA_NODE_DYNAMICS_COMPRESSOR = 13
 };
+enum { GA_COMPRESSOR_THRESHOLD = 0, GA_COMPRESSOR_KNEE = 1, GA_COMPRESSOR_RATIO = 2, GA_COMPRESSOR_ATTACK = 3, GA_COMPRESSOR_RELEASE = 4,
+       GA_COMPRESSOR_MAKEUP_GAIN = 5, GA_COMPRESSOR_PARAM_COUNT = 6 };
 enum { GA_DISTANCE_LINEAR = 0, GA_DISTANCE_INVERSE = 1, GA_DISTANCE_EXPONENTIAL = 2 };   /* SpatialPannerNode.DistanceModelType, SpatialPannerNode.cs:42-47 */
 enum { GA_SPATIAL_PARAM_COUNT = 17, GA_SPATIAL_DISTANCE_MODEL = 17, GA_SPATIAL_HRIR_AZIMUTHS = 18 };
 enum { GA_STREAM_PLAYING = 0, GA_STREAM_PAUSED = 1, GA_STREAM_STOPPED = 2 };   /* StreamState, AudioStreamSourceNodeBase.cs:12-17 */
