@@ -531,7 +531,8 @@ class StereoPannerNode(AudioNode):  # Nodes/StereoPannerNode.cs:9-163
 
 class DynamicsCompressorNode(AudioNode):
     """A bus compressor / limiter: this library's own definition (include/graphaudio_hip.h) -- the reference
-    has no such node, and the CPU oracle refuses to create one (ArgumentException).  One input (2 channels, clamped-max, speakers),
+    has no such node; the CPU oracle states the same definition once more in double precision and is pinned to the float64 model
+    of the tests.  One input (2 channels, clamped-max, speakers),
     one output with the input's channel count; the channels share one gain (the level is the larger magnitude).  All six parameters
     are k-rate and take values and timelines; connecting a signal to one raises NotSupportedException.  No look-ahead, no adaptive
     release, no automatic makeup gain, no ``reduction`` read-back."""

@@ -12,6 +12,9 @@
 // restatement is pinned only by independent analytic models (numpy/scipy; tests/test_oracle_*.py and
 // tests/golden/).  It is labelled "restatement", never "the reference".
 //
+// One node restates nothing: DynamicsCompressorNode is this project's own definition (the reference has
+// none), stated here a second time so that graphs with compressors have a CPU side to compare with.
+//
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.  The
 // product (graphaudio_amd/, libgraphaudio_hip.so) never links, imports or calls it.
 //
@@ -1736,6 +1739,65 @@ struct DelayNode : Node {
   void onDispose() override { out.reset(); }
 };
 
+// ---- DynamicsCompressorNode: THE PROJECT'S OWN DEFINITION, NOT A RESTATEMENT OF THE REFERENCE ----
+// The reference has no dynamics node.  Everything else in this file restates reference code; this node states the definition of
+// include/graphaudio_hip.h / DESIGN.md section 2g once more, statement for statement (steps 1-7 there), in double precision --
+// as tests/_compressor_model.py does in numpy, which pins it (tests/test_oracle_compressor.py).  It does not depend on
+// GAO_DOUBLE_TRIG: both builds hold the same node.
+struct DynamicsCompressorNode : Node {
+  BufPtr out;
+  double yL = 0.0;  // the level detector's state: moves only in blocks in which the node is pulled
+  DynamicsCompressorNode(Context* c, int id) : Node(c, id, GA_NODE_DYNAMICS_COMPRESSOR, 1, 1) {
+    inputs[0]->setChannelCount(2);
+    inputs[0]->mode = GA_COUNT_MODE_CLAMPED_MAX;
+    inputs[0]->interpretation = GA_INTERP_SPEAKERS;
+    createParam(-24.f, -100.f, 0.f, false);  // GA_COMPRESSOR_THRESHOLD, dB
+    createParam(30.f, 0.f, 40.f, false);     // GA_COMPRESSOR_KNEE, dB
+    createParam(12.f, 1.f, 20.f, false);     // GA_COMPRESSOR_RATIO
+    createParam(0.003f, 0.f, 1.f, false);    // GA_COMPRESSOR_ATTACK, s
+    createParam(0.25f, 0.f, 1.f, false);     // GA_COMPRESSOR_RELEASE, s
+    createParam(0.f, -40.f, 40.f, false);    // GA_COMPRESSOR_MAKEUP_GAIN, dB
+  }
+  void process() override {
+    AudioBuffer* in = inputs[0]->buffer.get();
+    const int ch = in->channelCount;
+    if (!out || out->channelCount != ch) out = rent(ch);
+    // per block: the six values at the block's start (k-rate: Param::computeValues), clamped as floats, widened
+    double v[GA_COMPRESSOR_PARAM_COUNT];
+    for (int p = 0; p < GA_COMPRESSOR_PARAM_COUNT; p++)
+      v[p] = (double)Param::clampf(params[p]->computed[0], params[p]->minValue, params[p]->maxValue);
+    const double T = v[GA_COMPRESSOR_THRESHOLD], W = v[GA_COMPRESSOR_KNEE], R = v[GA_COMPRESSOR_RATIO], M = v[GA_COMPRESSOR_MAKEUP_GAIN];
+    const double at = v[GA_COMPRESSOR_ATTACK], rl = v[GA_COMPRESSOR_RELEASE], fs = (double)ctx->sampleRate;
+    const double aA = at > 0.0 ? std::exp(-1.0 / (at * fs)) : 0.0;
+    const double aR = rl > 0.0 ? std::exp(-1.0 / (rl * fs)) : 0.0;
+    if (in->silent) {  // silent out; the state still moves, by the model's own statement with xL = 0
+      out->clear();
+      for (int i = 0; i < kBlock; i++) yL = (0.0 > yL) ? aA * yL + (1.0 - aA) * 0.0 : aR * yL + (1.0 - aR) * 0.0;
+      outputs[0]->buffer = out;
+      return;
+    }
+    for (int i = 0; i < kBlock; i++) {
+      float a = 0.f;  // 1. the link: the largest magnitude over the channels, exact in float
+      for (int c = 0; c < ch; c++) a = std::max(a, std::fabs(in->span(c)[i]));
+      const double xG = 20.0 * std::log10(std::max((double)a, 1e-6));  // 2.
+      const double d = xG - T;                                           // 3.
+      double yG;
+      if (2.0 * d < -W) yG = xG;
+      else if (W > 0.0 && std::fabs(2.0 * d) <= W) {
+        const double q = d + W / 2.0;
+        yG = xG + ((1.0 / R - 1.0) * (q * q)) / (2.0 * W);
+      } else yG = T + d / R;
+      const double xL = xG - yG;                                         // 4.
+      yL = (xL > yL) ? aA * yL + (1.0 - aA) * xL : aR * yL + (1.0 - aR) * xL;  // 5.
+      const float g = (float)std::pow(10.0, (M - yL) / 20.0);            // 6. the one rounding to float
+      for (int c = 0; c < ch; c++) out->span(c)[i] = in->span(c)[i] * g;  // 7. a float product
+    }
+    out->markNonSilent();
+    outputs[0]->buffer = out;
+  }
+  void onDispose() override { out.reset(); }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1873,6 +1935,7 @@ int gao_node_create_ex(ga_context* ctx, int node_type, double arg, int* out_id) 
       case GA_NODE_OSCILLATOR: c.nodes.push_back(std::make_unique<OscillatorNode>(&c, id)); break;
       case GA_NODE_DELAY: c.nodes.push_back(std::make_unique<DelayNode>(&c, id, arg)); break;
       case GA_NODE_STREAM_SOURCE: c.nodes.push_back(std::make_unique<StreamNode>(&c, id)); break;
+      case GA_NODE_DYNAMICS_COMPRESSOR: c.nodes.push_back(std::make_unique<DynamicsCompressorNode>(&c, id)); break;  // (the project's own node)
       default: fail(GA_ERR_INVALID_ARGUMENT, "unknown node type");
     }
     *out_id = id;
@@ -1920,6 +1983,11 @@ int gao_node_connect_param(ga_context* ctx, int src, int dst_node, int dst_param
     Node* s = getNode(c, src);
     Param* p = getParam(c, dst_node, dst_param);
     if (output_index < 0 || output_index >= (int)s->outputs.size()) fail(GA_ERR_OUT_OF_RANGE, "outputIndex");  // :88-89
+    if (getNode(c, dst_node)->type == GA_NODE_DYNAMICS_COMPRESSOR) {  // as ga_node_connect_param: values and timelines only
+      static const char* const names[GA_COMPRESSOR_PARAM_COUNT] = {"threshold", "knee", "ratio", "attack", "release", "makeupGain"};
+      fail(GA_ERR_UNSUPPORTED, std::string("DynamicsCompressorNode: a signal connected to parameter ") + names[dst_param] +
+                                   " is refused (the node's parameters take values and timelines)");
+    }
     Output* o = s->outputs[output_index].get();
     c.executeOrPost([o, p]() { o->connectTo(p->input.get()); });  // AudioParam.ConnectFrom, AudioParam.cs:73-77
   });

@@ -2,15 +2,91 @@
 import numpy as np
 
 from graphaudio_amd import (AudioBufferSourceNode, BiQuadFilterNode, ChannelCountMode, ChannelInterpretation, ChannelMergerNode,
-                            ChannelSplitterNode, ConstantSourceNode, ConvolverNode, DelayNode, FilterType, GainNode, OscillatorNode,
-                            OscillatorType, PlayableAudioBuffer, StereoPannerNode)
+                            ChannelSplitterNode, ConstantSourceNode, ConvolverNode, DelayNode, DynamicsCompressorNode, FilterType, GainNode,
+                            OscillatorNode, OscillatorType, PlayableAudioBuffer, StereoPannerNode)
 
 SR = 48000
+RATE_MOD_SEEDS = 80000
+COMPRESSOR_SEEDS = 90000
 
 
-def build_random_graph(ctx, seed, frames, keep=None, handles=None):
+class CompressorDraws:
+    """Seeds >= 90000: DynamicsCompressorNodes, drawn from a generator of their own (older seeds keep their graphs).  `stand_in`
+    builds a unity GainNode with the compressor's input settings in each one's place, from the same draws: the same graph without
+    the compression.  What was built is reported in handles["compressors"]: one dict per node with `node`, `place` (bus / chain /
+    param / rate / loop_delay / loop_nodelay), `cases` (defaults / timeline / attack0 / release0 / ratio1 / knee0), `next` (where a
+    replug connects it: "dest", "chain" or a node) and `loop_safe` (makeupGain stays <= 0: the node may sit on a feedback loop)."""
+
+    def __init__(self, seed, dur, stand_in, handles):
+        self.on = seed >= COMPRESSOR_SEEDS
+        self.rng = np.random.default_rng(seed + 90210)
+        self.dur = dur
+        self.stand_in = stand_in
+        self.built = handles.setdefault("compressors", []) if handles is not None else []
+        # half of the seeds build no feedback loops, so that their graphs render in chunks of several blocks: a graph with a loop that
+        # cannot be cut at a delay renders block by block, and the planner's per-chunk state of a compressor would hardly be exercised
+        self.loops = not self.on or bool(self.rng.random() < 0.5)
+
+    def chance(self, p):
+        return self.on and bool(self.rng.random() < p)
+
+    def node(self, ctx, place, next_="chain", loop_safe=False):
+        rng = self.rng
+        cases = set()
+        values = {}
+        if rng.random() < 0.25:
+            cases.add("defaults")
+            if loop_safe:
+                values["MakeupGain"] = 0.0
+        else:
+            values["Threshold"] = float(rng.choice([rng.uniform(-60.0, -10.0), rng.uniform(-100.0, 0.0)]))
+            values["Knee"] = float(rng.choice([0.0, rng.uniform(0.0, 40.0)]))
+            values["Ratio"] = float(rng.choice([1.0, rng.uniform(1.0, 20.0), rng.uniform(1.0, 20.0)]))
+            values["Attack"] = float(rng.choice([0.0, rng.uniform(0.0, 0.02), rng.uniform(0.0, 1.0)]))
+            values["Release"] = float(rng.choice([0.0, rng.uniform(0.0, 0.1), rng.uniform(0.0, 1.0)]))
+            values["MakeupGain"] = float(rng.uniform(-12.0, 0.0) if loop_safe else rng.uniform(-12.0, 12.0))
+            cases |= {c for c, k, v in (("attack0", "Attack", 0.0), ("release0", "Release", 0.0), ("ratio1", "Ratio", 1.0),
+                                        ("knee0", "Knee", 0.0)) if values[k] == v}
+        timeline = None
+        if rng.random() < 0.3:
+            name = "Threshold" if loop_safe or rng.random() < 0.5 else "MakeupGain"
+            lo, hi = (-60.0, 0.0) if name == "Threshold" else (-12.0, 12.0)
+            t0 = float(rng.uniform(0, self.dur * 0.5))
+            timeline = (name, float(rng.uniform(lo, hi)), t0, float(rng.uniform(lo, hi)), t0 + float(rng.uniform(0.003, self.dur * 0.5)))
+            cases.add("timeline")
+        if self.stand_in:
+            n = GainNode(ctx)
+            n.Inputs[0].SetChannelCount(2)
+            n.Inputs[0].SetChannelCountMode(ChannelCountMode.ClampedMax)
+            n.Inputs[0].SetChannelInterpretation(ChannelInterpretation.Speakers)
+            n.stands_in = True
+            return n
+        n = DynamicsCompressorNode(ctx)
+        for k, v in values.items():
+            getattr(n, k).Value = v
+        if timeline:
+            name, v0, t0, v1, t1 = timeline
+            getattr(n, name).SetValueAtTime(v0, t0)
+            getattr(n, name).LinearRampToValueAtTime(v1, t1)
+        self.built.append(dict(node=n, place=place, cases=cases, next=next_, loop_safe=loop_safe))
+        return n
+
+    def placed(self, n, place):
+        """`n` turned out to sit on a feedback loop: report that too"""
+        for rec in self.built:
+            if rec["node"] is n:
+                rec.setdefault("also", set()).add(place)
+
+
+def _is_gain(n):
+    """a GainNode of the graph proper (a compressor's stand-in is wired like the compressor, never like a gain)"""
+    return isinstance(n, GainNode) and not getattr(n, "stands_in", False)
+
+
+def build_random_graph(ctx, seed, frames, keep=None, handles=None, stand_in=False):
     """Sources -> random chains (gain / biquad / convolver) -> optional shared bus nodes -> destination."""
     rng = np.random.default_rng(seed)
+    cmp = CompressorDraws(seed, frames / SR, stand_in, handles)
     rng2 = np.random.default_rng(seed + 7777)   # later additions draw from their own stream: old seeds keep their graphs
     rng3 = np.random.default_rng(seed + 31337)  # round 3: unity gains (handed on without a kernel) -- seeds >= 20000 only
     unity = seed >= 20000
@@ -31,7 +107,10 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
             g.Inputs[0].SetChannelCount(int(rng.choice([1, 2])))
         if rng.random() < 0.3:
             g.Inputs[0].SetChannelCountMode(ChannelCountMode(int(rng.integers(0, 3))))
-        g.Connect(ctx.Destination)
+        if cmp.chance(0.6):   # a bus compressor: the node's intended use
+            g.Connect(cmp.node(ctx, "bus", next_="dest")).Connect(ctx.Destination)
+        else:
+            g.Connect(ctx.Destination)
         buses.append(g)
     nvoices = int(rng.integers(2, 10))
     earlier_nodes = []
@@ -111,6 +190,11 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
             chain_of_voice.append(n)
             if handles is not None:
                 handles.setdefault(type(n).__name__, []).append(n)
+            if cmp.chance(0.2):   # a compressor as a chain element (it may land on a feedback loop below: makeupGain <= 0)
+                n = cmp.node(ctx, "chain", loop_safe=True)
+                node.Connect(n)
+                node = n
+                chain_of_voice.append(n)
         # the remaining pure-Core nodes (drawn from rng2: the graphs of old seeds keep their shape and gain a tail)
         extra = float(rng2.random())
         if seed >= 40000 and extra >= 0.30 and rng4.random() < 0.3:
@@ -161,7 +245,7 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
         # seeds >= 50000 (round 4): FEEDBACK -- a later node of the chain feeds an earlier one through a gain below 1.  The reference
         # renders such loops with an implicit one-block delay on the edge that closes them (Nodes/AudioNode.cs:153-156), the device
         # path one block per chunk since round 4.  (Drawn from a generator of their own: older seeds keep their graphs.)
-        if seed >= 50000:
+        if seed >= 50000 and cmp.loops:
             rng5 = np.random.default_rng(seed * 31 + v)
             inner = [n for n in chain_of_voice[1:] if not isinstance(n, (ChannelSplitterNode, ChannelMergerNode))]
             if len(inner) >= 2 and rng5.random() < 0.6:
@@ -170,12 +254,15 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
                 fb = GainNode(ctx)
                 fb.Gain.Value = float(rng5.uniform(0.05, 0.35))
                 inner[i1].Connect(fb)
-                if rng5.random() < 0.25 and isinstance(inner[i0], GainNode):
+                if rng5.random() < 0.25 and _is_gain(inner[i0]):
                     fb.Connect(inner[i0].Gain)      # the loop closes through a parameter
                 else:
                     fb.Connect(inner[i0])
+                    for n in inner[i0:i1 + 1]:
+                        if isinstance(n, DynamicsCompressorNode):
+                            cmp.placed(n, "loop_delay" if any(isinstance(m, DelayNode) for m in inner[i0:i1 + 1]) else "loop_nodelay")
                 # (not handed to the session's edit list: a feedback gain edited up to 1.2 makes the loop blow up)
-            elif len(inner) == 1 and isinstance(inner[0], (GainNode, DelayNode, BiQuadFilterNode)) and rng5.random() < 0.4:
+            elif len(inner) == 1 and (_is_gain(inner[0]) or isinstance(inner[0], (DelayNode, BiQuadFilterNode))) and rng5.random() < 0.4:
                 fb = GainNode(ctx)              # node -> gain -> node
                 fb.Gain.Value = float(rng5.uniform(0.05, 0.35))
                 inner[0].Connect(fb)
@@ -237,7 +324,7 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
                 continue
             targets = []
             for n in voice_chains[j][1:]:
-                if isinstance(n, GainNode): targets.append((n.Gain, 0.3))
+                if _is_gain(n): targets.append((n.Gain, 0.3))
                 elif isinstance(n, BiQuadFilterNode): targets.append((n.Frequency, 300.0))
                 elif isinstance(n, DelayNode): targets.append((n.DelayTime, 0.003))
                 elif isinstance(n, StereoPannerNode): targets.append((n.Pan, 0.5))
@@ -249,7 +336,10 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
             frm = srcs[int(rng4.integers(0, len(srcs)))]
             dg = GainNode(ctx)
             dg.Gain.Value = float(depth * rng4.uniform(0.3, 2.0))
-            frm.Connect(dg)
+            if cmp.chance(0.4):   # a compressor's output into the parameter
+                frm.Connect(cmp.node(ctx, "param", next_=dg)).Connect(dg)
+            else:
+                frm.Connect(dg)
             dg.Connect(prm)
             if handles is not None:
                 handles.setdefault("mod_gains", []).append(dg)
@@ -260,17 +350,40 @@ def build_random_graph(ctx, seed, frames, keep=None, handles=None):
         rng6 = np.random.default_rng(seed * 13 + 1)
         for chain in voice_chains:
             if rng6.random() < 0.6:
-                rate_modulator(ctx, rng6, chain[0], frames / SR, handles)
+                rate_modulator(ctx, rng6, chain[0], frames / SR, handles, cmp if cmp.on else None)
+    # seeds >= 90000: a voice of its own with a compressor inside a feedback loop, source -> gain -> [delay] -> compressor -> back into
+    # the gain through a gain below 1 (with a delay of two blocks or more the loop can be cut there; without one it renders block by block)
+    if cmp.loops and cmp.chance(0.6):
+        r = cmp.rng
+        s = AudioBufferSourceNode(ctx)
+        n = int(r.integers(128 * 4, frames + 300))
+        s.Buffer = PlayableAudioBuffer.FromChannelArrays([(r.standard_normal(n) * 0.3).astype(np.float32) for _ in range(int(r.choice([1, 2])))], SR)
+        gi = GainNode(ctx)
+        gi.Gain.Value = float(r.uniform(0.3, 0.9))
+        s.Connect(gi)
+        node, place = gi, "loop_nodelay"
+        if r.random() < 0.5:
+            dl = DelayNode(ctx, 0.05)
+            dl.DelayTime.Value = float(r.choice([r.uniform(0, 0.004), r.uniform(0.0055, 0.012)]))
+            node.Connect(dl)
+            node, place = dl, "loop_delay"
+        cm = cmp.node(ctx, place, loop_safe=True)
+        node.Connect(cm)
+        fb = GainNode(ctx)
+        fb.Gain.Value = float(r.uniform(0.05, 0.35))
+        cm.Connect(fb).Connect(gi)
+        cm.Connect(buses[0] if buses and r.random() < 0.5 else ctx.Destination)
+        s.Start(float(r.choice([0.0, r.uniform(0, frames / SR * 0.4)])))
+        if handles is not None:
+            handles.setdefault("sources", []).append(s)
     if handles is not None:
         handles.update(buses=buses, shared_ir=shared_ir)
     return dest_ch
 
 
-RATE_MOD_SEEDS = 80000
-
-
-def rate_modulator(ctx, rng, s, dur, handles=None):
-    """An oscillator or a looping noise buffer through a depth gain (0.02 - 0.3) into `s.PlaybackRate`; returns the depth gain."""
+def rate_modulator(ctx, rng, s, dur, handles=None, cmp=None):
+    """An oscillator or a looping noise buffer through a depth gain (0.02 - 0.3) into `s.PlaybackRate`; returns the depth gain.
+    With `cmp` (CompressorDraws), a compressor may sit between the modulator and the depth gain: its cone holds the modulator alone."""
     if rng.random() < 0.6:
         m = OscillatorNode(ctx)
         m.Type = OscillatorType(int(rng.integers(0, 4)))
@@ -282,7 +395,10 @@ def rate_modulator(ctx, rng, s, dur, handles=None):
         m.Loop = True
     dg = GainNode(ctx)
     dg.Gain.Value = float(rng.uniform(0.02, 0.3))
-    m.Connect(dg)
+    if cmp is not None and cmp.chance(0.4):
+        m.Connect(cmp.node(ctx, "rate", next_=dg)).Connect(dg)
+    else:
+        m.Connect(dg)
     dg.Connect(s.PlaybackRate)
     when = float(rng.choice([0.0, rng.uniform(0, dur * 0.5)]))
     m.Start(when)
@@ -293,11 +409,12 @@ def rate_modulator(ctx, rng, s, dur, handles=None):
     return dg
 
 
-def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None):
+def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None, handles=None):
     """Render a random graph in random pieces and EDIT it between the pieces (parameter writes and automation, stop,
     new voices, dispose, rewiring, impulse-response swaps, audio-rate modulation, channel settings).  The same seed
-    replays the same session on any context.  Returns (output, log of (piece, action, exception type or None))."""
-    h = {}
+    replays the same session on any context.  Returns (output, log of (piece, action, exception type or None)).
+    `handles` (a dict) receives what build_random_graph reports and, under "cmp_edits", the compressor edits that were made."""
+    h = handles if handles is not None else {}
     ch = build_random_graph(ctx, seed, frames, keep=keep, handles=h)
     rng = np.random.default_rng(seed ^ 0x5EED)
     out = np.zeros((ch, frames), np.float32)
@@ -533,6 +650,62 @@ def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None)
                     s.PlaybackRate.LinearRampToValueAtTime(float(rng7.uniform(0.5, 2.0)), now + float(rng7.uniform(0.01, 0.04)))
         return kind
 
+    # seeds >= 90000: edits of DynamicsCompressorNodes -- a parameter's Value, a timeline, unplug / replug, dispose, and a signal
+    # connected to a parameter, which both sides refuse with the same exception.  A generator of its own: older sessions keep theirs.
+    rng9 = np.random.default_rng(seed ^ 0xC0A9)
+    cmp_parked = []
+    cmp_edits = h.setdefault("cmp_edits", [])
+    cmp_kind = [None]
+
+    def cmp_act(now):
+        kind = str(rng9.choice(["cmp_value", "cmp_sched", "cmp_unplug", "cmp_dispose", "cmp_signal"], p=[0.3, 0.2, 0.25, 0.05, 0.2]))
+        cmp_kind[0] = kind
+        live = [c for c in h.get("compressors", []) if id(c["node"]) not in dead]
+        if not live:
+            return kind + "_none"
+        if kind == "cmp_unplug" and cmp_parked and rng9.random() < 0.5:
+            c = cmp_parked.pop(int(rng9.integers(0, len(cmp_parked))))
+            if id(c["node"]) in dead:
+                return "cmp_replug_dead"
+            nxt = c["next"]   # a chain compressor goes to a bus or the destination, one in front of a parameter or a rate back to its depth
+            if nxt == "chain":   # gain, a bus compressor to the destination only (bus -> compressor -> bus: a loop without a gain below 1)
+                buses = [b for b in h["buses"] if id(b) not in dead]
+                nxt = buses[int(rng9.integers(0, len(buses)))] if buses and rng9.random() < 0.5 else "dest"
+            c["node"].Connect(ctx.Destination if isinstance(nxt, str) or id(nxt) in dead else nxt)
+            cmp_edits.append("cmp_replug")
+            return "cmp_replug"
+        c = live[int(rng9.integers(0, len(live)))]
+        n = c["node"]
+        if kind == "cmp_value":
+            name, _, mn, mx = DynamicsCompressorNode.PARAMS[int(rng9.integers(0, 6))]
+            if name == "makeupGain":
+                mn, mx = -12.0, (0.0 if c["loop_safe"] else 12.0)
+            getattr(n, name[0].upper() + name[1:]).Value = float(rng9.choice([mn, mx, rng9.uniform(mn, mx), rng9.uniform(mn, mx)]))
+        elif kind == "cmp_sched":
+            name = "Threshold" if c["loop_safe"] or rng9.random() < 0.5 else "MakeupGain"
+            lo, hi = (-60.0, 0.0) if name == "Threshold" else (-12.0, 12.0)
+            t = now + float(rng9.uniform(0, 0.02))
+            getattr(n, name).SetValueAtTime(float(rng9.uniform(lo, hi)), t)
+            getattr(n, name).LinearRampToValueAtTime(float(rng9.uniform(lo, hi)), t + float(rng9.uniform(0.005, 0.04)))
+        elif kind == "cmp_unplug":
+            if any(c is q for q in cmp_parked):
+                return "cmp_unplug_twice"
+            n.Disconnect()
+            cmp_parked.append(c)
+        elif kind == "cmp_dispose":
+            n.Dispose()
+            dead.add(id(n))
+        else:   # refused: NotSupportedException on both sides, and the graph is as it was
+            cands = [x for x in sources + gains if id(x) not in dead]
+            if not cands:
+                return "cmp_signal_none"
+            name = DynamicsCompressorNode.PARAMS[int(rng9.integers(0, 6))][0]
+            cmp_edits.append(kind)
+            cands[int(rng9.integers(0, len(cands)))].Connect(getattr(n, name[0].upper() + name[1:]))
+        if kind != "cmp_signal":
+            cmp_edits.append(kind)
+        return kind
+
     global last_pieces, details
     last_pieces = []
     details = []
@@ -561,4 +734,9 @@ def run_random_session(ctx, seed, frames=128 * 48, max_piece=128 * 9, keep=None)
                 log.append((piece, rate_act(ctx.CurrentTime), None))
             except Exception as e:
                 log.append((piece, "?", type(e).__name__))
+        if seed >= COMPRESSOR_SEEDS and rng9.random() < 0.8:
+            try:
+                log.append((piece, cmp_act(ctx.CurrentTime), None))
+            except Exception as e:
+                log.append((piece, cmp_kind[0], type(e).__name__))
     return out, log

@@ -2,6 +2,7 @@
 import os
 import re
 
+import numpy as np
 import pytest
 
 from tests import _compressor_model as M
@@ -26,12 +27,26 @@ def test_python_class_has_the_definitions_parameters_and_defaults():
 
 
 def test_python_parameters_are_krate_audio_params_in_native_order():
-    """on the CPU oracle's API a node of this type cannot be created (the oracle does not know it): the normal exception"""
-    from graphaudio_amd import ArgumentException, DynamicsCompressorNode
+    """on the CPU oracle's API a node type the oracle does not know cannot be created: the normal exception.  The compressor it
+    knows (tests/test_oracle_compressor.py): six k-rate parameters in the native order with the header's defaults"""
+    from graphaudio_amd import ArgumentException, DynamicsCompressorNode, SpatialPannerNode
     from tests._oracle import OracleContext
     ctx = OracleContext(48000)
     with pytest.raises(ArgumentException):
-        DynamicsCompressorNode(ctx)
+        SpatialPannerNode(ctx)
+    on_oracle = DynamicsCompressorNode(ctx)
+    hdr = _header()
+    for i, (name, default, mn, mx) in enumerate(DEFINITION):
+        p = [on_oracle.Threshold, on_oracle.Knee, on_oracle.Ratio, on_oracle.Attack, on_oracle.Release, on_oracle.MakeupGain][i]
+        assert p._index == i and p.Name == name
+        assert p.Value == np.float32(default)   # (read back through gao_param_get_value: the oracle's own default)
+        m = re.search(r"GA_COMPRESSOR_%s\s+default\s+(-?[\d.]+)" % HEADER_NAMES[i], hdr)
+        assert m and float(m.group(1)) == default, name
+        for v, want in ((mn - 1.0, mn), (mx + 1.0, mx)):   # ... and the oracle's own range
+            p.Value = v
+            assert p.Value == want
+    with pytest.raises(ArgumentException):
+        ctx._call("param_set_value", on_oracle.NodeId, 6, 0.0)   # (there is no seventh)
 
     # the parameter objects, on a context stand-in that records the calls instead of making them
     class Recorder:
